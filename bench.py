@@ -28,6 +28,9 @@ MFMA_PEAK_TFLOPS = 2500.0   # dense bf16/fp16 MFMA peak, /opt/skills/guides/MI35
 # all-zero operands: 2448): tools/mfma_power.cpp, profiles/r02_mfma_power.log.  Reported beside `frac`, never instead of it.
 MFMA_DENSE_SUSTAINED_TFLOPS = 1899.0
 PMC_SUMMARY = "r05_gemm_pmc_summary.json"   # profiles/: counters of the current code (tools/run_gemm_pmc.sh), see `traffic_source`
+DUMP_BYTES = 48 << 20       # --dump-outputs: bytes of float32 written at most (whole output, or a seeded sample of it)
+DUMP_SEED = 1234
+DUMP_MIN_COLS = 16
 
 
 def model_cfg(H, K, T):
@@ -242,6 +245,35 @@ def cpu_baseline(sd_cpu, cfg, H, K, px_s, px_d):
                        % (cores, n_v, t_v, runs[0], runs[2], t_c))
 
 
+def dump_outputs(out, d):
+    """`--dump-outputs DIR`: what the last timed step returned to its caller - the emitted tokens [n, H] of encode_video (the
+    inputs_embeds rows under --via-mixin) - as float32 DIR/tokens.npy.  Past DUMP_BYTES a fixed sample is written instead: every
+    row at a seeded, sorted choice of columns, or (when fewer than DUMP_MIN_COLS columns would fit) a seeded, sorted choice of rows
+    at DUMP_MIN_COLS such columns.  The choice depends on n and H alone, so two builds that emit the same n compare element for
+    element.  Returns the file's path."""
+    import numpy as np
+    n, H = out.shape
+    rows = cols = None
+    if n * H * 4 > DUMP_BYTES:
+        rng = np.random.default_rng(DUMP_SEED)
+        c = min(H, DUMP_BYTES // (4 * n))
+        if c < DUMP_MIN_COLS:
+            c = DUMP_MIN_COLS
+            rows = np.sort(rng.choice(n, DUMP_BYTES // (4 * c), replace=False))
+        cols = np.sort(rng.choice(H, c, replace=False))
+    x = out
+    if rows is not None:
+        x = x.index_select(0, torch.from_numpy(rows).to(x.device))
+    if cols is not None:
+        x = x.index_select(1, torch.from_numpy(cols).to(x.device))
+    os.makedirs(d, exist_ok=True)
+    path = os.path.join(d, "tokens.npy")
+    np.save(path, x.float().cpu().numpy())
+    sys.stderr.write("bench.py: wrote %s: %s of the [%d, %d] output\n"
+                     % (path, "all" if x.shape == out.shape else "a [%d, %d] sample (seed %d)" % (tuple(x.shape) + (DUMP_SEED,)), n, H))
+    return path
+
+
 def pmc_leg(gemms, budget_s, H, live_gemm_ms):
     """The in-run counter leg (see the call site): -> (traffic bytes per launch, MFMA-busy fraction, MFMA-busy of the Q-Former's
     stacked K/V GEMM, provenance string, full per-shape summary) or None when it could not run."""
@@ -431,7 +463,12 @@ def main():
                     "step with config.tdc_frame_cap = T (N > 1: + config.tdc_shard_frames, every rank holds the whole video as the "
                     "reference's eval workers do); the JSON line says config.entry = \"mixin\"")
     ap.add_argument("--dump-gemm-shapes", default=None, help="write the GEMM launches of one step (for tools/gemm_pmc)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the last one returned "
+                    "(the emitted tokens) as float32 DIR/tokens.npy: the whole array, or past 48 MiB a seeded sample of it "
+                    "(dump_outputs); inputs and weights are seeded, so runs with the same arguments compare output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     for k in ("launch_timeout", "rank_timeout"):
         if getattr(args, k) < 0:
             setattr(args, k, 600.0 + 4.0 * (args.steps + args.warmup))
@@ -592,6 +629,8 @@ def main():
         dt = max(float(x.item()) for x in every)
     ms_per_step = dt / args.steps * 1e3
     fps = T * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     # ---- roofline of the dominant kernel (tdc_gemm MFMA kernel): one extra pass under the library's launch profiler
     # (tdc_profile_*: hipEvents recorded inside libtdc_hip.so around every GEMM / attention / LayerNorm / fused cross-attention

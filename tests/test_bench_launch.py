@@ -95,6 +95,54 @@ def test_rank_guard_ends_a_stuck_rank_with_124():
     assert r.returncode == 124 and "rank-timeout" in r.stderr
 
 
+def test_steps_below_one_is_an_error_message():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--no-cpu-baseline"], env=_env(),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps" in r.stderr and "Traceback" not in r.stderr
+
+
+def test_dump_outputs_writes_the_whole_output_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 tokens.npy, the whole array when it fits DUMP_BYTES, otherwise every row at a seeded choice of
+    columns (or, when too few columns fit, a seeded choice of rows at DUMP_MIN_COLS columns) - the same choice on every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    small = torch.randn(10, 64, generator=g).half()
+    got = np.load(bench.dump_outputs(small, str(tmp_path / "small")))
+    assert got.dtype == np.float32 and np.array_equal(got, small.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 << 10)
+    for n, H, shape in ((300, 512, (300, 54)), (4096, 512, (1024, 16))):
+        out = torch.randn(n, H, generator=g).half()
+        a = np.load(bench.dump_outputs(out, str(tmp_path / ("a%d" % n))))
+        b = np.load(bench.dump_outputs(out, str(tmp_path / ("b%d" % n))))
+        assert a.dtype == np.float32 and a.shape == shape and a.nbytes <= bench.DUMP_BYTES and np.array_equal(a, b)
+        full = out.float().numpy()
+        if shape[0] == n:           # every row: each dumped column is a column of the output
+            for j in range(a.shape[1]):
+                assert any(np.array_equal(a[:, j], full[:, k]) for k in range(H))
+        else:
+            assert np.isin(a, full).all()
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_and_steps(tmp_path):
+    """bench.py --steps K times K steps and writes the last one's emitted tokens: one row per emitted token, float32."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--frames", "64", "--steps", "2",
+                        "--warmup", "1", "--no-cpu-baseline", "--pmc", "off", "--dump-outputs", str(tmp_path)],
+                       env=_env(), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    res = json.loads(lines[0])
+    assert res["steps"] == 2 and res["ms_per_step"] > 0
+    a = np.load(str(tmp_path / "tokens.npy"))
+    assert a.dtype == np.float32 and a.shape[0] == res["config"]["emitted_tokens"] and 0 < a.shape[1] <= res["config"]["hidden"]
+    assert np.isfinite(a).all() and a.nbytes <= 64 << 20
+
+
 @pytest.mark.gpu
 def test_torchrun_form_of_the_drivers_scaling_run_on_one_gpu():
     """The driver's N > 1 command line - python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
