@@ -26,7 +26,8 @@ import numpy as np
 import torch
 
 from . import segment as seg
-from .pipeline import sample_indicator
+from .pipeline import (emission_plan, frame_indices, join_side_tower, precise_features, sample_indicator,
+                       select_segments_with, start_side_tower, text_prompt, visual_budget)
 
 
 def owner_of(frame, ranges):
@@ -124,8 +125,7 @@ class ShardedVideoEncoder:
         encodes (`siglip_frames`; `dino_frames` = the same - plus the next rank's first frame with halo=True, the
         re-encode-instead-of-exchange variant), and the per-second 0/1 vector the audio interleave needs.  Pure host
         integers: identical on every rank."""
-        cfg = self.e.cfg
-        idx = seg.uniform_indices(T0, min(seg.get_max_num_frames(budget_text_len, cfg), frame_cap))
+        idx = frame_indices(self.e.cfg, T0, budget_text_len, frame_cap)
         T = len(idx)
         lo, hi = seg.shard_ranges(T, self.world)[self.rank]
         want_halo = bool(halo)
@@ -193,13 +193,12 @@ class ShardedVideoEncoder:
             idx = self._maps[key] = torch.from_numpy(pairs).to(device)
         return e.compact_rows(recv, idx, cols)
 
-    def _refine_selection(self, band, sims, mns, eps, px_dino_local_halo, ranges, recompute_halo):
-        """a5 at the reference's precision, sharded (pipeline.encode_video_with does the same serially): the pairs of `band` - the
-        same list on every rank - are re-encoded by the engine's precise DINOv2 tower.  Pair i belongs to the rank that owns frame
-        i; it needs frame i + 1 as well, which for the last local frame is the right neighbour's first: that rank sends the precise
-        feature rows of its first frame (as the boundary exchange of step 1 does for the fast tower), unless the caller handed
-        this rank the halo frame's pixels (recompute_halo).  The refined values are all-gathered in band order; every rank then
-        runs the same host selection."""
+    def _refined_sims(self, band, px_dino_local_halo, ranges, recompute_halo):
+        """the `refine` of pipeline.select_segments_with, sharded: the pairs of `band` - the same list on every rank - are
+        re-encoded by the engine's precise DINOv2 tower.  Pair i belongs to the rank that owns frame i; it needs frame i + 1 as
+        well, which for the last local frame is the right neighbour's first: that rank sends the precise feature rows of its
+        first frame (as the boundary exchange of step 1 does for the fast tower), unless the caller handed this rank the halo
+        frame's pixels (recompute_halo).  -> the refined values of the whole band in band order, on every rank."""
         e, rank, world = self.e, self.rank, self.world
         lo, hi = ranges[rank]
         inband = set(band)
@@ -211,13 +210,7 @@ class ShardedVideoEncoder:
         cross = rank < world - 1 and hi > lo and (hi - 1) in inband                          # my last pair crosses the boundary
         if cross and recompute_halo:
             frames.add(hi)                                                                   # its pixels are local (row hi - lo)
-        frames = sorted(frames)
-        feats = {}
-        if frames:
-            idx = torch.tensor([f - lo for f in frames], device=px_dino_local_halo.device)
-            fp = e.precise_dino(px_dino_local_halo[idx])
-            Pp = fp.shape[0] // len(frames)
-            feats = {f: fp[j * Pp:(j + 1) * Pp] for j, f in enumerate(frames)}
+        feats = precise_features(e, px_dino_local_halo, sorted(frames), lo) if frames else {}
         if not recompute_halo:
             sends = [(feats[lo].contiguous(), rank - 1)] if send_first else []
             recvs = []
@@ -230,8 +223,7 @@ class ShardedVideoEncoder:
         dev = px_dino_local_halo.device
         local = e.pair_sims(feats, [(i, i + 1) for i in mine]) if mine else torch.zeros(0, dtype=torch.float32, device=dev)
         counts = [sum(1 for i in band if l <= i < h) for (l, h) in ranges]
-        refined = self._all_gather_var(local.to(torch.float32), counts).tolist()
-        return seg.select_refined(sims, mns, eps, band, refined)
+        return self._all_gather_var(local.to(torch.float32), counts).tolist()
 
     def encode_video(self, px_siglip_local, px_dino_local_halo, T, image_size, n_text_tokens, prompt_ids, audio=None,
                      sample_indices=None, recompute_halo=False):
@@ -253,26 +245,16 @@ class ShardedVideoEncoder:
             # Q-Former): this rank only takes part in the final all-gather
             assert T <= cfg.get("max_num_segments", 24) + 1
             Nf = self._tokens_per_frame(image_size, audio)
-            plan = seg.emit_plan(T, Nf, e.K, list(range(T)), cfg["tokenizer_model_max_length"] -
-                                 cfg.get("inference_max_length", 16) - n_text_tokens, cfg.get("add_static", True))
+            plan, learned = emission_plan(e, T, Nf, list(range(T)), visual_budget(cfg, n_text_tokens))
             pairs, _ = split_plan(plan, ranges, Nf, e.K)
-            if cfg.get("query_type", "Avg_pool") != "learned":
+            if not learned:
                 self.comm.exchange([], [])
             return self._gather_tokens(lambda out: None, [len(p) for p in pairs], e.H, e.dtype, px_siglip_local.device)
-        # engine.two_streams (small shards: bench.py switches it on at <= 128 frames per rank): the SigLIP tower runs on a side
-        # stream beside the DINOv2 tower, so the partly filled last tile rounds of one tower's GEMMs are filled by the other's
-        # workgroups (T = 64 on one GPU: +0.6-1.1 %; at 512 frames per launch the tails are too short to matter)
-        side, sig_early = None, None
-        if getattr(e, "two_streams", False) and px_siglip_local.is_cuda:
-            side = e.tower_stream() if hasattr(e, "tower_stream") else torch.cuda.Stream(device=px_siglip_local.device)
-            side.wait_stream(torch.cuda.current_stream(px_siglip_local.device))
-            with torch.cuda.stream(side):
-                sig_early = e.tower("siglip", px_siglip_local)
+        side_sig = start_side_tower(e, px_siglip_local)
         dino_all = e.tower("dino", px_dino_local_halo)
         P = dino_all.shape[0] // n_d
-        mns = cfg.get("max_num_segments", 24)
         sig = None
-        if T <= mns + 1:
+        if T <= cfg.get("max_num_segments", 24) + 1:
             seg_idx = list(range(T))
         else:
             # T > 25 >= 3 * world: every rank owns frames.  Local pairs, then the pair across the right-hand boundary.
@@ -295,7 +277,7 @@ class ShardedVideoEncoder:
             # the host read queues behind the tower (with a host-side transport - gloo - the device is synchronised anyway)
             ev = e.mark() if (hasattr(e, "mark") and sims_local.is_cuda and not getattr(self.comm, "_host_side_now", lambda: True)()) \
                 else None
-            if side is None:
+            if side_sig is None:
                 sig = e.tower("siglip", px_siglip_local)
             counts = [(h - l) - (0 if r < world - 1 else 1) for r, (l, h) in enumerate(ranges)]
             if ev is not None:
@@ -304,20 +286,12 @@ class ShardedVideoEncoder:
                     sims = self._all_gather_var(sims_local, counts).tolist()
             else:
                 sims = self._all_gather_var(sims_local, counts).tolist()
-            assert len(sims) == T - 1
-            seg_idx = seg.select_segments(sims, mns)
-            eps = getattr(e, "selection_eps", None)
-            band = seg.selection_band(sims, mns, eps) if eps else []         # host integers: identical on every rank
-            if band and seg.band_allowed(band, T, getattr(e, "selection_max_fraction", 0.125)):
-                seg_idx = self._refine_selection(band, sims, mns, eps, px_dino_local_halo, ranges, recompute_halo)
+            assert len(sims) == T - 1         # the same list on every rank: every rank joins the refinement's exchanges
+            seg_idx = select_segments_with(e, sims, lambda b: self._refined_sims(b, px_dino_local_halo, ranges, recompute_halo))
         dino = dino_all[: Tl * P]
         # 2. local towers + connector (+ audio rows of the local frames)
-        if side is not None:
-            torch.cuda.current_stream(px_siglip_local.device).wait_stream(side)
-            sig = sig_early
-            sig.record_stream(torch.cuda.current_stream(px_siglip_local.device))
-        elif sig is None:
-            sig = e.tower("siglip", px_siglip_local)
+        if sig is None:
+            sig = join_side_tower(e, side_sig, px_siglip_local)
         X, sizes = e.connector(sig, dino, Tl, [tuple(image_size)] * Tl)
         N = X.shape[0] // Tl
         K = e.K
@@ -325,14 +299,13 @@ class ShardedVideoEncoder:
             sample_indices = [1] * T
         Xf, Nf = e.with_audio(X, Tl, N, e.local_audio(audio, sample_indices, T, lo, hi))
         # 3. shared plan, query hand-off
-        max_visual_len = cfg["tokenizer_model_max_length"] - cfg.get("inference_max_length", 16) - n_text_tokens
-        plan = seg.emit_plan(T, Nf, K, seg_idx, max_visual_len, cfg.get("add_static", True))
+        plan, learned = emission_plan(e, T, Nf, seg_idx, visual_budget(cfg, n_text_tokens))
         pairs, comp_local = split_plan(plan, ranges, Nf, K)
         keys = plan["key_frames"]
         my_comp = [gi for gi, f in enumerate(plan["comp_frames"]) if lo <= f < hi]
-        pid = prompt_ids if cfg.get("text_input", True) else None
+        pid = text_prompt(cfg, prompt_ids)
         comp = None
-        if cfg.get("query_type", "Avg_pool") == "learned":          # cambrian_arch.py:1639-1640: one shared query block
+        if learned:
             if my_comp:
                 comp = e.compress_frames(Xf, Nf, [plan["comp_frames"][gi] - lo for gi in my_comp], e.learned_queries(),
                                          [0] * len(my_comp), pid)

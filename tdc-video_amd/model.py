@@ -421,6 +421,11 @@ class CambrianMetaModel:
             raise ValueError("config.tdc_frame_cap must be a positive frame count, got %r" % (cap,))
         return cap
 
+    def tdc_side_stream(self, frames_per_rank):
+        """engine.two_streams (pipeline.start_side_tower): the config's choice, by default on at <= 128 frames per rank"""
+        ts = getattr(self.config, "tdc_two_streams", None)
+        return bool(ts) if ts is not None else frames_per_rank <= 128
+
     def tdc_sharded_engine(self):
         """dist.ShardedVideoEncoder over the default process group when `config.tdc_shard_frames` is set and
         torch.distributed runs with more than one rank (one process per GPU, RCCL); None otherwise."""
@@ -603,8 +608,7 @@ class CambrianMetaForCausalLM(ABC):
                     # selection, dist.ShardedVideoEncoder exchanges what crosses the rank boundaries and all-gathers the
                     # emitted tokens, so every rank returns the same 10-tuple as the serial path, bit for bit
                     fp = sharded.frame_plan(vid_s.shape[0], btl, cap, vindex)
-                    ts = getattr(model.config, "tdc_two_streams", None)
-                    eng.two_streams = bool(ts) if ts is not None else (fp["hi"] - fp["lo"]) <= 128
+                    eng.two_streams = model.tdc_side_stream(fp["hi"] - fp["lo"])
                     sel_s = torch.as_tensor(fp["siglip_frames"], dtype=torch.long, device=vid_s.device)
                     sel_d = torch.as_tensor(fp["dino_frames"], dtype=torch.long, device=vid_d.device)
                     vis = sharded.encode_video(vid_s[sel_s].to(eng.dev), vid_d[sel_d].to(eng.dev), fp["T"],
@@ -613,8 +617,7 @@ class CambrianMetaForCausalLM(ABC):
                     keep["final_size"] = [seg.unpad_newline_map(eng.side, tuple(image_sizes[i]), 0)[1]] * fp["T"]
                     splice = None
                 else:
-                    ts = getattr(model.config, "tdc_two_streams", None)
-                    eng.two_streams = bool(ts) if ts is not None else min(vid_s.shape[0], cap) <= 128
+                    eng.two_streams = model.tdc_side_stream(min(vid_s.shape[0], cap))
                     vis = eng.encode_video(vid_s.to(eng.dev), vid_d.to(eng.dev), tuple(image_sizes[i]),
                                            budget_text_len=btl, n_text_tokens=n_text, prompt_ids=prompt_ids, audio=audio,
                                            frame_cap=cap, info=keep, splice=splice, video_index=vindex)

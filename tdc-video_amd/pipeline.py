@@ -18,6 +18,10 @@ from . import weights as Wt
 from .weights import pad64
 
 
+def _lin(l):
+    return L.Lin(l.w.data_ptr(), l.b.data_ptr() if l.b is not None else None, l.w.shape[0], l.w.shape[1])
+
+
 class _LRU(dict):
     """Small bounded cache for the host-built index / mask / prompt tables (keys: geometry or prompt-id tuples): a server that
     sees many prompts and resolutions does not grow host and device memory without bound; the least recently used entry
@@ -101,7 +105,7 @@ class VideoEncoder:
         for t in self.towers.values():
             t["dtype"] = dino_dtype or tower_dtype if t.kind == "dino" else tower_dtype
         # a5 at the reference's precision under bf16 DINOv2 operands: a second, fp16-operand DINOv2 tower for the pairs whose
-        # similarities decide the selection (encode_video_with / dist.ShardedVideoEncoder: selection_band -> refine_pairs)
+        # similarities decide the selection (select_segments_with, on the serial and the sharded path)
         if selection_refine is None:
             selection_refine = bool(d_sd) and (dino_dtype or tower_dtype) == torch.bfloat16 and not fp8_towers
         self.selection_eps = None
@@ -170,13 +174,23 @@ class VideoEncoder:
         if free_bytes is None:
             free, _total = torch.cuda.mem_get_info(self.dev)
             unused = torch.cuda.memory_reserved(self.dev) - torch.cuda.memory_allocated(self.dev)
-            wkey = "_vit_ws_" + t.kind if getattr(self, "two_streams", False) else "_vit_ws"
-            ws = getattr(self, wkey, None)
+            ws = getattr(self, self._vit_ws_key(t), None)
             free_bytes = free + max(0, unused) + (ws.numel() if ws is not None else 0)
         budget = 0.6 * free_bytes
         while B > 1 and lib.tdc_vit_workspace_bytes(C.byref(m), B, Hpx, Wpx) > budget:
             B = (B + 1) // 2
         return B
+
+    def _workspace(self, key, nbytes):
+        """the native composite's device workspace in attribute `key`, grown to nbytes (kept for the engine's life)"""
+        ws = getattr(self, key, None)
+        if ws is None or ws.numel() < nbytes:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+            setattr(self, key, ws)
+        return ws
+
+    def _vit_ws_key(self, t):       # one workspace per tower when the towers run concurrently on two streams
+        return "_vit_ws_" + t.kind if getattr(self, "two_streams", False) else "_vit_ws"
 
     # ---- native composite (csrc/api.cpp: tdc_vit_fwd): the whole tower batch is one C call ------------------------------
     def _vit_struct(self, t, gh, gw):
@@ -186,9 +200,6 @@ class VideoEncoder:
         if (gh, gw) in cache:
             return cache[(gh, gw)]
         pos, cls_row = Wt.tower_pos(t, gh, gw, self.dev)
-
-        def lin(l):
-            return L.Lin(l.w.data_ptr(), l.b.data_ptr() if l.b is not None else None, l.w.shape[0], l.w.shape[1])
         layers = (L.VitLayer * len(t.layers))()
         zeros = None
         if t.get("fp8"):    # one zero ln_c1 vector long enough for every lin of the tower (tdc_vit_layer.zeros)
@@ -196,7 +207,7 @@ class VideoEncoder:
             zeros = t.setdefault("_zeros", torch.zeros(zn, dtype=torch.float32, device=self.dev))
         for i, Lr in enumerate(t.layers):
             layers[i] = L.VitLayer(Lr.ln1_g.data_ptr(), Lr.ln1_b.data_ptr(), Lr.ln2_g.data_ptr(), Lr.ln2_b.data_ptr(),
-                                   lin(Lr.qkv), lin(Lr.out), lin(Lr.fc1), lin(Lr.fc2),
+                                   _lin(Lr.qkv), _lin(Lr.out), _lin(Lr.fc1), _lin(Lr.fc2),
                                    Lr.qkv_c1.data_ptr() if Lr.qkv_c1 is not None else None,
                                    Lr.fc1_c1.data_ptr() if Lr.fc1_c1 is not None else None,
                                    Lr.qkv.wscale or 0.0, Lr.fc1.wscale or 0.0,
@@ -210,7 +221,7 @@ class VideoEncoder:
             t.has_cls
         m.act = {"gelu_tanh": L.ACT_GELU_TANH, "gelu_erf": L.ACT_GELU_ERF, "swiglu": L.ACT_SWIGLU}[t.act]
         m.eps = t.eps
-        m.patch_lin = lin(t.patch_lin)
+        m.patch_lin = _lin(t.patch_lin)
         m.pos, m.ldpos = pos.data_ptr(), pos.stride(0)
         m.cls_row = cls_row.data_ptr() if cls_row is not None else None
         fl = t.get("final_ln")
@@ -228,13 +239,7 @@ class VideoEncoder:
         g = H // t.patch
         m = self._vit_struct(t, g, g)[0]
         lib = L.load()
-        need = lib.tdc_vit_workspace_bytes(C.byref(m), B, H, W)
-        # one workspace per tower when the towers run concurrently on two streams, otherwise one shared buffer
-        wkey = "_vit_ws_" + t.kind if getattr(self, "two_streams", False) else "_vit_ws"
-        ws = getattr(self, wkey, None)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
-            setattr(self, wkey, ws)
+        ws = self._workspace(self._vit_ws_key(t), lib.tdc_vit_workspace_bytes(C.byref(m), B, H, W))
         D = t.dim
         out = torch.empty(B * out_grid * out_grid, pad64(D), device=self.dev, dtype=self.dtype)
         i0, i1, fr = self._bil(g, out_grid)
@@ -477,19 +482,16 @@ class VideoEncoder:
         if getattr(self, "_conn_struct", None) is not None:
             return self._conn_struct
         c = self.c
-
-        def lin(l):
-            return L.Lin(l.w.data_ptr(), l.b.data_ptr() if l.b is not None else None, l.w.shape[0], l.w.shape[1])
         layers = (L.SvaLayer * len(c.sva))()
         for i, Lr in enumerate(c.sva):
             x = L.SvaLayer()
-            x.proj_context, x.proj_in_c, x.proj_in_q = lin(Lr.proj_context), lin(Lr.proj_in_c), lin(Lr.proj_in_q)
+            x.proj_context, x.proj_in_c, x.proj_in_q = _lin(Lr.proj_context), _lin(Lr.proj_in_c), _lin(Lr.proj_in_q)
             x.pos[0], x.pos[1], x.ldpos = Lr.pos[0].data_ptr(), Lr.pos[1].data_ptr(), Lr.pos[0].stride(0)
-            x.kv[0], x.kv[1] = lin(Lr.kv[0]), lin(Lr.kv[1])
+            x.kv[0], x.kv[1] = _lin(Lr.kv[0]), _lin(Lr.kv[1])
             x.q_ln_g, x.q_ln_b = Lr.q_ln[0].data_ptr(), Lr.q_ln[1].data_ptr()
-            x.q_proj, x.o_proj = lin(Lr.q_proj), lin(Lr.o_proj)
+            x.q_proj, x.o_proj = _lin(Lr.q_proj), _lin(Lr.o_proj)
             x.norm_g, x.norm_b = Lr.norm[0].data_ptr(), Lr.norm[1].data_ptr()
-            x.out1, x.out2 = lin(Lr.out1), lin(Lr.out2)
+            x.out1, x.out2 = _lin(Lr.out1), _lin(Lr.out2)
             layers[i] = x
         vq = torch.zeros(pad64(c.C), device=self.dev, dtype=self.dtype)
         vq[: c.C] = c.vision_query.to(self.dtype).to(self.dev)
@@ -497,10 +499,10 @@ class VideoEncoder:
         m.dtype, m.C, m.side, m.heads, m.n_layers = ops._dtcode(self.dtype), c.C, self.side, 16, len(c.sva)
         for i in range(2):
             a = c.aux[i]
-            m.aux[i] = L.AuxProj(lin(a.fc1), lin(a.fc2), a.ln_g.data_ptr(), a.ln_b.data_ptr())
+            m.aux[i] = L.AuxProj(_lin(a.fc1), _lin(a.fc2), a.ln_g.data_ptr(), a.ln_b.data_ptr())
         m.vision_query, m.ones_C, m.zeros_C = vq.data_ptr(), c.ones_C.data_ptr(), c.zeros_C.data_ptr()
         m.layers_host = layers
-        m.mm1, m.mm2 = lin(c.mm1), lin(c.mm2)
+        m.mm1, m.mm2 = _lin(c.mm1), _lin(c.mm2)
         self._conn_struct = (m, layers, vq)
         return self._conn_struct
 
@@ -531,10 +533,7 @@ class VideoEncoder:
         assert dino_feat.shape[0] == T * P and P == (self.side * r) ** 2
         assert sig_feat.shape[1] >= m.aux[0].fc1.k and dino_feat.shape[1] >= m.aux[1].fc1.k
         lib = L.load()
-        need = lib.tdc_connector_workspace_bytes(C.byref(m), T)
-        ws = getattr(self, "_conn_ws", None)
-        if ws is None or ws.numel() < need:
-            ws = self._conn_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        ws = self._workspace("_conn_ws", lib.tdc_connector_workspace_bytes(C.byref(m), T))
         out = torch.empty(T * self.side * self.side, pad64(self.c.H), device=self.dev, dtype=self.dtype)
         L.check(lib.tdc_connector_fwd(C.byref(m), ops._ptr(sig_feat), sig_feat.stride(0), ops._ptr(dino_feat),
                                       dino_feat.stride(0), T, ops._ptr(mask), ops._ptr(out), out.stride(0), ops._ptr(ws),
@@ -754,26 +753,23 @@ class VideoEncoder:
             return self._qf_struct
         c, qf = self.c, self.c.qformer
         self._tile_cross_weights()
-
-        def lin(l):
-            return L.Lin(l.w.data_ptr(), l.b.data_ptr() if l.b is not None else None, l.w.shape[0], l.w.shape[1])
         zero = L.Lin(None, None, 0, 0)
         layers = (L.QformerLayer * len(qf.layers))()
         for i, Lr in enumerate(qf.layers):
             x = L.QformerLayer()
-            x.qkv, x.attn_out = lin(Lr.qkv), lin(Lr.attn_out)
+            x.qkv, x.attn_out = _lin(Lr.qkv), _lin(Lr.attn_out)
             x.attn_ln_g, x.attn_ln_b = Lr.attn_ln[0].data_ptr(), Lr.attn_ln[1].data_ptr()
             if Lr.cross is not None:
                 x.has_cross, x.cross_idx = 1, Lr.cross.idx
-                x.cross_q, x.cross_out = lin(Lr.cross.q), lin(Lr.cross.out)
+                x.cross_q, x.cross_out = _lin(Lr.cross.q), _lin(Lr.cross.out)
                 x.cross_ln_g, x.cross_ln_b = Lr.cross.ln[0].data_ptr(), Lr.cross.ln[1].data_ptr()
                 if Lr.cross.q_tiled is not None:
                     x.cross_q_tiled, x.cross_out_tiled = Lr.cross.q_tiled.data_ptr(), Lr.cross.out_tiled.data_ptr()
             else:
                 x.has_cross, x.cross_idx, x.cross_q, x.cross_out = 0, 0, zero, zero
-            x.fq1, x.fq2 = lin(Lr.ffn_q.fc1), lin(Lr.ffn_q.fc2)
+            x.fq1, x.fq2 = _lin(Lr.ffn_q.fc1), _lin(Lr.ffn_q.fc2)
             x.fq_ln_g, x.fq_ln_b = Lr.ffn_q.ln[0].data_ptr(), Lr.ffn_q.ln[1].data_ptr()
-            x.ft1, x.ft2 = lin(Lr.ffn_t.fc1), lin(Lr.ffn_t.fc2)
+            x.ft1, x.ft2 = _lin(Lr.ffn_t.fc1), _lin(Lr.ffn_t.fc2)
             x.ft_ln_g, x.ft_ln_b = Lr.ffn_t.ln[0].data_ptr(), Lr.ffn_t.ln[1].data_ptr()
             layers[i] = x
         m = L.QformerModel()
@@ -781,9 +777,9 @@ class VideoEncoder:
             c.H, 1e-12
         m.word, m.pos, m.ldw = qf.word.data_ptr(), qf.pos.data_ptr(), qf.word.stride(0)
         m.emb_ln_g, m.emb_ln_b = qf.emb_ln[0].data_ptr(), qf.emb_ln[1].data_ptr()
-        m.cross_kv, m.vision_proj = lin(qf.cross_kv), lin(c.vision_proj)
+        m.cross_kv, m.vision_proj = _lin(qf.cross_kv), _lin(c.vision_proj)
         if qf.cross_k is not None:
-            m.cross_k, m.cross_v, m.cross_bv = lin(qf.cross_k), lin(qf.cross_v), qf.cross_bv.data_ptr()
+            m.cross_k, m.cross_v, m.cross_bv = _lin(qf.cross_k), _lin(qf.cross_v), qf.cross_bv.data_ptr()
             m.xattn_mode = fused_on
         m.layers_host = layers
         self._qf_struct = (m, layers, fused_on)
@@ -810,10 +806,7 @@ class VideoEncoder:
         assert qs.dtype == torch.int32 and qs.numel() >= F        # value range checked on the host list (compress_frames)
         assert enc.shape[0] >= F * Nf and enc.shape[1] >= m.cross_kv.k and qtable.shape[1] >= pad64(m.dim)
         lib = L.load()
-        need = lib.tdc_qformer_workspace_bytes(C.byref(m), F, K, Lt, Nf)
-        ws = getattr(self, "_qf_ws", None)
-        if ws is None or ws.numel() < need:
-            ws = self._qf_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        ws = self._workspace("_qf_ws", lib.tdc_qformer_workspace_bytes(C.byref(m), F, K, Lt, Nf))
         out = torch.empty(F * K, pad64(self.c.H), device=self.dev, dtype=self.dtype)
         L.check(lib.tdc_qformer_fwd(C.byref(m), ops._ptr(enc), enc.stride(0), F, Nf, ops._ptr(qtable), qtable.stride(0),
                                     ops._ptr(qs), ops._ptr(ids), Lt, K, ops._ptr(out), out.stride(0), ops._ptr(ws),
@@ -902,19 +895,35 @@ class VideoEncoder:
 # ---------------------------------------------------------------------------------------------------------------------
 # Orchestration over an "engine" (VideoEncoder on GPUs; the gloo tests of dist.py plug in a CPU test double that
 # implements tower / sims_tensor / connector / with_audio / make_queries / compress_frames / emit / query_width).
-def compress_with(e, X, T, N, seg_indices, prompt_ids, max_visual_len, audio=None, keep=None, splice=None, info=None):
-    K = e.K
+# Each policy decision of the video path has one function below, called by the serial and the sharded (dist.py) path.
+def visual_budget(cfg, n_text_tokens):
+    """max_visual_len of a sample with n_text_tokens non-image tokens (tdc/cambrian_arch.py:1499-1505)"""
+    return cfg["tokenizer_model_max_length"] - cfg.get("inference_max_length", 16) - n_text_tokens
+
+
+def emission_plan(e, T, Nf, seg_indices, max_visual_len):
+    """a11-a19 -> (segment.emit_plan, whether all chunks share the learned query block: cambrian_arch.py:1639-1640)"""
     cfg = getattr(e, "cfg", {})
+    return (seg.emit_plan(T, Nf, e.K, seg_indices, max_visual_len, cfg.get("add_static", True)),
+            cfg.get("query_type", "Avg_pool") == "learned")
+
+
+def text_prompt(cfg, prompt_ids):
+    """the Q-Former's text prompt: the sample's BERT ids, or none when `text_input` is off"""
+    return prompt_ids if cfg.get("text_input", True) else None
+
+
+def compress_with(e, X, T, N, seg_indices, prompt_ids, max_visual_len, audio=None, keep=None, splice=None, info=None):
     Xf, Nf = e.with_audio(X, T, N, audio)
-    plan = seg.emit_plan(T, Nf, K, seg_indices, max_visual_len, cfg.get("add_static", True))
+    plan, learned = emission_plan(e, T, Nf, seg_indices, max_visual_len)
     comp = None
     if plan["comp_frames"]:
-        if cfg.get("query_type", "Avg_pool") == "learned":      # cambrian_arch.py:1639-1640: one shared query block
+        if learned:
             qtable, qsrc = e.learned_queries(), [0] * len(plan["comp_frames"])
         else:
             qtable, qsrc = e.make_queries(Xf, N, Nf, plan["key_frames"]), plan["comp_chunk"]
         comp = e.compress_frames(Xf, Nf, plan["comp_frames"], qtable, qsrc, prompt_ids, keep)
-    pairs = seg.emit_pairs(plan, Nf, K)
+    pairs = seg.emit_pairs(plan, Nf, e.K)
     if keep is not None:
         keep["plan"] = plan
         keep["n_visual"] = len(pairs)
@@ -923,6 +932,11 @@ def compress_with(e, X, T, N, seg_indices, prompt_ids, max_visual_len, audio=Non
     if splice is not None:
         return e.emit(Xf, comp, pairs, splice)
     return e.emit(Xf, comp, pairs)
+
+
+def frame_indices(cfg, T0, budget_text_len, frame_cap):
+    """a1 (tdc/cambrian_arch.py:899-916): the input frames kept, at most frame_cap (a5's second cap, :813-822, keeps all)"""
+    return seg.uniform_indices(T0, min(seg.get_max_num_frames(budget_text_len, cfg), frame_cap))
 
 
 def sample_indicator(T0, idx, video_index=None):
@@ -944,81 +958,89 @@ def sample_indicator(T0, idx, video_index=None):
     return samp
 
 
+def start_side_tower(e, px_siglip):
+    """`two_streams`, before the DINOv2 tower: SigLIP on the engine's side stream fills the partly filled last tile rounds of
+    the other tower's GEMMs (T = 64: +0.6-1.1 %).  -> (stream, features) for join_side_tower, or None (off, host tensors)."""
+    if not (getattr(e, "two_streams", False) and px_siglip.is_cuda):
+        return None
+    side = e.tower_stream() if hasattr(e, "tower_stream") else torch.cuda.Stream(device=px_siglip.device)
+    side.wait_stream(torch.cuda.current_stream(px_siglip.device))
+    with torch.cuda.stream(side):
+        return side, e.tower("siglip", px_siglip)
+
+
+def join_side_tower(e, started, px_siglip):
+    """-> the SigLIP features for the compute stream: start_side_tower's, joined, or enqueued now if it started none"""
+    if started is None:
+        return e.tower("siglip", px_siglip)
+    side, sig = started
+    torch.cuda.current_stream(sig.device).wait_stream(side)
+    sig.record_stream(torch.cuda.current_stream(sig.device))
+    return sig
+
+
+def select_segments_with(e, sims, refine, info=None):
+    """a5 (tdc/cambrian_arch.py:832-849) on the T - 1 host similarities.  With engine.selection_eps, the pairs whose order that
+    error leaves open (segment.selection_band) are re-ranked on refine(band) -> their fp16-tower similarities in band order,
+    unless the band is a plateau (segment.band_allowed).  info receives refined_pairs and refine_skipped_pairs."""
+    mns = e.cfg.get("max_num_segments", 24)
+    eps = getattr(e, "selection_eps", None)
+    band = seg.selection_band(sims, mns, eps) if eps else []
+    if band and not seg.band_allowed(band, len(sims) + 1, getattr(e, "selection_max_fraction", 0.125)):
+        if info is not None:
+            info["refine_skipped_pairs"] = len(band)
+        band = []
+    if info is not None:
+        info["refined_pairs"] = list(band)
+    return seg.select_refined(sims, mns, eps, band, refine(band)) if band else seg.select_segments(sims, mns)
+
+
+def precise_features(e, px_dino, frames, lo=0):
+    """{frame: its feature rows from the fp16-operand DINOv2 tower} for the ascending `frames` (pixels: px_dino[frame - lo])"""
+    fp = e.precise_dino(px_dino[torch.tensor([f - lo for f in frames], device=px_dino.device)])
+    Pp = fp.shape[0] // len(frames)
+    return {f: fp[j * Pp:(j + 1) * Pp] for j, f in enumerate(frames)}
+
+
 def encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio=None,
                       frame_cap=224, keep=None, splice=None, video_index=None, info=None):
     cfg = e.cfg
     T0 = px_siglip.shape[0]
-    idx = seg.uniform_indices(T0, min(seg.get_max_num_frames(budget_text_len, cfg), frame_cap))     # a1
+    idx = frame_indices(cfg, T0, budget_text_len, frame_cap)                                        # a1
     if len(idx) != T0:
         sel = torch.tensor(idx, device=px_siglip.device)
         px_siglip, px_dino = px_siglip[sel], px_dino[sel]
     T = len(idx)
-    # The two towers are independent (a5's second frame cap is a no-op once a1 capped at <= frame_cap frames): with
-    # `two_streams` they are enqueued on two HIP streams so one tower's kernel tails / memory-bound phases are
-    # filled by the other tower's workgroups.
-    side = None
-    if getattr(e, "two_streams", False) and T <= frame_cap and px_siglip.is_cuda:
-        side = e.tower_stream() if hasattr(e, "tower_stream") else torch.cuda.Stream(device=px_siglip.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            sig_early = e.tower("siglip", px_siglip)
+    side_sig = start_side_tower(e, px_siglip)
     dino = e.tower("dino", px_dino)                                                                 # a4
-    mns = cfg.get("max_num_segments", 24)
     sig = None
-    if T <= mns + 1:                                                                                # a5
-        sel2, seg_idx = list(range(T)), list(range(T))
+    if T <= cfg.get("max_num_segments", 24) + 1:                                                    # a5
+        seg_idx = list(range(T))
     else:
-        sel2 = seg.uniform_indices(T, frame_cap)
-        if len(sel2) != T:
-            s2 = torch.tensor(sel2, device=px_siglip.device)
-            P = dino.shape[0] // T
-            dino = dino.view(T, P, -1)[s2].reshape(len(sel2) * P, -1)
-            px_siglip = px_siglip[s2]
-            T = len(sel2)
         sims_dev = e.sims_tensor(dino, T)
         ev = e.mark() if hasattr(e, "mark") and sims_dev.is_cuda else None
-        if side is None:
-            # the SigLIP tower does not depend on the selection: enqueue it BEFORE the one host read of the similarities,
-            # so the device keeps working while the host ranks them (a3) - and read them on a side stream (fetch), so the
-            # host does not wait for the tower either
+        if side_sig is None:
+            # the SigLIP tower does not depend on the selection: enqueue it BEFORE the one host read of the similarities, so
+            # the device keeps working while the host ranks them (a3) - read on a side stream (fetch): no wait for the tower
             sig = e.tower("siglip", px_siglip)
         sims = e.fetch(sims_dev, ev) if ev is not None else sims_dev.tolist()
-        seg_idx = seg.select_segments(sims, mns)
-        # a5 at the reference's precision (engine.selection_eps: bf16 DINOv2 operands with the fp16 copy of the tower at hand): when
-        # the ranks that decide the selection are closer than the operand type's error, the pairs in that band are re-encoded
-        eps = getattr(e, "selection_eps", None)
-        band = seg.selection_band(sims, mns, eps) if eps else []
-        if band and not seg.band_allowed(band, T, getattr(e, "selection_max_fraction", 0.125)):
-            if info is not None:
-                info["refine_skipped_pairs"] = len(band)      # a plateau at the decisive rank: the fast tower's ranking stands
-            band = []
-        if band:
-            frames = seg.band_frames(band)
-            pxd = px_dino if len(sel2) == px_dino.shape[0] else px_dino[torch.tensor(sel2, device=px_dino.device)]
-            fp = e.precise_dino(pxd[torch.tensor(frames, device=pxd.device)])
-            Pp = fp.shape[0] // len(frames)
-            feats = {f: fp[j * Pp:(j + 1) * Pp] for j, f in enumerate(frames)}
-            refined = e.pair_sims(feats, [(i, i + 1) for i in band]).tolist()
-            seg_idx = seg.select_refined(sims, mns, eps, band, refined)
-        if info is not None:
-            info["refined_pairs"] = list(band)
-    if side is not None:
-        torch.cuda.current_stream().wait_stream(side)
-        sig = sig_early
-        sig.record_stream(torch.cuda.current_stream())
-    elif sig is None:
-        sig = e.tower("siglip", px_siglip)                                                          # a3
+
+        def refine(band):
+            return e.pair_sims(precise_features(e, px_dino, seg.band_frames(band)), [(i, i + 1) for i in band]).tolist()
+        seg_idx = select_segments_with(e, sims, refine, info)
+    if sig is None:
+        sig = join_side_tower(e, side_sig, px_siglip)                                               # a3
     sizes = [tuple(image_size)] * T
     X, final_size = e.connector(sig, dino, T, sizes, keep)                                          # a6-a10
     N = X.shape[0] // T
-    max_visual_len = cfg["tokenizer_model_max_length"] - cfg.get("inference_max_length", 16) - n_text_tokens
-    pid = prompt_ids if cfg.get("text_input", True) else None
+    max_visual_len = visual_budget(cfg, n_text_tokens)
+    pid = text_prompt(cfg, prompt_ids)
     if audio is not None:                                                                           # a20
         audio = e.local_audio(audio, sample_indicator(T0, idx, video_index), T, 0, T)
     vis = compress_with(e, X, T, N, seg_idx, pid, max_visual_len, audio, keep, splice, info)        # a11-a19 (+a21)
-    if keep is not None:
-        keep.update(frame_indices=idx, selected=sel2, seg_indices=seg_idx, siglip_feat=sig, dino_feat=dino,
+    if keep is not None:                    # selected: what a5's second frame cap keeps - every frame (frame_indices)
+        keep.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, siglip_feat=sig, dino_feat=dino,
                     final_size=final_size, X=X)
     if info is not None:
-        info.update(frame_indices=idx, selected=sel2, seg_indices=seg_idx, final_size=final_size)
+        info.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, final_size=final_size)
     return vis

@@ -14,15 +14,7 @@ import math
 
 import torch
 
-
-def pad64(n):
-    return (n + 63) // 64 * 64
-
-
-def _register_real_nk(w, n, k):
-    """un-padded dims of a prepared weight: kept on the tensor and, by data pointer, for the library's launch profiler"""
-    from . import ops
-    ops.register_real_nk(w, n, k)
+from .ops import pad64, register_real_nk
 
 
 class Lin:
@@ -65,7 +57,7 @@ def make_lin(W, b, dtype, dev, row_scale=None, col_scale=None, col_shift=None, n
         bp[:n] = bias
         bp = bp.to(dev)
     w = Wp.to(dev).contiguous()
-    _register_real_nk(w, n, k)  # algorithmic dims for FLOP accounting (bench.py)
+    register_real_nk(w, n, k)  # algorithmic dims for FLOP accounting (bench.py)
     return Lin(w, bp, n, k)
 
 
@@ -99,7 +91,7 @@ def to_fp8(lin, dev):
     w2max = float(Wq.float().norm(dim=1).max())
     bmax = float(lin.b.abs().max()) if lin.b is not None else 0.0
     W8 = W8.to(dev).contiguous()
-    _register_real_nk(W8, *getattr(lin.w, "_real_nk", (lin.n, lin.k)))
+    register_real_nk(W8, *getattr(lin.w, "_real_nk", (lin.n, lin.k)))
     return Lin(W8, lin.b, lin.n, lin.k, wscale=sw, zeros=torch.zeros(n_pad, dtype=torch.float32, device=dev),
                w2max=w2max, bmax=bmax)
 
@@ -257,7 +249,7 @@ def prep_dino(sd, heads, dtype, dev, patch=14, eps=1e-6, fp8=False, ln_fuse=Fals
             Wi[0:2 * hid:2], Wi[1:2 * hid:2] = Win[:hid], Win[hid:]
             bi[0:2 * hid:2], bi[1:2 * hid:2] = bin_[:hid], bin_[hid:]
             Lr.fc1 = make_lin(Wi, bi, dtype, dev, n_pad=2 * hp, **f2)
-            _register_real_nk(Lr.fc1.w, 2 * hid, Win.shape[1])
+            register_real_nk(Lr.fc1.w, 2 * hid, Win.shape[1])
             Lr.fc2 = make_lin(sd[p + "mlp.weights_out.weight"], sd[p + "mlp.weights_out.bias"], dtype, dev,
                               row_scale=sd[p + "layer_scale2.lambda1"])
             t.act = "swiglu"
