@@ -9,8 +9,9 @@ vision_proj + L2, token emission) over ONE synthetic video of T frames whose pix
 For N>1 the T frames of the one video are sharded by contiguous ranges over the ranks (strong scaling), with the RCCL
 exchanges of tdc-video_amd/dist.py (boundary-frame DINOv2 features, similarities all-gather, key-frame query hand-off,
 emitted-token all-gather).
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` (dominant kernel = tdc_gemm MFMA
-kernel, timed live with events on the launch stream) and `cpu_baseline` (the oracle on the host cores, bounded sample).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times its steps, writes
+--dump-outputs and prints the line; `--full` adds, after the timed steps, `roofline` (dominant kernel = tdc_gemm MFMA kernel,
+timed live with events on the launch stream in one extra step) and `cpu_baseline` (the oracle on the host cores, bounded sample).
 """
 import argparse
 import json
@@ -403,239 +404,14 @@ def rank_guard(seconds):
     return t
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--frames", type=int, default=512)
-    ap.add_argument("--K", type=int, default=144, help="context_token_num (BASELINE configs: 144; reference default 16)")
-    ap.add_argument("--hidden", type=int, default=3584, help="LLM embed dim (Qwen2-7B)")
-    ap.add_argument("--dtype", default="mixed", choices=["mixed", "bf16", "fp16", "fp8"],
-                    help="mixed (default): the two ViT towers in bf16, connector + Q-Former in fp16 - the type whose compressed "
-                         "tokens pass the north_star's 1e-3 against the fp32 oracle at full depth (tests/test_hip_configs.py); "
-                         "fp8 (BASELINE config 5): e4m3 operands for the towers' LayerNorm-fed GEMMs (qkv, fc1) through "
-                         "v_mfma_f32_16x16x128_f8f6f4, bf16 everywhere else")
-    ap.add_argument("--res", default="fp16", choices=["fp16", "fp32"],
-                    help="the towers' residual stream in HBM: fp16 (default; the reference's own arithmetic - its HF towers run "
-                         "under torch_dtype=float16 - 4 B per element and residual add, sums formed in fp32 and rounded once) or fp32 "
-                         "(8 B per element: rounds 1-3)")
-    ap.add_argument("--dino-dtype", default="", choices=["", "bf16", "fp16"], help="operand type of the DINOv2 tower alone "
-                    "(config.tdc_dino_dtype; default: the towers' type): fp16 keeps the a5 similarities at the reference's precision")
-    ap.add_argument("--selection-refine", type=int, default=-1, choices=[-1, 0, 1], help="a5 at the reference's precision under bf16 "
-                    "DINOv2 operands (VideoEncoder.selection_refine): -1 = automatic (on for bf16 DINOv2 operands), 0 / 1.  The synthetic "
-                    "video's decisive similarity ranks are 0.43 apart, so nothing is re-encoded in the timed region either way")
-    ap.add_argument("--ln-fuse", action="store_true", help="the towers' pre-LayerNorms folded into the neighbouring GEMMs "
-                    "(VideoEncoder(ln_fuse=True)); over the fp16 residual stream this needs --dtype fp16: the consumer GEMMs read the "
-                    "stream itself, no LayerNorm kernel runs inside the layer loop")
-    ap.add_argument("--px", type=int, default=384, help="SigLIP input size (DINO uses px-6: 378); 336 -> 336/336")
-    ap.add_argument("--fp8-level", type=int, default=1, choices=[1, 2, 3],
-                    help="--dtype fp8: 1 = qkv / fc1 (quantised by the LayerNorm kernel), 2 = also out-proj / fc2, "
-                         "3 = as 2 with the MLP hidden written as e4m3 by fc1 itself")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--tower-batch", type=int, default=512)
-    ap.add_argument("--two-streams", type=int, default=-1, help="run the two towers on two HIP streams: 0 / 1, -1 = on at <= 128 "
-                    "frames per rank (small batches leave partly filled last tile rounds, which the other tower's workgroups fill)")
-    ap.add_argument("--gemm-shape-times", default="", help="write per-shape GEMM times of the profiled step to this file")
-    ap.add_argument("--xattn-mode", type=int, default=1, choices=[0, 1, 2], help="Q-Former cross-attention block: 0 = per-kernel "
-                    "sequence (stacked K/V GEMM, q GEMM, tdc_attention, dense GEMM, LayerNorm), 1 = output projection + residual + "
-                    "LayerNorm in one kernel behind q GEMM + tdc_attention, 2 = the whole block in one kernel per layer "
-                    "(tdc_qformer_xattn)")
-    ap.add_argument("--recompute-halo", action="store_true", help="N > 1: every rank re-encodes its right neighbour's first frame "
-                    "through DINOv2 instead of receiving its features point to point (fallback form of the boundary exchange)")
-    ap.add_argument("--audio", action="store_true", help="BASELINE config 4: + T seconds of 16 kHz audio through BEATs "
-                    "on the device, 50 audio tokens per frame in the Q-Former KV (1 GPU only)")
-    ap.add_argument("--pmc", default="auto", choices=["auto", "on", "off"], help="N = 1: after the timed region collect FETCH_SIZE / "
-                    "WRITE_SIZE / SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE in fresh child processes (rocprofv3 --pmc over a torch-free "
-                    "replay of this run's GEMM launches) and report them as roofline.traffic / mfma_busy_pmc; auto = when rocprofv3 exists")
-    ap.add_argument("--pmc-budget", type=float, default=90.0, help="wall-clock budget of that leg in seconds")
-    ap.add_argument("--pmc-out", default="", help="write the leg's per-shape summary (JSON) to this file")
-    ap.add_argument("--launch-timeout", type=float, default=-1.0, help="N > 1 started as plain `python bench.py --gpus N`: wall-clock "
-                    "guard of the launcher in seconds; on expiry every rank is stopped and the exit code is 124 (0 = no guard; default "
-                    "600 + 4 x (steps + warmup))")
-    ap.add_argument("--rank-timeout", type=float, default=-1.0, help="wall-clock guard inside every rank in seconds (0 = none; "
-                    "default 600 + 4 x (steps + warmup): a step takes 1.2 s at T = 512 on one GPU)")
-    ap.add_argument("--collective-timeout", type=float, default=180.0, help="N > 1: timeout of the process group (rendezvous and "
-                    "every collective) in seconds")
-    ap.add_argument("--via-mixin", action="store_true", help="drive the step through the drop-in boundary instead of VideoEncoder: "
-                    "a stub language model hosting model.CambrianMetaForCausalLM, one call of prepare_inputs_labels_for_multimodal("
-                    "input_ids, ..., images=[siglip[1,T,...], dino[1,T,...]], image_sizes, video_indices=[None], prompts=[ids]) per "
-                    "step with config.tdc_frame_cap = T (N > 1: + config.tdc_shard_frames, every rank holds the whole video as the "
-                    "reference's eval workers do); the JSON line says config.entry = \"mixin\"")
-    ap.add_argument("--dump-gemm-shapes", default=None, help="write the GEMM launches of one step (for tools/gemm_pmc)")
-    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the last one returned "
-                    "(the emitted tokens) as float32 DIR/tokens.npy: the whole array, or past 48 MiB a seeded sample of it "
-                    "(dump_outputs); inputs and weights are seeded, so runs with the same arguments compare output for output")
-    args = ap.parse_args()
-    if args.steps < 1 or args.warmup < 0:
-        ap.error("--steps must be >= 1 and --warmup >= 0")
-    for k in ("launch_timeout", "rank_timeout"):
-        if getattr(args, k) < 0:
-            setattr(args, k, 600.0 + 4.0 * (args.steps + args.warmup))
-
-    if args.gpus > 1 and "RANK" not in os.environ:
-        # plain `python bench.py --gpus N`: become the launcher.  Nothing above has touched the GPU (no torch.cuda call), and
-        # nothing below this branch runs in this process.
-        sys.exit(self_launch(args.gpus, args.launch_timeout))
-    rank = int(os.environ.get("RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    if world != args.gpus:
-        sys.exit("bench.py: --gpus %d but WORLD_SIZE=%d (run `python bench.py --gpus N` by itself, or under "
-                 "torch.distributed.run --nproc-per-node N)" % (args.gpus, world))
-    # test hooks (never set by the driver): TDC_BENCH_ONE_GPU=1 maps every rank onto GPU 0 and TDC_DIST_BACKEND=gloo
-    # swaps the transport, so the N>1 code path can be exercised on a 1-GPU box
-    if os.environ.get("TDC_BENCH_ONE_GPU"):
-        local = 0
-    guard = rank_guard(args.rank_timeout)
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    if world > 1:
-        import datetime
-        import torch.distributed as dist
-        backend = os.environ.get("TDC_DIST_BACKEND", "nccl")
-        # a bounded timeout on the rendezvous and on every collective: a rank that never arrives fails the job within minutes
-        tmo = datetime.timedelta(seconds=args.collective_timeout)
-        if backend == "nccl":
-            dist.init_process_group("nccl", device_id=dev, timeout=tmo)
-        else:
-            dist.init_process_group(backend, timeout=tmo)
-    import tdc_video_amd  # noqa: F401
+def roofline_leg(args, step, enc, rank, world, two_streams, ms_per_step):
+    """`--full`: the roofline of the dominant kernel (tdc_gemm MFMA kernel) from one extra pass under the library's launch profiler
+    (tdc_profile_*: hipEvents recorded inside libtdc_hip.so around every GEMM / attention / LayerNorm / fused cross-attention
+    launch, on the stream the kernel is launched on) - the SAME host path as the timed steps: the C++ composites
+    tdc_vit_fwd / tdc_connector_fwd / tdc_qformer_fwd, not a per-kernel Python replay of them.  Every rank runs it (the pass
+    holds the step's collectives).  Returns the line's `roofline` dict."""
     from tdc_video_amd import ops
-    from tdc_video_amd.pipeline import VideoEncoder
-    from tdc_video_amd import segment as seg
-    if os.environ.get("TDC_BENCH_PERSIST_GRID"):     # experiment hook of self_launch's CU split (tools/half_chip_gate.sh)
-        from tdc_video_amd import lib as tlib
-        tlib.load().tdc_gemm_set_persistent_grid(int(os.environ["TDC_BENCH_PERSIST_GRID"]))
-
-    dtype = torch.float16 if args.dtype in ("fp16", "mixed") else torch.bfloat16          # connector, Q-Former, outputs
-    tower_dtype = torch.bfloat16 if args.dtype == "mixed" else dtype                       # the two ViT towers
     T, K, H = args.frames, args.K, args.hidden
-    px_s = args.px
-    px_d = args.px - 6 if args.px == 384 else args.px
-    cfg = model_cfg(H, K, T)
-    gen = torch.Generator(device=dev).manual_seed(0)
-    sd = random_state_dict(H, K, dev, gen, siglip_px=px_s)
-    two_streams = args.two_streams if args.two_streams >= 0 else int((T + world - 1) // world <= 128)
-    res16 = args.res == "fp16"
-    product_setting = {"dtype": str(dtype).replace("torch.", ""), "tdc_tower_dtype": str(tower_dtype).replace("torch.", ""),
-                       "tdc_tower_res_dtype": "float16" if res16 else "float32", "tdc_tower_batch": args.tower_batch,
-                       "tdc_fp8_towers": args.fp8_level if args.dtype == "fp8" else 0, "tdc_frame_cap": T,
-                       "tdc_two_streams": bool(two_streams)}
-    if args.ln_fuse:
-        product_setting["tdc_ln_fuse"] = True
-    if args.selection_refine >= 0:
-        product_setting["tdc_selection_refine"] = bool(args.selection_refine)
-    if args.dino_dtype:
-        product_setting["tdc_dino_dtype"] = {"bf16": "bfloat16", "fp16": "float16"}[args.dino_dtype]
-    lm = None
-    if args.via_mixin:
-        if args.audio or args.recompute_halo:
-            sys.exit("bench.py: --via-mixin covers the video path (no --audio / --recompute-halo)")
-        extra = {k: v for k, v in product_setting.items() if k != "dtype"}
-        if world > 1:
-            extra["tdc_shard_frames"] = True
-        lm = build_mixin_lm(cfg, sd, dev, dtype, extra)
-        enc = lm.get_model().tdc_engine(device=dev, dtype=dtype)       # built by the mixin from its own parameters
-    else:
-        enc = VideoEncoder(sd, cfg, dtype=dtype, device=dev, siglip_heads=16, dino_heads=24, qformer_heads=12,
-                           tower_batch=args.tower_batch, fp8_towers=args.fp8_level if args.dtype == "fp8" else 0,
-                           tower_dtype=tower_dtype, tower_res_dtype=torch.float16 if res16 else None, ln_fuse=args.ln_fuse,
-                           dino_dtype={"bf16": torch.bfloat16, "fp16": torch.float16, "": None}[args.dino_dtype],
-                           selection_refine=None if args.selection_refine < 0 else bool(args.selection_refine))
-        enc.two_streams = bool(two_streams)
-    enc.xattn_mode = args.xattn_mode
-    wav = None
-    if args.audio:
-        sys.path.insert(0, os.path.join(ROOT, "tools"))
-        from bench_beats import random_beats_state
-        from tdc_video_amd.beats import BEATS_ITER3_CFG, BeatsEncoder
-        from tdc_video_amd import weights as Wt
-        enc.cfg["audio_input"] = True
-        enc.c.audio_proj = Wt.make_lin(torch.randn(H, 768, device=dev, generator=gen) * 0.02,
-                                       torch.zeros(H, device=dev), dtype, dev)
-        enc.beats = BeatsEncoder(random_beats_state(BEATS_ITER3_CFG), BEATS_ITER3_CFG, dtype=dtype, device=dev)
-        # 1 frame per second; every rank holds the waveform (16 MB at T = 512) and encodes only its own 10-s windows
-        gw = torch.Generator(device=dev).manual_seed(77)
-        wav = (0.1 * torch.randn(1, 16000 * T, device=dev, generator=gw)).half()
-    sd_cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        sd_cpu = {k: v.cpu() for k, v in sd.items()}
-    del sd
-    torch.cuda.empty_cache()
-
-    prompt_ids = [101] + list(range(2000, 2010)) + [102]          # 12 BERT ids (SURVEY 8(d))
-    lo, hi = seg.shard_ranges(T, world)[rank]
-    if lm is not None:
-        # the reference's call (tdc/language_model/cambrian_qwen.py:415-438): one sample, <image> after the system prompt,
-        # 64 text tokens; every rank is handed the whole video, as the reference's per-GPU eval workers are
-        vs = synth_video(0, T, px_s, dev, tower_dtype)
-        vd = synth_video(0, T, px_d, dev, tower_dtype, seed=4321) if px_d != px_s else vs
-        ids = torch.arange(100, 165, device=dev)
-        ids[14] = -200                                                  # IMAGE_TOKEN_INDEX (tdc/constants.py)
-        ids = ids[None]
-        images = [vs[None], vd[None]]
-
-        def step():
-            o = lm.prepare_inputs_labels_for_multimodal(ids, None, None, None, None, images, image_sizes=[(384, 384)],
-                                                        video_indices=[None], prompts=[prompt_ids], audios=[None])
-            return o[4][0]
-    elif world == 1:
-        vs = synth_video(0, T, px_s, dev, tower_dtype)
-        vd = synth_video(0, T, px_d, dev, tower_dtype, seed=4321) if px_d != px_s else vs
-
-        def step():
-            return enc.encode_video(vs, vd, (384, 384), budget_text_len=64, n_text_tokens=64, prompt_ids=prompt_ids,
-                                    frame_cap=T, audio={"audio_wav": wav} if wav is not None else None)
-    else:
-        from tdc_video_amd import dist as tdist
-        vs = synth_video(lo, hi, px_s, dev, tower_dtype)       # a rank only ever holds its own frames
-        halo = 1 if (args.recompute_halo and lo < hi < T) else 0        # + the right neighbour's first frame, re-encoded here
-        vd = synth_video(lo, hi + halo, px_d, dev, tower_dtype, seed=4321 if px_d != px_s else 1234)
-        sharded = tdist.ShardedVideoEncoder(enc, rank, world)
-
-        def step():
-            return sharded.encode_video(vs, vd, T, (384, 384), n_text_tokens=64, prompt_ids=prompt_ids,
-                                        audio={"audio_wav": wav} if wav is not None else None,
-                                        recompute_halo=bool(args.recompute_halo))
-
-    def barrier():
-        if world > 1:
-            torch.distributed.barrier()
-        torch.cuda.synchronize()
-
-    for _ in range(args.warmup):
-        out = step()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        out = step()
-    barrier()
-    dt = time.perf_counter() - t0
-    rank_ms = None
-    ranks_seen = [0]
-    if world > 1:
-        # who took part, as seen over the process group itself (RCCL at N > 1): every rank's id and device index
-        me = torch.tensor([rank, local], device=dev, dtype=torch.int64)
-        seen = [torch.zeros_like(me) for _ in range(world)]
-        torch.distributed.all_gather(seen, me)
-        ranks_seen = sorted(int(x[0].item()) for x in seen)
-        rank_devices = [int(x[1].item()) for x in sorted(seen, key=lambda x: int(x[0].item()))]
-        # per-rank step times (a straggler shows as max >> min), then the MAX over the ranks as the job's time
-        mine = torch.tensor([dt], device=dev, dtype=torch.float64)
-        every = [torch.zeros_like(mine) for _ in range(world)]
-        torch.distributed.all_gather(every, mine)
-        rank_ms = [round(float(x.item()) / args.steps * 1e3, 2) for x in every]
-        dt = max(float(x.item()) for x in every)
-    ms_per_step = dt / args.steps * 1e3
-    fps = T * args.steps / dt
-    if args.dump_outputs and rank == 0:
-        dump_outputs(out, args.dump_outputs)
-
-    # ---- roofline of the dominant kernel (tdc_gemm MFMA kernel): one extra pass under the library's launch profiler
-    # (tdc_profile_*: hipEvents recorded inside libtdc_hip.so around every GEMM / attention / LayerNorm / fused cross-attention
-    # launch, on the stream the kernel is launched on) - the SAME host path as the timed steps: the C++ composites
-    # tdc_vit_fwd / tdc_connector_fwd / tdc_qformer_fwd, not a per-kernel Python replay of them
     ops.profile_start()
     step()
     torch.cuda.synchronize()
@@ -740,6 +516,247 @@ def main():
             tflops=MFMA_DENSE_SUSTAINED_TFLOPS, frac=round(achieved / MFMA_DENSE_SUSTAINED_TFLOPS, 4),
             note="replayed constant, not measured in this run: bf16 16x16x32 MFMAs on dense random register operands, no memory "
                  "traffic, every CU busy (tools/mfma_power.cpp, profiles/r02_mfma_power.log); all-zero operands reach 2448")
+    return roofline
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--frames", type=int, default=512)
+    ap.add_argument("--K", type=int, default=144, help="context_token_num (BASELINE configs: 144; reference default 16)")
+    ap.add_argument("--hidden", type=int, default=3584, help="LLM embed dim (Qwen2-7B)")
+    ap.add_argument("--dtype", default="mixed", choices=["mixed", "bf16", "fp16", "fp8"],
+                    help="mixed (default): the two ViT towers in bf16, connector + Q-Former in fp16 - the type whose compressed "
+                         "tokens pass the north_star's 1e-3 against the fp32 oracle at full depth (tests/test_hip_configs.py); "
+                         "fp8 (BASELINE config 5): e4m3 operands for the towers' LayerNorm-fed GEMMs (qkv, fc1) through "
+                         "v_mfma_f32_16x16x128_f8f6f4, bf16 everywhere else")
+    ap.add_argument("--res", default="fp16", choices=["fp16", "fp32"],
+                    help="the towers' residual stream in HBM: fp16 (default; the reference's own arithmetic - its HF towers run "
+                         "under torch_dtype=float16 - 4 B per element and residual add, sums formed in fp32 and rounded once) or fp32 "
+                         "(8 B per element: rounds 1-3)")
+    ap.add_argument("--dino-dtype", default="", choices=["", "bf16", "fp16"], help="operand type of the DINOv2 tower alone "
+                    "(config.tdc_dino_dtype; default: the towers' type): fp16 keeps the a5 similarities at the reference's precision")
+    ap.add_argument("--selection-refine", type=int, default=-1, choices=[-1, 0, 1], help="a5 at the reference's precision under bf16 "
+                    "DINOv2 operands (VideoEncoder.selection_refine): -1 = automatic (on for bf16 DINOv2 operands), 0 / 1.  The synthetic "
+                    "video's decisive similarity ranks are 0.43 apart, so nothing is re-encoded in the timed region either way")
+    ap.add_argument("--ln-fuse", action="store_true", help="the towers' pre-LayerNorms folded into the neighbouring GEMMs "
+                    "(VideoEncoder(ln_fuse=True)); over the fp16 residual stream this needs --dtype fp16: the consumer GEMMs read the "
+                    "stream itself, no LayerNorm kernel runs inside the layer loop")
+    ap.add_argument("--px", type=int, default=384, help="SigLIP input size (DINO uses px-6: 378); 336 -> 336/336")
+    ap.add_argument("--fp8-level", type=int, default=1, choices=[1, 2, 3],
+                    help="--dtype fp8: 1 = qkv / fc1 (quantised by the LayerNorm kernel), 2 = also out-proj / fc2, "
+                         "3 = as 2 with the MLP hidden written as e4m3 by fc1 itself")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure what the headline does not need: "
+                    "`roofline` (one extra step under the library's launch profiler; N = 1: + the counter leg of --pmc) and, N = 1, "
+                    "`cpu_baseline` (the oracle on the host cores).  Without it a run sets up, warms up, times its steps, writes "
+                    "--dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without `cpu_baseline`")
+    ap.add_argument("--tower-batch", type=int, default=512)
+    ap.add_argument("--two-streams", type=int, default=-1, help="run the two towers on two HIP streams: 0 / 1, -1 = on at <= 128 "
+                    "frames per rank (small batches leave partly filled last tile rounds, which the other tower's workgroups fill)")
+    ap.add_argument("--gemm-shape-times", default="", help="--full: write per-shape GEMM times of the profiled step to this file")
+    ap.add_argument("--xattn-mode", type=int, default=1, choices=[0, 1, 2], help="Q-Former cross-attention block: 0 = per-kernel "
+                    "sequence (stacked K/V GEMM, q GEMM, tdc_attention, dense GEMM, LayerNorm), 1 = output projection + residual + "
+                    "LayerNorm in one kernel behind q GEMM + tdc_attention, 2 = the whole block in one kernel per layer "
+                    "(tdc_qformer_xattn)")
+    ap.add_argument("--recompute-halo", action="store_true", help="N > 1: every rank re-encodes its right neighbour's first frame "
+                    "through DINOv2 instead of receiving its features point to point (fallback form of the boundary exchange)")
+    ap.add_argument("--audio", action="store_true", help="BASELINE config 4: + T seconds of 16 kHz audio through BEATs "
+                    "on the device, 50 audio tokens per frame in the Q-Former KV (1 GPU only)")
+    ap.add_argument("--pmc", default="auto", choices=["auto", "on", "off"], help="--full, N = 1: after the timed region collect FETCH_SIZE / "
+                    "WRITE_SIZE / SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE in fresh child processes (rocprofv3 --pmc over a torch-free "
+                    "replay of this run's GEMM launches) and report them as roofline.traffic / mfma_busy_pmc; auto = when rocprofv3 exists")
+    ap.add_argument("--pmc-budget", type=float, default=90.0, help="wall-clock budget of that leg in seconds")
+    ap.add_argument("--pmc-out", default="", help="write the leg's per-shape summary (JSON) to this file")
+    ap.add_argument("--launch-timeout", type=float, default=-1.0, help="N > 1 started as plain `python bench.py --gpus N`: wall-clock "
+                    "guard of the launcher in seconds; on expiry every rank is stopped and the exit code is 124 (0 = no guard; default "
+                    "600 + 4 x (steps + warmup))")
+    ap.add_argument("--rank-timeout", type=float, default=-1.0, help="wall-clock guard inside every rank in seconds (0 = none; "
+                    "default 600 + 4 x (steps + warmup): a step takes 1.2 s at T = 512 on one GPU)")
+    ap.add_argument("--collective-timeout", type=float, default=180.0, help="N > 1: timeout of the process group (rendezvous and "
+                    "every collective) in seconds")
+    ap.add_argument("--via-mixin", action="store_true", help="drive the step through the drop-in boundary instead of VideoEncoder: "
+                    "a stub language model hosting model.CambrianMetaForCausalLM, one call of prepare_inputs_labels_for_multimodal("
+                    "input_ids, ..., images=[siglip[1,T,...], dino[1,T,...]], image_sizes, video_indices=[None], prompts=[ids]) per "
+                    "step with config.tdc_frame_cap = T (N > 1: + config.tdc_shard_frames, every rank holds the whole video as the "
+                    "reference's eval workers do); the JSON line says config.entry = \"mixin\"")
+    ap.add_argument("--dump-gemm-shapes", default=None, help="--full: write the GEMM launches of one step (for tools/gemm_pmc)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the last one returned "
+                    "(the emitted tokens) as float32 DIR/tokens.npy: the whole array, or past 48 MiB a seeded sample of it "
+                    "(dump_outputs); inputs and weights are seeded, so runs with the same arguments compare output for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        needs = [o for o, v in (("--gemm-shape-times", args.gemm_shape_times), ("--dump-gemm-shapes", args.dump_gemm_shapes),
+                                ("--pmc on", args.pmc == "on"), ("--pmc-out", args.pmc_out)) if v]
+        if needs:
+            ap.error("%s: only with --full (they report on its profiled step)" % ", ".join(needs))
+    for k in ("launch_timeout", "rank_timeout"):
+        if getattr(args, k) < 0:
+            setattr(args, k, 600.0 + 4.0 * (args.steps + args.warmup))
+
+    if args.gpus > 1 and "RANK" not in os.environ:
+        # plain `python bench.py --gpus N`: become the launcher.  Nothing above has touched the GPU (no torch.cuda call), and
+        # nothing below this branch runs in this process.
+        sys.exit(self_launch(args.gpus, args.launch_timeout))
+    rank = int(os.environ.get("RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    if world != args.gpus:
+        sys.exit("bench.py: --gpus %d but WORLD_SIZE=%d (run `python bench.py --gpus N` by itself, or under "
+                 "torch.distributed.run --nproc-per-node N)" % (args.gpus, world))
+    # test hooks (never set by the driver): TDC_BENCH_ONE_GPU=1 maps every rank onto GPU 0 and TDC_DIST_BACKEND=gloo
+    # swaps the transport, so the N>1 code path can be exercised on a 1-GPU box
+    if os.environ.get("TDC_BENCH_ONE_GPU"):
+        local = 0
+    guard = rank_guard(args.rank_timeout)
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    if world > 1:
+        import datetime
+        import torch.distributed as dist
+        backend = os.environ.get("TDC_DIST_BACKEND", "nccl")
+        # a bounded timeout on the rendezvous and on every collective: a rank that never arrives fails the job within minutes
+        tmo = datetime.timedelta(seconds=args.collective_timeout)
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=dev, timeout=tmo)
+        else:
+            dist.init_process_group(backend, timeout=tmo)
+    import tdc_video_amd  # noqa: F401
+    from tdc_video_amd.pipeline import VideoEncoder
+    from tdc_video_amd import segment as seg
+    if os.environ.get("TDC_BENCH_PERSIST_GRID"):     # experiment hook of self_launch's CU split (tools/half_chip_gate.sh)
+        from tdc_video_amd import lib as tlib
+        tlib.load().tdc_gemm_set_persistent_grid(int(os.environ["TDC_BENCH_PERSIST_GRID"]))
+
+    dtype = torch.float16 if args.dtype in ("fp16", "mixed") else torch.bfloat16          # connector, Q-Former, outputs
+    tower_dtype = torch.bfloat16 if args.dtype == "mixed" else dtype                       # the two ViT towers
+    T, K, H = args.frames, args.K, args.hidden
+    px_s = args.px
+    px_d = args.px - 6 if args.px == 384 else args.px
+    cfg = model_cfg(H, K, T)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    sd = random_state_dict(H, K, dev, gen, siglip_px=px_s)
+    two_streams = args.two_streams if args.two_streams >= 0 else int((T + world - 1) // world <= 128)
+    res16 = args.res == "fp16"
+    product_setting = {"dtype": str(dtype).replace("torch.", ""), "tdc_tower_dtype": str(tower_dtype).replace("torch.", ""),
+                       "tdc_tower_res_dtype": "float16" if res16 else "float32", "tdc_tower_batch": args.tower_batch,
+                       "tdc_fp8_towers": args.fp8_level if args.dtype == "fp8" else 0, "tdc_frame_cap": T,
+                       "tdc_two_streams": bool(two_streams)}
+    if args.ln_fuse:
+        product_setting["tdc_ln_fuse"] = True
+    if args.selection_refine >= 0:
+        product_setting["tdc_selection_refine"] = bool(args.selection_refine)
+    if args.dino_dtype:
+        product_setting["tdc_dino_dtype"] = {"bf16": "bfloat16", "fp16": "float16"}[args.dino_dtype]
+    lm = None
+    if args.via_mixin:
+        if args.audio or args.recompute_halo:
+            sys.exit("bench.py: --via-mixin covers the video path (no --audio / --recompute-halo)")
+        extra = {k: v for k, v in product_setting.items() if k != "dtype"}
+        if world > 1:
+            extra["tdc_shard_frames"] = True
+        lm = build_mixin_lm(cfg, sd, dev, dtype, extra)
+        enc = lm.get_model().tdc_engine(device=dev, dtype=dtype)       # built by the mixin from its own parameters
+    else:
+        enc = VideoEncoder(sd, cfg, dtype=dtype, device=dev, siglip_heads=16, dino_heads=24, qformer_heads=12,
+                           tower_batch=args.tower_batch, fp8_towers=args.fp8_level if args.dtype == "fp8" else 0,
+                           tower_dtype=tower_dtype, tower_res_dtype=torch.float16 if res16 else None, ln_fuse=args.ln_fuse,
+                           dino_dtype={"bf16": torch.bfloat16, "fp16": torch.float16, "": None}[args.dino_dtype],
+                           selection_refine=None if args.selection_refine < 0 else bool(args.selection_refine))
+        enc.two_streams = bool(two_streams)
+    enc.xattn_mode = args.xattn_mode
+    wav = None
+    if args.audio:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        from bench_beats import random_beats_state
+        from tdc_video_amd.beats import BEATS_ITER3_CFG, BeatsEncoder
+        from tdc_video_amd import weights as Wt
+        enc.cfg["audio_input"] = True
+        enc.c.audio_proj = Wt.make_lin(torch.randn(H, 768, device=dev, generator=gen) * 0.02,
+                                       torch.zeros(H, device=dev), dtype, dev)
+        enc.beats = BeatsEncoder(random_beats_state(BEATS_ITER3_CFG), BEATS_ITER3_CFG, dtype=dtype, device=dev)
+        # 1 frame per second; every rank holds the waveform (16 MB at T = 512) and encodes only its own 10-s windows
+        gw = torch.Generator(device=dev).manual_seed(77)
+        wav = (0.1 * torch.randn(1, 16000 * T, device=dev, generator=gw)).half()
+    sd_cpu = None
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        sd_cpu = {k: v.cpu() for k, v in sd.items()}
+    del sd
+    torch.cuda.empty_cache()
+
+    prompt_ids = [101] + list(range(2000, 2010)) + [102]          # 12 BERT ids (SURVEY 8(d))
+    lo, hi = seg.shard_ranges(T, world)[rank]
+    if lm is not None:
+        # the reference's call (tdc/language_model/cambrian_qwen.py:415-438): one sample, <image> after the system prompt,
+        # 64 text tokens; every rank is handed the whole video, as the reference's per-GPU eval workers are
+        vs = synth_video(0, T, px_s, dev, tower_dtype)
+        vd = synth_video(0, T, px_d, dev, tower_dtype, seed=4321) if px_d != px_s else vs
+        ids = torch.arange(100, 165, device=dev)
+        ids[14] = -200                                                  # IMAGE_TOKEN_INDEX (tdc/constants.py)
+        ids = ids[None]
+        images = [vs[None], vd[None]]
+
+        def step():
+            o = lm.prepare_inputs_labels_for_multimodal(ids, None, None, None, None, images, image_sizes=[(384, 384)],
+                                                        video_indices=[None], prompts=[prompt_ids], audios=[None])
+            return o[4][0]
+    elif world == 1:
+        vs = synth_video(0, T, px_s, dev, tower_dtype)
+        vd = synth_video(0, T, px_d, dev, tower_dtype, seed=4321) if px_d != px_s else vs
+
+        def step():
+            return enc.encode_video(vs, vd, (384, 384), budget_text_len=64, n_text_tokens=64, prompt_ids=prompt_ids,
+                                    frame_cap=T, audio={"audio_wav": wav} if wav is not None else None)
+    else:
+        from tdc_video_amd import dist as tdist
+        vs = synth_video(lo, hi, px_s, dev, tower_dtype)       # a rank only ever holds its own frames
+        halo = 1 if (args.recompute_halo and lo < hi < T) else 0        # + the right neighbour's first frame, re-encoded here
+        vd = synth_video(lo, hi + halo, px_d, dev, tower_dtype, seed=4321 if px_d != px_s else 1234)
+        sharded = tdist.ShardedVideoEncoder(enc, rank, world)
+
+        def step():
+            return sharded.encode_video(vs, vd, T, (384, 384), n_text_tokens=64, prompt_ids=prompt_ids,
+                                        audio={"audio_wav": wav} if wav is not None else None,
+                                        recompute_halo=bool(args.recompute_halo))
+
+    def barrier():
+        if world > 1:
+            torch.distributed.barrier()
+        torch.cuda.synchronize()
+
+    for _ in range(args.warmup):
+        out = step()
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        out = step()
+    barrier()
+    dt = time.perf_counter() - t0
+    rank_ms = None
+    ranks_seen = [0]
+    if world > 1:
+        # who took part, as seen over the process group itself (RCCL at N > 1): every rank's id and device index
+        me = torch.tensor([rank, local], device=dev, dtype=torch.int64)
+        seen = [torch.zeros_like(me) for _ in range(world)]
+        torch.distributed.all_gather(seen, me)
+        ranks_seen = sorted(int(x[0].item()) for x in seen)
+        rank_devices = [int(x[1].item()) for x in sorted(seen, key=lambda x: int(x[0].item()))]
+        # per-rank step times (a straggler shows as max >> min), then the MAX over the ranks as the job's time
+        mine = torch.tensor([dt], device=dev, dtype=torch.float64)
+        every = [torch.zeros_like(mine) for _ in range(world)]
+        torch.distributed.all_gather(every, mine)
+        rank_ms = [round(float(x.item()) / args.steps * 1e3, 2) for x in every]
+        dt = max(float(x.item()) for x in every)
+    ms_per_step = dt / args.steps * 1e3
+    fps = T * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+
+    roofline = roofline_leg(args, step, enc, rank, world, two_streams, ms_per_step) if args.full else None
     if world > 1:
         # every rank is done with the process group: leave it in step (a rank that exits while a peer is still inside a
         # collective shows up as a watchdog abort in that peer's log)
@@ -778,8 +795,9 @@ def main():
         "rank_ms_per_step": None if rank_ms is None else {"min": min(rank_ms), "max": max(rank_ms), "per_rank": rank_ms},
         "ranks_seen": ranks_seen, "rank_devices": rank_devices if world > 1 else [local],
         "dist_backend": (os.environ.get("TDC_DIST_BACKEND", "nccl") + " (RCCL)" * (os.environ.get("TDC_DIST_BACKEND", "nccl") == "nccl")) if world > 1 else None,
-        "roofline": roofline,
     }
+    if roofline is not None:
+        res["roofline"] = roofline
     if sd_cpu is not None:
         res["cpu_baseline"] = cpu_baseline(sd_cpu, cfg, H, K, px_s, px_d)
     print(json.dumps(res))

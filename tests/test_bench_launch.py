@@ -47,7 +47,7 @@ def test_plain_python_bench_gpus2_on_one_gpu(via_mixin):
     every rank calls prepare_inputs_labels_for_multimodal with the whole video and config.tdc_shard_frames splits its frames
     over the ranks (model.py -> dist.ShardedVideoEncoder); the emitted stream has the same length either way."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "64", "--steps", "1",
-                        "--warmup", "1", "--no-cpu-baseline"] + (["--via-mixin"] if via_mixin else []),
+                        "--warmup", "1", "--full"] + (["--via-mixin"] if via_mixin else []),
                        env=_env(TDC_BENCH_ONE_GPU="1", TDC_DIST_BACKEND="gloo"),
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -101,6 +101,15 @@ def test_steps_below_one_is_an_error_message():
     assert r.returncode == 2 and "--steps" in r.stderr and "Traceback" not in r.stderr
 
 
+def test_profiled_step_outputs_need_full():
+    """What reports on --full's profiled step is an argument error in a plain run, not a silently missing file."""
+    for extra in (["--dump-gemm-shapes", "shapes.txt"], ["--gemm-shape-times", "times.txt"], ["--pmc-out", "pmc.json"],
+                  ["--pmc", "on"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, env=_env(), capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 2 and "--full" in r.stderr and "Traceback" not in r.stderr, (extra, r.stderr[-500:])
+
+
 def test_dump_outputs_writes_the_whole_output_or_a_fixed_sample(tmp_path, monkeypatch):
     """--dump-outputs: float32 tokens.npy, the whole array when it fits DUMP_BYTES, otherwise every row at a seeded choice of
     columns (or, when too few columns fit, a seeded choice of rows at DUMP_MIN_COLS columns) - the same choice on every call."""
@@ -141,6 +150,27 @@ def test_bench_dump_outputs_and_steps(tmp_path):
     a = np.load(str(tmp_path / "tokens.npy"))
     assert a.dtype == np.float32 and a.shape[0] == res["config"]["emitted_tokens"] and 0 < a.shape[1] <= res["config"]["hidden"]
     assert np.isfinite(a).all() and a.nbytes <= 64 << 20
+
+
+@pytest.mark.gpu
+def test_bench_full_adds_the_roofline_and_leaves_the_steps_alone(tmp_path):
+    """A plain run measures the headline alone; --full adds `roofline` from one extra profiled step after the timed ones, and
+    the timed steps compute the same tokens either way."""
+    import numpy as np
+    got = {}
+    for full in (False, True):
+        d = tmp_path / ("full" if full else "plain")
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--frames", "64", "--steps", "1",
+                            "--warmup", "1", "--dump-outputs", str(d)] + (["--full", "--no-cpu-baseline", "--pmc", "off"] if full else []),
+                           env=_env(), capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        got[full] = json.loads(lines[0]), np.load(str(d / "tokens.npy"))
+    plain, full = got[False][0], got[True][0]
+    assert "roofline" not in plain and "cpu_baseline" not in plain
+    assert full["roofline"]["frac"] > 0 and full["roofline"]["launches"] > 0 and "cpu_baseline" not in full
+    assert plain["config"] == full["config"] and np.array_equal(got[False][1], got[True][1])
 
 
 @pytest.mark.gpu

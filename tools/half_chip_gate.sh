@@ -6,7 +6,7 @@ set -o pipefail
 O=gpurun_out/half_chip_gate.log
 LO=0x$(printf 'f%.0s' $(seq 32))
 HI=0x$(printf 'f%.0s' $(seq 32))$(printf '0%.0s' $(seq 32))
-B="timeout -k 10 420 python bench.py --no-cpu-baseline --steps 6 --warmup 2"
+B="timeout -k 10 420 python bench.py --full --no-cpu-baseline --steps 6 --warmup 2"
 pick() { python -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); r=d['roofline']; print(sys.argv[2], 'frames', d['config']['frames'], 'fps', d['value'], 'ms', d['ms_per_step'], 'gemm_ms', r['gemm_ms_per_step'], 'gemm_TF', r['achieved'], 'attn_ms', r['attention']['ms_per_step'], 'ln_ms', r['layernorm_ms_per_step'])" "$1" "$2" >> $O; }
 : > $O
 echo "== 0. sanity: a masked process runs at all" >> $O

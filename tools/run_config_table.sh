@@ -5,7 +5,7 @@
 # default, context_token_num of the released checkpoints).
 O=gpurun_out/cfg
 mkdir -p $O
-run() { name=$1; shift; timeout -k 10 400 python bench.py --no-cpu-baseline --pmc off "$@" > $O/$name.json 2> $O/$name.err || echo "$name failed"; python3 -c "
+run() { name=$1; shift; timeout -k 10 400 python bench.py --full --no-cpu-baseline --pmc off "$@" > $O/$name.json 2> $O/$name.err || echo "$name failed"; python3 -c "
 import json,sys
 d=json.loads(open('$O/$name.json').read().strip().splitlines()[-1]); r=d['roofline']; x=r['xattn_block']
 print('%-28s %7.1f frames/s %8.1f ms  gemm frac %.4f  xattn_block %.3f ms frac %s  emitted %d' % ('$name', d['value'], d['ms_per_step'], r['frac'], x['ms_per_step'], x['frac'], d['config']['emitted_tokens']))"; }

@@ -1,7 +1,7 @@
 #!/bin/bash
 # HBM-traffic and MFMA-busy counters (one counter per pass) of the GEMM kernels on the bench's shapes (run on the MI355X box from the repo root).
-#   1. python bench.py --steps 1 --warmup 0 --no-cpu-baseline --dump-gemm-shapes gpurun_out/gemm_shapes.txt
-#   2. bash tools/run_gemm_pmc.sh gpurun_out/gemm_shapes.txt
+#   1. python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --dump-gemm-shapes gemm_shapes.txt
+#   2. bash tools/run_gemm_pmc.sh gemm_shapes.txt
 set -e
 export PMC_REPS=${PMC_REPS:-2}     # launches per shape; the summary takes the last one
 SHAPES=${1:-tools/gemm_shapes_T512.txt}
