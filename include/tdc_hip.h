@@ -180,6 +180,22 @@ int tdc_resample_tokens(const void* x, int x_f32, int ldx, int tok_off, int n_in
  * order is fixed (fp32), so the similarity ranking is reproducible run to run. */
 int tdc_frame_cossim(const void* f, long long n, int T, float* sims, float* scratch, int dtype, void* stream);
 size_t tdc_frame_cossim_scratch_floats(int T);
+/* cosine similarity of arbitrary slot pairs of a slab of per-frame features (the frame cache's DINOv2 rows): frame s starts
+ * at slab + s * slot_stride elements (16-bit, slot_stride % 8 == 0, slab 16-byte aligned), n elements each (n % 8 == 0);
+ * pairs: device int32 [n_pairs, 2] (slot_a, slot_b), n_pairs <= 65535.  sims[p] is bit for bit what tdc_frame_cossim gives
+ * for the same two frames adjacent in a contiguous buffer (shared chunking and reduction order).
+ * scratch: tdc_pair_cossim_scratch_floats(n_pairs) floats. */
+int tdc_pair_cossim(const void* slab, long long slot_stride, long long n, const int* pairs, int n_pairs, float* sims,
+                    float* scratch, int dtype, void* stream);
+size_t tdc_pair_cossim_scratch_floats(int n_pairs);
+/* 128-bit content fingerprint of rows of any type: row r = the row_bytes bytes at base + rows[r] * row_stride (rows: device
+ * int32 [n_rows], n_rows <= 65535; any alignment, any length) -> out[2r], out[2r + 1] (device u64).  Words w_i = the row as
+ * little-endian u64 (tail zero-padded), x_i = w_i ^ (i * 0x9E3779B97F4A7C15), h_k = mix(sum_i mix(x_i ^ S_k) ^ row_bytes)
+ * with the splitmix64 finaliser mix and S_1 = 0x243F6A8885A308D3, S_2 = 0x13198A2E03707344 (sums mod 2^64: the bits do not
+ * depend on the reduction order).  Not cryptographic.  scratch: tdc_fingerprint_rows_scratch_bytes(n_rows) bytes. */
+int tdc_fingerprint_rows(const void* base, long long row_stride, const int* rows, int n_rows, long long row_bytes,
+                         unsigned long long* out, void* scratch, void* stream);
+size_t tdc_fingerprint_rows_scratch_bytes(int n_rows);
 /* mean over the token axis: x [B, P, ld] 16-bit -> y [B, ld] 16-bit (global context, cambrian_arch.py:1009) */
 int tdc_token_mean(const void* x, int P, int ld, void* y, int B, int dtype, void* stream);
 /* adaptive_avg_pool1d over the token axis: y[b, k] = mean of x rows [floor(kN/K), ceil((k+1)N/K)) of frame

@@ -147,16 +147,15 @@ __global__ __launch_bounds__(256) void resample8_kernel(const T* x, int ldx, int
 
 // ------------------------------------------------------------------------------------------------ cos-sim
 // pass 1: partial sums of <f_t, f_t> and <f_t, f_{t+1}> (fp32, fixed reduction order => deterministic ranking);
-// grid (chunks, T).  pass 2: combine.
+// grid (chunks, T).  pass 2: combine.  tdc_frame_cossim (adjacent frames of one buffer) and tdc_pair_cossim (arbitrary slot
+// pairs of a slab) share cossim_chunk / cossim_combine, so the two give the same bits for the same two frames: the <a, a>
+// partials do not depend on the partner b, and the chunking, thread stride and reduction order are the same code.
 constexpr int CS_CHUNKS = 32;
 template <class T>
-__global__ __launch_bounds__(256) void cossim_partial(const T* f, long long n, int Tn, float* part) {
+__device__ __forceinline__ void cossim_chunk(const T* a, const T* b, long long n, int ch, float* out) {
     typedef typename VecOf<T>::v8 v8;
-    const int t = blockIdx.y, ch = blockIdx.x;
     const long long per = ((n / 8 + CS_CHUNKS - 1) / CS_CHUNKS) * 8;
     const long long lo = ch * per, hi = (lo + per < n) ? lo + per : n;
-    const T* a = f + (long long)t * n;
-    const T* b = f + (long long)(t + 1 < Tn ? t + 1 : t) * n;
     float saa = 0.f, sab = 0.f;
     for (long long i = lo + threadIdx.x * 8; i < hi; i += 256 * 8) {
         v8 va = *(const v8*)(a + i), vb = *(const v8*)(b + i);
@@ -173,21 +172,45 @@ __global__ __launch_bounds__(256) void cossim_partial(const T* f, long long n, i
     if ((threadIdx.x & 63) == 0) { red[0][w] = saa; red[1][w] = sab; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        part[((long long)t * CS_CHUNKS + ch) * 2 + 0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        part[((long long)t * CS_CHUNKS + ch) * 2 + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        out[0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        out[1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
     }
+}
+// pa / pb: the CS_CHUNKS (aa, ab) partials of frame a (partnered with b) and of frame b (its own aa)
+__device__ __forceinline__ float cossim_combine(const float* pa, const float* pb) {
+    float aa = 0.f, ab = 0.f, bb = 0.f;
+    for (int c = 0; c < CS_CHUNKS; ++c) {
+        aa += pa[c * 2];
+        ab += pa[c * 2 + 1];
+        bb += pb[c * 2];
+    }
+    // F.cosine_similarity: x.y / max(|x| |y|, eps) with eps = 1e-8
+    return ab / fmaxf(sqrtf(aa) * sqrtf(bb), 1e-8f);
+}
+template <class T>
+__global__ __launch_bounds__(256) void cossim_partial(const T* f, long long n, int Tn, float* part) {
+    const int t = blockIdx.y, ch = blockIdx.x;
+    cossim_chunk(f + (long long)t * n, f + (long long)(t + 1 < Tn ? t + 1 : t) * n, n, ch,
+                 part + ((long long)t * CS_CHUNKS + ch) * 2);
 }
 __global__ void cossim_final(const float* part, int Tn, float* sims) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= Tn - 1) return;
-    float aa = 0.f, ab = 0.f, bb = 0.f;
-    for (int c = 0; c < CS_CHUNKS; ++c) {
-        aa += part[((long long)t * CS_CHUNKS + c) * 2];
-        ab += part[((long long)t * CS_CHUNKS + c) * 2 + 1];
-        bb += part[((long long)(t + 1) * CS_CHUNKS + c) * 2];
-    }
-    // F.cosine_similarity: x.y / max(|x| |y|, eps) with eps = 1e-8
-    sims[t] = ab / fmaxf(sqrtf(aa) * sqrtf(bb), 1e-8f);
+    sims[t] = cossim_combine(part + (long long)t * CS_CHUNKS * 2, part + (long long)(t + 1) * CS_CHUNKS * 2);
+}
+// pairs: grid (chunks, n_pairs, 2); side 0 = slot a partnered with slot b, side 1 = slot b (its own <b, b> only)
+template <class T>
+__global__ __launch_bounds__(256) void pair_cossim_partial(const T* slab, long long slot_stride, long long n, const int* pairs,
+                                                           float* part) {
+    const int p = blockIdx.y, side = blockIdx.z, ch = blockIdx.x;
+    const long long sa = pairs[2 * p], sb = pairs[2 * p + 1];
+    const T* b = slab + sb * slot_stride;
+    cossim_chunk(side ? b : slab + sa * slot_stride, b, n, ch, part + (((long long)p * 2 + side) * CS_CHUNKS + ch) * 2);
+}
+__global__ void pair_cossim_final(const float* part, int n_pairs, float* sims) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs) return;
+    sims[p] = cossim_combine(part + (long long)p * 2 * CS_CHUNKS * 2, part + ((long long)p * 2 + 1) * CS_CHUNKS * 2);
 }
 
 // ------------------------------------------------------------------------------------------------ pooling
@@ -508,6 +531,19 @@ extern "C" int tdc_frame_cossim(const void* f, long long n, int T, float* sims, 
     return (int)hipGetLastError();
 }
 extern "C" size_t tdc_frame_cossim_scratch_floats(int T) { return (size_t)T * CS_CHUNKS * 2; }
+
+extern "C" int tdc_pair_cossim(const void* slab, long long slot_stride, long long n, const int* pairs, int n_pairs,
+                               float* sims, float* scratch, int dtype, void* stream) {
+    if (!slab || !pairs || !sims || !scratch || n_pairs <= 0 || n_pairs > 65535 || n <= 0 || (n % 8) != 0 || slot_stride < n ||
+        (slot_stride % 8) != 0 || ((uintptr_t)slab & 15))
+        return TDC_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH(dtype, hipLaunchKernelGGL(pair_cossim_partial<TT>, dim3(CS_CHUNKS, n_pairs, 2), dim3(256), 0, st,
+                                       (const TT*)slab, slot_stride, n, pairs, scratch));
+    hipLaunchKernelGGL(pair_cossim_final, dim3((n_pairs + 255) / 256), dim3(256), 0, st, scratch, n_pairs, sims);
+    return (int)hipGetLastError();
+}
+extern "C" size_t tdc_pair_cossim_scratch_floats(int n_pairs) { return (size_t)n_pairs * 2 * CS_CHUNKS * 2; }
 
 extern "C" int tdc_token_mean(const void* x, int P, int ld, void* y, int B, int dtype, void* stream) {
     if (!x || !y || B <= 0 || P <= 0 || ld <= 0 || (ld & 7) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15)) return TDC_E_BADARG;

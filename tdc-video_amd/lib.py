@@ -161,6 +161,12 @@ SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "tdc_frame_cossim": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "tdc_frame_cossim_scratch_floats": (C.c_size_t, [C.c_int]),
+    "tdc_pair_cossim": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_int, C.c_void_p]),
+    "tdc_pair_cossim_scratch_floats": (C.c_size_t, [C.c_int]),
+    "tdc_fingerprint_rows": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "tdc_fingerprint_rows_scratch_bytes": (C.c_size_t, [C.c_int]),
     "tdc_token_mean": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tdc_adaptive_pool_tokens": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                            C.c_void_p, C.c_int, C.c_void_p]),

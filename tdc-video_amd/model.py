@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import lib as L
 from . import segment as seg
-from .pipeline import VideoEncoder
+from .pipeline import VideoEncoder, encode_image_cached
 
 IGNORE_INDEX = -100        # tdc/constants.py
 IMAGE_TOKEN_INDEX = -200
@@ -369,7 +369,8 @@ class CambrianMetaModel:
         (VideoEncoder.auto_tower_batch; the result does not depend on it bit for bit, the reference's own chunk is 64,
         tdc/cambrian_arch.py:698-745);
         `config.tdc_frame_cap` (default 224 = the reference's "in case of OOM" constant, tdc/cambrian_arch.py:907-916,813-822):
-        the cap of both frame sub-samplings; `config.tdc_shard_frames`: see prepare_inputs_labels_for_multimodal.
+        the cap of both frame sub-samplings; `config.tdc_shard_frames`: see prepare_inputs_labels_for_multimodal;
+        `config.tdc_video_cache_bytes`: see tdc_video_cache.
         bench.py's line is reproduced by dtype=float16, tdc_tower_dtype="bfloat16", tdc_tower_res_dtype="float16",
         tdc_frame_cap=T (its `product_setting` field says so; `bench.py --via-mixin` runs exactly that)."""
         if self._tdc_encoder is None or refresh:
@@ -420,6 +421,30 @@ class CambrianMetaModel:
         if isinstance(cap, bool) or not isinstance(cap, int) or cap < 1:
             raise ValueError("config.tdc_frame_cap must be a positive frame count, got %r" % (cap,))
         return cap
+
+    def tdc_video_cache(self):
+        """the engine's FrameCache (cache.py) when `config.tdc_video_cache_bytes` is a positive byte budget; None when the key
+        is absent or 0.  Videos and single images then skip the towers and the connector for frames whose content the
+        cache holds - the results are bit for bit those without it.  Ignored (None) under `config.tdc_shard_frames`:
+        the frame-sharded path does not cache.  A new engine (tdc_engine(refresh=True)) gets a new, empty cache."""
+        n = getattr(self.config, "tdc_video_cache_bytes", None)
+        if isinstance(n, bool) or not (n is None or isinstance(n, int)) or (n or 0) < 0:
+            raise ValueError("config.tdc_video_cache_bytes must be a byte budget (a non-negative int; 0 / absent = off), "
+                             "got %r" % (n,))
+        if not n or getattr(self.config, "tdc_shard_frames", False):
+            return None
+        eng = self.tdc_engine()
+        c = getattr(self, "_tdc_video_cache", None)
+        if c is None or getattr(self, "_tdc_video_cache_engine", None) is not eng or c.max_bytes != n:
+            c = self._tdc_video_cache = eng.new_cache(n)
+            self._tdc_video_cache_engine = eng
+        return c
+
+    def tdc_video_cache_clear(self):
+        """empty the frame cache (and release its device memory); no-op when it is off"""
+        c = getattr(self, "_tdc_video_cache", None)
+        if c is not None:
+            c.clear()
 
     def tdc_side_stream(self, frames_per_rank):
         """engine.two_streams (pipeline.start_side_tower): the config's choice, by default on at <= 128 frames per rank"""
@@ -538,6 +563,7 @@ class CambrianMetaForCausalLM(ABC):
         if towers is None or images is None or input_ids.shape[1] == 1:
             return (input_ids, position_ids, attention_mask, past_key_values, None, labels, None, None, None, None)
         eng = model.tdc_engine()
+        vcache = model.tdc_video_cache()             # config.tdc_video_cache_bytes (validated even when no video comes)
         cfgd = self._cfg()
         K = cfgd.get("context_token_num", 16)
         H = model.config.hidden_size
@@ -606,7 +632,8 @@ class CambrianMetaForCausalLM(ABC):
                     # with the same video - how the reference's eval drivers start their workers, eval/eval_mlvu.py:129-157 -
                     # but here the ranks split the FRAMES of the one video): this rank encodes frames [lo, hi) of the a1
                     # selection, dist.ShardedVideoEncoder exchanges what crosses the rank boundaries and all-gathers the
-                    # emitted tokens, so every rank returns the same 10-tuple as the serial path, bit for bit
+                    # emitted tokens, so every rank returns the same 10-tuple as the serial path, bit for bit.  The frame cache
+                    # (config.tdc_video_cache_bytes) is not used here: tdc_video_cache() is None under tdc_shard_frames
                     fp = sharded.frame_plan(vid_s.shape[0], btl, cap, vindex)
                     eng.two_streams = model.tdc_side_stream(fp["hi"] - fp["lo"])
                     sel_s = torch.as_tensor(fp["siglip_frames"], dtype=torch.long, device=vid_s.device)
@@ -618,15 +645,19 @@ class CambrianMetaForCausalLM(ABC):
                     splice = None
                 else:
                     eng.two_streams = model.tdc_side_stream(min(vid_s.shape[0], cap))
+                    cached = {} if vcache is None else {"cache": vcache}          # config.tdc_video_cache_bytes
                     vis = eng.encode_video(vid_s.to(eng.dev), vid_d.to(eng.dev), tuple(image_sizes[i]),
                                            budget_text_len=btl, n_text_tokens=n_text, prompt_ids=prompt_ids, audio=audio,
-                                           frame_cap=cap, info=keep, splice=splice, video_index=vindex)
+                                           frame_cap=cap, info=keep, splice=splice, video_index=vindex, **cached)
                 spliced.append(splice is not None)
             else:
                 # single images: every image is a static frame, no segmentation / Q-Former (cambrian_arch.py:980-983)
-                sig = eng.tower("siglip", vid_s.to(eng.dev))
-                dino = eng.tower("dino", vid_d.to(eng.dev))
-                X, sizes = eng.connector(sig, dino, 1, [tuple(image_sizes[i])])
+                if vcache is not None:
+                    X, sizes = encode_image_cached(eng, vcache, vid_s.to(eng.dev), vid_d.to(eng.dev), tuple(image_sizes[i]))
+                else:
+                    sig = eng.tower("siglip", vid_s.to(eng.dev))
+                    dino = eng.tower("dino", vid_d.to(eng.dev))
+                    X, sizes = eng.connector(sig, dino, 1, [tuple(image_sizes[i])])
                 vis = X[:, :H]
                 keep["final_size"] = sizes
             if not is_video:

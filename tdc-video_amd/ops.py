@@ -379,6 +379,45 @@ def frame_cossim(f, T, n):
     return sims
 
 
+def pair_cossim(slab, pairs, n):
+    """slab: 16-bit [slots, ...] per-frame features, n elements per frame; pairs: host list of (slot_a, slot_b) -> fp32 [len(pairs)]
+    cos-sim values, bit for bit what frame_cossim gives for the same two frames adjacent in one buffer."""
+    assert slab.is_cuda and slab.is_contiguous() and slab.dim() >= 2 and n % 8 == 0
+    stride = slab[0].numel()
+    assert stride >= n and stride % 8 == 0 and 0 < len(pairs) <= 65535
+    flat = [int(v) for ab in pairs for v in ab]
+    assert min(flat) >= 0 and max(flat) < slab.shape[0], "pair slot out of range"        # the kernel trusts its slots
+    lib = L.load()
+    p = torch.tensor(flat, dtype=torch.int32).to(slab.device, non_blocking=True)
+    scratch = torch.empty(lib.tdc_pair_cossim_scratch_floats(len(pairs)), device=slab.device, dtype=torch.float32)
+    sims = torch.empty(len(pairs), device=slab.device, dtype=torch.float32)
+    L.check(lib.tdc_pair_cossim(_ptr(slab), stride, n, _ptr(p), len(pairs), _ptr(sims), _ptr(scratch), _dt(slab), _stream()),
+            "tdc_pair_cossim")
+    return sims
+
+
+def fingerprint_rows(x, rows, row_bytes=None, row_stride=None):
+    """128-bit content fingerprints of rows of x (any dtype, contiguous): row r = row_bytes bytes (default: one x[i]) at byte
+    offset rows[r] * row_stride (default: x[0]'s size) -> device int64 [len(rows), 2] (the two u64 halves, bit-cast).
+    rows: host list of ints, range-checked here (the kernel trusts its indices).  Same bits as cache.fingerprint_rows_host."""
+    assert x.is_cuda and x.is_contiguous() and x.dim() >= 1
+    total = x.numel() * x.element_size()
+    row_stride = x[0].numel() * x.element_size() if row_stride is None else int(row_stride)
+    row_bytes = row_stride if row_bytes is None else int(row_bytes)
+    rows = [int(r) for r in rows]
+    assert rows and row_bytes > 0 and row_stride >= 0
+    assert min(rows) >= 0 and max(rows) * row_stride + row_bytes <= total, "fingerprint row out of range"
+    lib = L.load()
+    out = torch.empty(len(rows), 2, device=x.device, dtype=torch.int64)
+    for s in range(0, len(rows), 65535):                  # grid.y bound of one launch
+        part = rows[s:s + 65535]
+        r = torch.tensor(part, dtype=torch.int32).to(x.device, non_blocking=True)
+        scratch = torch.empty(lib.tdc_fingerprint_rows_scratch_bytes(len(part)), device=x.device, dtype=torch.uint8)
+        L.check(lib.tdc_fingerprint_rows(_ptr(x), row_stride, _ptr(r), len(part), row_bytes, _ptr(out[s:]), _ptr(scratch),
+                                         _stream()), "tdc_fingerprint_rows")
+    return out
+
+
 def token_mean(x, B, P):
     _chk2d(x, "x")
     assert x.shape[0] >= B * P and x.is_contiguous()

@@ -390,6 +390,25 @@ class VideoEncoder:
             t.record_stream(torch.cuda.current_stream(self.dev))
             return t.cpu().tolist()
 
+    def slot_sims(self, slab, pairs, defer=False):
+        """a5 on cached rows: slab [slots, P, Dp] DINOv2 rows, pairs [(slot_a, slot_b)] -> host list of their cos-sims (the
+        values sims_tensor gives for the two frames adjacent; read like the similarities: mark() / fetch()).  defer: return a
+        function that reads them, so the host can enqueue more work before it waits."""
+        sims = ops.pair_cossim(slab, pairs, slab[0].numel())
+        ev = self.mark()
+        return (lambda: self.fetch(sims, ev)) if defer else self.fetch(sims, ev)
+
+    def fingerprint(self, px, rows, row_bytes=None, row_stride=None):
+        """frame cache keys: the 128-bit content fingerprints of the frames px[rows] (read in place; row_bytes / row_stride:
+        other rows of px's bytes, ops.fingerprint_rows) -> host list of (u64, u64)"""
+        fp = ops.fingerprint_rows(px.contiguous(), rows, row_bytes, row_stride)
+        return [(a & 0xFFFFFFFFFFFFFFFF, b & 0xFFFFFFFFFFFFFFFF) for a, b in self.fetch(fp, self.mark())]
+
+    def new_cache(self, max_bytes):
+        """a FrameCache of max_bytes for encode_video(cache=...) of this engine (cache.py)"""
+        from .cache import FrameCache, engine_signature
+        return FrameCache(max_bytes, engine_signature(self))
+
     def frame_sims(self, dino_feat, T):
         """same as a python list (one D2H copy: the segmentation is host logic)."""
         return self.sims_tensor(dino_feat, T).tolist()
@@ -881,13 +900,19 @@ class VideoEncoder:
 
     # ------------------------------------------------------------------------------------------------ top level
     def encode_video(self, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio=None,
-                     frame_cap=224, keep=None, splice=None, video_index=None, info=None):
+                     frame_cap=224, keep=None, splice=None, video_index=None, info=None, cache=None):
         """One video: pixels -> emitted visual tokens [n, H] (S0-S10).  `budget_text_len` is the text length used by
         get_max_num_frames (cambrian_arch.py:753-759), `n_text_tokens` the non-image token count (:1499-1505).
         frame_cap: the reference's "in case of OOM" constant 224 of BOTH caps (cambrian_arch.py:907-916 before the towers,
         :813-822 inside adapt_segment) as a parameter.
         keep: dict that receives every stage tensor (and makes the connector run its per-kernel form, which produces them);
-        info: dict that receives the host-side facts only (frame_indices, selected, seg_indices, final_size, n_visual) - free."""
+        info: dict that receives the host-side facts only (frame_indices, selected, seg_indices, final_size, n_visual) - free.
+        cache: a FrameCache (new_cache): frames whose content it holds skip the towers and the connector, new ones are stored -
+        the result is bit for bit that of cache=None (encode_video_cached).  keep= bypasses the cache (its per-kernel
+        connector form is what produces the stage tensors)."""
+        if cache is not None and keep is None:
+            return encode_video_cached(self, cache, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens,
+                                       prompt_ids, audio, frame_cap, splice, video_index, info)
         return encode_video_with(self, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids,
                                  audio, frame_cap, keep, splice, video_index, info)
 
@@ -1043,4 +1068,150 @@ def encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text
                     final_size=final_size, X=X)
     if info is not None:
         info.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, final_size=final_size)
+    return vis
+
+
+def encode_missing(e, cache, keys, px_siglip, px_dino, idx, image_size, after_dino=None):
+    """the frames idx[j] whose keys[j] the cache lacks (one per distinct key) through the towers and the connector, stored
+    -> those keys, or None when this call's frames do not fit the budget (nothing stored).  after_dino(new keys, their DINOv2
+    rows) is called between the two towers (encode_video_cached enqueues the a5 similarities there)."""
+    new = cache.lookup(keys)
+    if new:
+        first = {}
+        for j, k in enumerate(keys):
+            first.setdefault(k, j)
+        rows = [idx[first[k]] for k in new]
+        if rows == list(range(px_siglip.shape[0])):          # every input frame, in order: no gather copy
+            ps, pd = px_siglip, px_dino
+        else:
+            sel = torch.tensor(rows, device=px_siglip.device)
+            ps, pd = px_siglip[sel], px_dino[sel]
+        dino = e.tower("dino", pd)
+        if after_dino is not None:
+            after_dino(new, dino)
+        sig = e.tower("siglip", ps)
+        Xn, fsz = e.connector(sig, dino, len(new), [tuple(image_size)] * len(new))
+        if not cache.store(new, Xn, dino, fsz, set(keys)):
+            return None
+    return new
+
+
+def encode_image_cached(e, cache, px_siglip, px_dino, image_size):
+    """a single image ([1, 3, H, W] each) through the frame cache: (connector rows [N, Hp], [final size]) - what
+    e.connector(e.tower(...), e.tower(...), 1, [image_size]) returns, bit for bit"""
+    cache.bind(e)
+    keys, _ = cache.frame_keys(e, px_siglip, px_dino, [0], image_size)
+    if encode_missing(e, cache, keys, px_siglip, px_dino, [0], image_size) is None:
+        return e.connector(e.tower("siglip", px_siglip), e.tower("dino", px_dino), 1, [tuple(image_size)])
+    return cache.assemble(e, keys), cache.final_sizes(keys)
+
+
+def cached_audio(e, cache, audio, sample_indices, T):
+    """a20 of encode_video_cached: local_audio(audio, sample_indices, T), with the BEATs windows of a raw waveform taken from
+    the cache where it holds their waveform and mask slices (keys: fingerprints of the slices; window features are item-wise)"""
+    if not (isinstance(audio, dict) and audio.get("audio_tokens") is None and audio.get("beats_windows") is None
+            and audio.get("audio_wav") is not None and getattr(e, "beats", None) is not None):
+        return e.local_audio(audio, sample_indices, T, 0, T)
+    from .beats import SAMPLE_RATE
+    wav, mask = audio["audio_wav"], audio.get("audio_wav_mask")
+    n_s = wav.shape[1]
+    starts = e.beats.window_starts(n_s)
+    sizes = e.beats.window_token_counts(n_s)
+    plan = seg.audio_plan(sizes, [int(v) for v in sample_indices])
+    need = sorted({w for i in range(min(T, len(plan))) for (w, _, _) in plan[i][0]})
+    if not need:
+        return e.local_audio(audio, sample_indices, T, 0, T)
+    m = None if mask is None else torch.as_tensor(mask).bool().cpu()
+    if m is not None and not bool(m.any()):
+        m = None                                                  # what window_features does with an all-False mask
+    n, eb = SAMPLE_RATE * 10, wav.element_size()
+    wd = wav if wav.is_cuda else wav.to(e.dev)                    # fingerprinted on the device (a host waveform is copied)
+    keys = {}
+    for w in need:
+        a, b = SAMPLE_RATE * starts[w], min(n_s, SAMPLE_RATE * (starts[w] + 10))
+        mk = None if m is None else tuple(int(v) for v in fingerprint_mask(m[0, a:b]))
+        keys[w] = ("beats", str(wav.dtype), b - a, mk)
+    full = [w for w in need if keys[w][2] == n]
+    fps = {}
+    if full:
+        fps.update(zip(full, e.fingerprint(wd, full, n * eb, n * eb)))
+    for w in need:
+        if w not in fps:
+            fps[w] = e.fingerprint(wd, [1], keys[w][2] * eb, SAMPLE_RATE * starts[w] * eb)[0]
+    keys = {w: keys[w] + (tuple(fps[w]),) for w in need}
+    feats = cache.windows(keys, lambda todo: e.beats_windows(wav, mask, only=todo))
+    return e.audio_tokens(feats, sample_indices, T, 0, T, window_sizes=sizes)
+
+
+def fingerprint_mask(m):
+    """host fingerprint of a boolean mask slice (the mask lives on the host: window_features reads it there)"""
+    from .cache import fingerprint_rows_host
+    return fingerprint_rows_host(m.to(torch.uint8).numpy()[None])[0]
+
+
+def encode_video_cached(e, cache, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio=None,
+                        frame_cap=224, splice=None, video_index=None, info=None):
+    """encode_video_with through a FrameCache (cache.py), bit for bit the same result: a1 as there; the a1-selected frames are
+    fingerprinted where they lie; only the frames the cache lacks run through the towers and the connector (frames are
+    independent through a3-a10) and are stored; the a5 similarities come from the cache or from the cached DINOv2 rows
+    (tdc_pair_cossim), the refinement's precise values from the cache or from the pixels passed; the connector rows of the kept
+    frames are gathered out of the slab; a20 and the prompt-dependent a11-a19 run as in encode_video_with.  A call whose
+    distinct frames exceed the budget runs encode_video_with and stores nothing.  info["cache"]: what this call reused and
+    encoded.  The tower batches see the HBM the cache holds as taken (auto_tower_batch): the rate may change, not the bits."""
+    cfg = e.cfg
+    cache.bind(e)
+    T0 = px_siglip.shape[0]
+    idx = frame_indices(cfg, T0, budget_text_len, frame_cap)                                        # a1
+    T = len(idx)
+    keys, dkeys = cache.frame_keys(e, px_siglip, px_dino, idx, image_size)
+    before = cache.stats()
+    segmented = T > cfg.get("max_num_segments", 24) + 1
+    early = {}
+
+    def after_dino(new, dino):
+        # a5 of the pairs whose frames are both new, from the fresh DINOv2 rows, enqueued BEFORE the SigLIP tower: the host
+        # reads them while the tower runs (as encode_video_with does); pairs with a cached frame come from the slab later
+        pos = {k: j for j, k in enumerate(new)}
+        todo = [i for i in range(T - 1) if keys[i] in pos and keys[i + 1] in pos and
+                cache.pair_get((dkeys[i], dkeys[i + 1])) is None]
+        if segmented and todo:
+            slab = dino.view(len(new), dino.shape[0] // len(new), dino.shape[1])
+            early["pairs"] = todo
+            early["read"] = e.slot_sims(slab, [(pos[keys[i]], pos[keys[i + 1]]) for i in todo], defer=True)
+
+    # a3/a4, a6-a10 for the frames the cache lacks; a call whose frames exceed the budget (known once the first frames fixed
+    # the row geometry) runs uncached
+    new = encode_missing(e, cache, keys, px_siglip, px_dino, idx, image_size, after_dino) if cache.fits(keys) else None
+    if new is None:
+        if info is not None:
+            info["cache"] = dict(bypassed=True, frames=T, frames_hit=0, frames_encoded=T, pairs_computed=0)
+        return encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio,
+                                 frame_cap, None, splice, video_index, info)
+    if not segmented:                                                                               # a5
+        seg_idx = list(range(T))
+    else:
+        sims = cache.adjacent_sims(e, keys, dkeys, early)
+
+        def precise(pairs):
+            frames = seg.band_frames(pairs)
+            feats = precise_features(e, px_dino, [idx[f] for f in frames])
+            return e.pair_sims(feats, [(idx[i], idx[i + 1]) for i in pairs]).tolist()
+        seg_idx = select_segments_with(e, sims, lambda band: cache.precise_sims(band, dkeys, precise), info)
+    X = cache.assemble(e, keys)
+    N = cache.rows_per_frame
+    final_size = cache.final_sizes(keys)
+    max_visual_len = visual_budget(cfg, n_text_tokens)
+    pid = text_prompt(cfg, prompt_ids)
+    if audio is not None:                                                                           # a20
+        audio = cached_audio(e, cache, audio, sample_indicator(T0, idx, video_index), T)
+    vis = compress_with(e, X, T, N, seg_idx, pid, max_visual_len, audio, None, splice, info)        # a11-a19 (+a21)
+    if info is not None:
+        after = cache.stats()
+        info.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, final_size=final_size)
+        fresh = set(new)
+        info["cache"] = dict(bypassed=False, frames=T, frames_hit=sum(1 for k in keys if k not in fresh),
+                             frames_encoded=after["frames_encoded"] - before["frames_encoded"],
+                             pairs_computed=after["pairs_computed"] - before["pairs_computed"],
+                             evictions=after["evictions"] - before["evictions"], bytes=after["bytes"],
+                             windows_encoded=after["windows_encoded"] - before["windows_encoded"])
     return vis
