@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import lib as L
 from . import segment as seg
-from .pipeline import VideoEncoder, encode_image_cached
+from .pipeline import VideoEncoder, batch_groups, encode_image_cached, frame_indices
 
 IGNORE_INDEX = -100        # tdc/constants.py
 IMAGE_TOKEN_INDEX = -200
@@ -370,7 +370,7 @@ class CambrianMetaModel:
         tdc/cambrian_arch.py:698-745);
         `config.tdc_frame_cap` (default 224 = the reference's "in case of OOM" constant, tdc/cambrian_arch.py:907-916,813-822):
         the cap of both frame sub-samplings; `config.tdc_shard_frames`: see prepare_inputs_labels_for_multimodal;
-        `config.tdc_video_cache_bytes`: see tdc_video_cache.
+        `config.tdc_video_cache_bytes`: see tdc_video_cache; `config.tdc_batch_frames`: see tdc_batch_frames.
         bench.py's line is reproduced by dtype=float16, tdc_tower_dtype="bfloat16", tdc_tower_res_dtype="float16",
         tdc_frame_cap=T (its `product_setting` field says so; `bench.py --via-mixin` runs exactly that)."""
         if self._tdc_encoder is None or refresh:
@@ -445,6 +445,22 @@ class CambrianMetaModel:
         c = getattr(self, "_tdc_video_cache", None)
         if c is not None:
             c.clear()
+
+    def tdc_batch_frames(self):
+        """`config.tdc_batch_frames`: the frame ceiling of a batched encode - the samples of one call are grouped greedily in
+        batch order, up to that many a1-selected frames per group (images: 1), and each group of two or more runs through
+        one tower and connector pass (VideoEncoder.encode_batch), bit for bit the per-sample results.  0 / absent: off, every
+        sample is encoded on its own (the default: a group holds its samples' pixels, tower features and connector rows on
+        the device at once).  Ignored (0) under `config.tdc_shard_frames` and with `config.tdc_video_cache_bytes` on."""
+        n = getattr(self.config, "tdc_batch_frames", None)
+        if n is None:
+            return 0
+        if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+            raise ValueError("config.tdc_batch_frames must be a frame ceiling (a non-negative int; 0 / absent = off), got %r"
+                             % (n,))
+        if getattr(self.config, "tdc_shard_frames", False) or getattr(self.config, "tdc_video_cache_bytes", None):
+            return 0
+        return n
 
     def tdc_side_stream(self, frames_per_rank):
         """engine.two_streams (pipeline.start_side_tower): the config's choice, by default on at <= 128 frames per rank"""
@@ -564,6 +580,7 @@ class CambrianMetaForCausalLM(ABC):
             return (input_ids, position_ids, attention_mask, past_key_values, None, labels, None, None, None, None)
         eng = model.tdc_engine()
         vcache = model.tdc_video_cache()             # config.tdc_video_cache_bytes (validated even when no video comes)
+        batch_frames = model.tdc_batch_frames()      # config.tdc_batch_frames (0: every sample on its own)
         cfgd = self._cfg()
         K = cfgd.get("context_token_num", 16)
         H = model.config.hidden_size
@@ -577,7 +594,9 @@ class CambrianMetaForCausalLM(ABC):
         visual = []          # per sample: [n_tokens, H] tensor on the engine device
         spliced = []         # per sample: `visual[i]` already holds the text rows around the visual tokens
         final_size = []
-        for i in range(bsz):
+
+        def facts(i):
+            """the host-side facts of sample i: pixels, text lengths, prompt ids, audio, a21 hand-off, frame cap"""
             if is_video:
                 vid_s, vid_d = images[0][i], images[1][i]
                 if vid_s.ndim == 3:
@@ -610,23 +629,31 @@ class CambrianMetaForCausalLM(ABC):
                         and audio.get("audio_tokens") is None:
                     # the reference's own audio dict (cambrian_arch.py:1547): raw waveform -> BEATs on the device
                     eng.beats = model.tdc_beats()
-            keep = {}
+            f = dict(i=i, vid_s=vid_s, vid_d=vid_d, n_text=n_text, prompt_ids=prompt_ids, audio=audio, splice=None)
             if is_video:
                 # a21 hand-off: when embed_tokens lives on the engine device in the engine dtype the
                 # emission gather also fetches the text embeddings and writes the inputs_embeds rows directly
-                splice = None
                 emb_w = getattr(getattr(model, "embed_tokens", None), "weight", None)
                 pos_img = torch.where(cur_ids == IMAGE_TOKEN_INDEX)[0].tolist()
                 if (getattr(self, "tdc_prefill_handoff", True) and emb_w is not None and emb_w.is_cuda
                         and emb_w.device == eng.dev and emb_w.dtype == eng.dtype and len(pos_img) == 1):
-                    splice = {"table": emb_w, "before": cur_ids[:pos_img[0]].tolist(),
-                              "after": cur_ids[pos_img[0] + 1:].tolist()}
+                    f["splice"] = {"table": emb_w, "before": cur_ids[:pos_img[0]].tolist(),
+                                   "after": cur_ids[pos_img[0] + 1:].tolist()}
                 # video_indices[i]: 0/1 per second of audio, 1 where a frame was decoded (cambrian_arch.py:916-926); [None]
                 # (what generate() passes) / None: input frame t is second t
-                vindex = video_indices[i] if video_indices is not None and i < len(video_indices) else None
-                cap = model.tdc_frame_cap()
-                btl = self._budget_text_len(ids_host[i])
-                sharded = model.tdc_sharded_engine()
+                f["vindex"] = video_indices[i] if video_indices is not None and i < len(video_indices) else None
+                f["cap"] = model.tdc_frame_cap()
+                f["btl"] = self._budget_text_len(ids_host[i])
+                f["sharded"] = model.tdc_sharded_engine()
+            return f
+
+        def encode_one(f):
+            """sample f through the engine on its own -> (visual tokens, spliced, final sizes)"""
+            i, vid_s, vid_d, n_text, prompt_ids, audio, splice = (f[k] for k in ("i", "vid_s", "vid_d", "n_text", "prompt_ids",
+                                                                                  "audio", "splice"))
+            keep = {}
+            if is_video:
+                vindex, cap, btl, sharded = f["vindex"], f["cap"], f["btl"], f["sharded"]
                 if sharded is not None:
                     # config.tdc_shard_frames under an initialised torch.distributed (one process per GPU, every rank called
                     # with the same video - how the reference's eval drivers start their workers, eval/eval_mlvu.py:129-157 -
@@ -649,7 +676,6 @@ class CambrianMetaForCausalLM(ABC):
                     vis = eng.encode_video(vid_s.to(eng.dev), vid_d.to(eng.dev), tuple(image_sizes[i]),
                                            budget_text_len=btl, n_text_tokens=n_text, prompt_ids=prompt_ids, audio=audio,
                                            frame_cap=cap, info=keep, splice=splice, video_index=vindex, **cached)
-                spliced.append(splice is not None)
             else:
                 # single images: every image is a static frame, no segmentation / Q-Former (cambrian_arch.py:980-983)
                 if vcache is not None:
@@ -660,10 +686,35 @@ class CambrianMetaForCausalLM(ABC):
                     X, sizes = eng.connector(sig, dino, 1, [tuple(image_sizes[i])])
                 vis = X[:, :H]
                 keep["final_size"] = sizes
-            if not is_video:
-                spliced.append(False)
+            return vis, splice is not None, keep["final_size"]
+
+        def encode_group(fs, n_frames):
+            """config.tdc_batch_frames: the samples fs in one tower and connector pass (VideoEncoder.encode_batch) -> what
+            encode_one returns for each, bit for bit"""
+            infos = [{} for _ in fs]
+            samples = [dict(px_siglip=f["vid_s"], px_dino=f["vid_d"], image_size=tuple(image_sizes[f["i"]]),
+                            image=not is_video, budget_text_len=f.get("btl"), n_text_tokens=f["n_text"], prompt_ids=f["prompt_ids"],
+                            audio=f["audio"], video_index=f.get("vindex"), splice=f["splice"]) for f in fs]
+            eng.two_streams = model.tdc_side_stream(n_frames)
+            vis = eng.encode_batch(samples, frame_cap=model.tdc_frame_cap(), infos=infos)
+            return [(v, f["splice"] is not None, info["final_size"]) for v, f, info in zip(vis, fs, infos)]
+
+        if not batch_frames or bsz == 1:
+            results = (encode_one(facts(i)) for i in range(bsz))
+        else:
+            # config.tdc_batch_frames: every sample's host-side facts first (the same exceptions as the loop above, raised
+            # before any encode), then the groups of batch_groups in sample order; a group of one runs encode_one
+            fs = [facts(i) for i in range(bsz)]
+            fr = [len(frame_indices(eng.cfg, f["vid_s"].shape[0], f["btl"], f["cap"])) if is_video else 1 for f in fs]
+            geo = [(tuple(f["vid_s"].shape[1:]), f["vid_s"].dtype, f["vid_s"].device, tuple(f["vid_d"].shape[1:]),
+                    f["vid_d"].dtype, f["vid_d"].device) for f in fs]
+            results = []
+            for g in batch_groups(fr, batch_frames, geo):
+                results += [encode_one(fs[g[0]])] if len(g) == 1 else encode_group([fs[i] for i in g], sum(fr[i] for i in g))
+        for vis, sp, fsz in results:
             visual.append(vis)
-            final_size.extend(keep["final_size"])
+            spliced.append(sp)
+            final_size.extend(fsz)
         # ---- a21: splice text embeddings and visual tokens, truncate, pad (cambrian_arch.py:1425-1495, :1712-1844)
         _labels, _position_ids, _attention_mask = labels, position_ids, attention_mask
         if attention_mask is None:

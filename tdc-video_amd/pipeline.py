@@ -916,6 +916,13 @@ class VideoEncoder:
         return encode_video_with(self, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids,
                                  audio, frame_cap, keep, splice, video_index, info)
 
+    def encode_batch(self, samples, frame_cap=224, infos=None):
+        """Several videos / single images in one tower and connector pass: samples = dicts of encode_video's arguments
+        (px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio, video_index, splice) plus
+        `image`; -> one result per sample, bit for bit what encode_video (an image: the mixin's image branch) returns for it.
+        infos: one info dict per sample (encode_batch_with).  All samples share the pixel geometry and type."""
+        return encode_batch_with(self, samples, frame_cap, infos)
+
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Orchestration over an "engine" (VideoEncoder on GPUs; the gloo tests of dist.py plug in a CPU test double that
@@ -1069,6 +1076,115 @@ def encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text
     if info is not None:
         info.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, final_size=final_size)
     return vis
+
+
+def batch_groups(frames, ceiling, keys=None):
+    """`config.tdc_batch_frames`: the samples of one call grouped greedily in batch order, the a1-selected frames of a group
+    (frames[i]; images count 1) summing to at most `ceiling`; a sample above the ceiling forms its own group, and so does a
+    change of keys[i] (the pixel geometry: frames of one group share one tower input).  -> lists of sample indices"""
+    groups, cur, n = [], [], 0
+    for i, f in enumerate(frames):
+        if cur and (n + f > ceiling or (keys is not None and keys[i] != keys[cur[-1]])):
+            groups.append(cur)
+            cur, n = [], 0
+        cur.append(i)
+        n += f
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def gather_frames(pxs, plans, device):
+    """the frames plans[j] of every pixel tensor pxs[j], in order, as one [sum, 3, H, W] tensor on `device`.  Each kept frame is
+    copied once: from a host tensor that copy is the upload itself, on the device it is the a1 index copy (whole tensors when
+    every frame is kept)."""
+    px0 = pxs[0]
+    out = torch.empty((sum(len(p) for p in plans),) + tuple(px0.shape[1:]), dtype=px0.dtype, device=device)
+    o = 0
+    for px, idx in zip(pxs, plans):
+        if tuple(px.shape[1:]) != tuple(px0.shape[1:]) or px.dtype != px0.dtype:
+            raise ValueError("a batch shares one tower input: pixels %s %s and %s %s differ"
+                             % (tuple(px0.shape[1:]), px0.dtype, tuple(px.shape[1:]), px.dtype))
+        dst = out[o:o + len(idx)]
+        if len(idx) == px.shape[0]:
+            dst.copy_(px)
+        elif px.device == out.device:
+            torch.index_select(px, 0, torch.tensor(idx, device=px.device), out=dst)
+        else:
+            dst.copy_(px[torch.tensor(idx)])
+        o += len(idx)
+    return out
+
+
+def encode_batch_with(e, samples, frame_cap, infos=None):
+    """Several samples in one tower and connector pass (`config.tdc_batch_frames`), each result bit for bit that of its own
+    encode_video_with call (an image: its connector rows [:, :H], as prepare_inputs_labels_for_multimodal's image branch).
+    samples: dicts of encode_video's arguments - px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids,
+    audio, video_index, splice - and `image` (True: one static frame, no a1 / a5 / Q-Former).  infos: one dict per sample
+    (or None) that receives what encode_video's info= does (images: final_size).  -> list of per-sample results.
+    a1 runs per sample; the kept frames of all samples go through one DINOv2 and one SigLIP pass; a5 takes the in-sample
+    adjacent pairs of one similarity launch over the group (the cross-sample pairs are dropped) read to the host once, and
+    selects (and refines, on the sample's own pixels) per sample; one connector call takes every frame's image_size and its
+    rows are split by the returned sizes; a20, a11-a19 and the a21 hand-off run per sample.  This rests on tower batch
+    invariance, the per-pair cos-sim reduction and the per-frame connector."""
+    cfg = e.cfg
+    mns = cfg.get("max_num_segments", 24)
+    plans = [[0] if s.get("image") else frame_indices(cfg, s["px_siglip"].shape[0], s["budget_text_len"], frame_cap)
+             for s in samples]                                                                      # a1
+    offs = [0]
+    for idx in plans:
+        offs.append(offs[-1] + len(idx))
+    Tg = offs[-1]
+    dev = getattr(e, "dev", samples[0]["px_siglip"].device)
+    px_s = gather_frames([s["px_siglip"] for s in samples], plans, dev)
+    px_d = gather_frames([s["px_dino"] for s in samples], plans, dev)
+    segmented = [not s.get("image") and len(idx) > mns + 1 for s, idx in zip(samples, plans)]
+    side_sig = start_side_tower(e, px_s)
+    dino = e.tower("dino", px_d)                                                                    # a4
+    sig = None
+    sims = None
+    if any(segmented):                                                                              # a5
+        sims_dev = e.sims_tensor(dino, Tg)
+        ev = e.mark() if hasattr(e, "mark") and sims_dev.is_cuda else None
+        if side_sig is None:
+            sig = e.tower("siglip", px_s)           # enqueued before the one host read, as in encode_video_with
+        sims = e.fetch(sims_dev, ev) if ev is not None else sims_dev.tolist()
+    seg_idx = []
+    for j, idx in enumerate(plans):
+        T, o = len(idx), offs[j]
+        if not segmented[j]:
+            seg_idx.append(list(range(T)))
+            continue
+
+        def refine(band, o=o):
+            return e.pair_sims(precise_features(e, px_d, seg.band_frames(band), -o), [(i, i + 1) for i in band]).tolist()
+        seg_idx.append(select_segments_with(e, sims[o:o + T - 1], refine, infos[j] if infos is not None else None))
+    if sig is None:
+        sig = join_side_tower(e, side_sig, px_s)                                                    # a3
+    sizes = [tuple(s["image_size"]) for s, idx in zip(samples, plans) for _ in idx]
+    X, final_size = e.connector(sig, dino, Tg, sizes)                                               # a6-a10
+    out, r = [], 0
+    for j, (s, idx) in enumerate(zip(samples, plans)):
+        T, o = len(idx), offs[j]
+        fs = final_size[o:o + T]
+        n = sum(h * (w + 1) for h, w in fs)          # unpad_newline: h rows of w tokens + a newline each
+        Xs = X[r:r + n]
+        r += n
+        info = infos[j] if infos is not None else None
+        if s.get("image"):
+            out.append(Xs[:, :e.H])
+            if info is not None:
+                info["final_size"] = fs
+            continue
+        audio = s.get("audio")
+        if audio is not None:                                                                       # a20
+            audio = e.local_audio(audio, sample_indicator(s["px_siglip"].shape[0], idx, s.get("video_index")), T, 0, T)
+        out.append(compress_with(e, Xs, T, n // T, seg_idx[j], text_prompt(cfg, s["prompt_ids"]),   # a11-a19 (+a21)
+                                 visual_budget(cfg, s["n_text_tokens"]), audio, None, s.get("splice"), info))
+        if info is not None:
+            info.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx[j], final_size=fs)
+    assert r == X.shape[0], "connector rows %d, split %d" % (X.shape[0], r)
+    return out
 
 
 def encode_missing(e, cache, keys, px_siglip, px_dino, idx, image_size, after_dino=None):
