@@ -230,6 +230,10 @@ class FrameCache:
     def rows_per_frame(self):
         return self._geom[0]
 
+    def dino_rows(self, key):
+        """the DINOv2 rows [P, Dp] of a stored frame: a view of its slab slot (contiguous)"""
+        return self._D[self._slots[key]]
+
     def assemble(self, e, keys):
         """the connector rows of the frames `keys`, in order -> [len(keys) * N, Hp] (one row gather out of the slab)"""
         N, Hp = self._geom[0], self._geom[1]
@@ -254,6 +258,11 @@ class FrameCache:
         self._pairs.move_to_end(key)
         while len(self._pairs) > self._pair_cap():
             self._pairs.popitem(last=False)
+
+    def put_computed(self, key, value):
+        """pair_put of a similarity this call computed (counted in pairs_computed)"""
+        self.pair_put(key, value)
+        self._counts["pairs_computed"] += 1
 
     def adjacent_sims(self, e, keys, dkeys, early=None):
         """a5: the T - 1 adjacent-frame similarities of the frames `keys` - stored values, those already enqueued (early:

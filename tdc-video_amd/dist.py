@@ -26,8 +26,9 @@ import numpy as np
 import torch
 
 from . import segment as seg
-from .pipeline import (emission_plan, frame_indices, join_side_tower, precise_features, sample_indicator,
-                       select_segments_with, start_side_tower, text_prompt, visual_budget)
+from .cache import fingerprint_rows_host
+from .pipeline import (cached_audio, emission_plan, encode_missing, frame_indices, join_side_tower, precise_features,
+                       sample_indicator, select_segments_with, start_side_tower, text_prompt, visual_budget)
 
 
 def owner_of(frame, ranges):
@@ -118,6 +119,10 @@ class ShardedVideoEncoder:
         self.comm = comm if comm is not None else TorchComm(rank, world, group)
         self._bufs = {}        # (tag, rows, cols, dtype) -> preallocated send / receive buffers of the token all-gather
         self._maps = {}        # shard lengths -> device index map of the compaction gather
+
+    def new_cache(self, nbytes):
+        """a FrameCache of nbytes for encode_video(cache=...) - this rank's own frames (engine.new_cache)"""
+        return self.e.new_cache(nbytes)
 
     # ---- a1 on every rank --------------------------------------------------------------------------------------------
     def frame_plan(self, T0, budget_text_len, frame_cap=224, video_index=None, halo=False):
@@ -226,12 +231,17 @@ class ShardedVideoEncoder:
         return self._all_gather_var(local.to(torch.float32), counts).tolist()
 
     def encode_video(self, px_siglip_local, px_dino_local_halo, T, image_size, n_text_tokens, prompt_ids, audio=None,
-                     sample_indices=None, recompute_halo=False):
+                     sample_indices=None, recompute_halo=False, cache=None, info=None):
         """px_siglip_local: frames [lo,hi) of the T frames that survive a1 (frame_plan); px_dino_local_halo: the same frames for
         the DINOv2 tower (the boundary frame's features are then exchanged), or frames [lo, hi + 1) - the next rank's first
         frame appended (none on the last rank) - with recompute_halo=True (on EVERY rank), to re-encode that frame here instead.  audio: as in the serial path - a full [T, 50, 768] token tensor, or a dict
         with "audio_tokens" / "beats_windows" (all windows) / "audio_wav" (raw 16 kHz waveform: BEATs runs here, on this
-        rank's windows only); sample_indices: frame_plan's per-second vector (all ones when a1 did not cap)."""
+        rank's windows only); sample_indices: frame_plan's per-second vector (all ones when a1 did not cap).
+        cache: a FrameCache (new_cache) of this rank's own frames - the result is bit for bit that of cache=None
+        (_encode_cached); info then receives info["cache"].  cache=None: no collective besides those listed above."""
+        if cache is not None:
+            return self._encode_cached(cache, px_siglip_local, px_dino_local_halo, T, image_size, n_text_tokens, prompt_ids,
+                                       audio, sample_indices, recompute_halo, info)
         e, rank, world = self.e, self.rank, self.world
         ranges = seg.shard_ranges(T, world)
         lo, hi = ranges[rank]
@@ -241,15 +251,7 @@ class ShardedVideoEncoder:
         n_d = px_dino_local_halo.shape[0]
         assert n_d == Tl + (1 if (recompute_halo and lo < hi < T) else 0) and px_siglip_local.shape[0] == Tl
         if Tl == 0:
-            # more ranks than frames (T < world <= 8 < max_num_segments + 1: the pass-through case, no similarities, no
-            # Q-Former): this rank only takes part in the final all-gather
-            assert T <= cfg.get("max_num_segments", 24) + 1
-            Nf = self._tokens_per_frame(image_size, audio)
-            plan, learned = emission_plan(e, T, Nf, list(range(T)), visual_budget(cfg, n_text_tokens))
-            pairs, _ = split_plan(plan, ranges, Nf, e.K)
-            if not learned:
-                self.comm.exchange([], [])
-            return self._gather_tokens(lambda out: None, [len(p) for p in pairs], e.H, e.dtype, px_siglip_local.device)
+            return self._pass_through(T, image_size, n_text_tokens, audio, ranges, px_siglip_local.device)
         side_sig = start_side_tower(e, px_siglip_local)
         dino_all = e.tower("dino", px_dino_local_halo)
         P = dino_all.shape[0] // n_d
@@ -294,10 +296,29 @@ class ShardedVideoEncoder:
             sig = join_side_tower(e, side_sig, px_siglip_local)
         X, sizes = e.connector(sig, dino, Tl, [tuple(image_size)] * Tl)
         N = X.shape[0] // Tl
-        K = e.K
         if sample_indices is None:
             sample_indices = [1] * T
         Xf, Nf = e.with_audio(X, Tl, N, e.local_audio(audio, sample_indices, T, lo, hi))
+        return self._compress_gather(Xf, N, Nf, T, ranges, seg_idx, n_text_tokens, prompt_ids, X.device)
+
+    def _pass_through(self, T, image_size, n_text_tokens, audio, ranges, device):
+        """a rank without frames: more ranks than frames (T < world <= 8 < max_num_segments + 1: the pass-through case, no
+        similarities, no Q-Former) - this rank only takes part in the final all-gather"""
+        e, cfg = self.e, self.e.cfg
+        assert T <= cfg.get("max_num_segments", 24) + 1
+        Nf = self._tokens_per_frame(image_size, audio)
+        plan, learned = emission_plan(e, T, Nf, list(range(T)), visual_budget(cfg, n_text_tokens))
+        pairs, _ = split_plan(plan, ranges, Nf, e.K)
+        if not learned:
+            self.comm.exchange([], [])
+        return self._gather_tokens(lambda out: None, [len(p) for p in pairs], e.H, e.dtype, device)
+
+    def _compress_gather(self, Xf, N, Nf, T, ranges, seg_idx, n_text_tokens, prompt_ids, device):
+        """steps 3-4 on the local frames' rows Xf [Tl * Nf, Hp] (N visual rows per frame): the shared plan, the query hand-off,
+        the Q-Former, the local emission and the token all-gather -> the whole stream"""
+        e, rank, cfg = self.e, self.rank, self.e.cfg
+        lo, hi = ranges[rank]
+        K = e.K
         # 3. shared plan, query hand-off
         plan, learned = emission_plan(e, T, Nf, seg_idx, visual_budget(cfg, n_text_tokens))
         pairs, comp_local = split_plan(plan, ranges, Nf, K)
@@ -323,7 +344,7 @@ class ShardedVideoEncoder:
                         sends.append((q_owned[ci * K:(ci + 1) * K].contiguous(), r))
             for c in need:
                 if not (lo <= keys[c] < hi):
-                    buf = torch.empty((K, e.query_width()), dtype=e.dtype, device=X.device)
+                    buf = torch.empty((K, e.query_width()), dtype=e.dtype, device=device)
                     recv_buf[c] = buf
                     recvs.append((buf, owner_of(keys[c], ranges)))
             self.comm.exchange(sends, recvs)
@@ -346,4 +367,200 @@ class ShardedVideoEncoder:
                 e.emit_into(Xf, comp, mine, out)              # the a19 gather writes the send buffer directly
             else:
                 out[: len(mine)].copy_(e.emit(Xf, comp, mine))
-        return self._gather_tokens(emit_local, [len(p) for p in pairs], e.H, e.dtype, X.device)
+        return self._gather_tokens(emit_local, [len(p) for p in pairs], e.H, e.dtype, device)
+
+    # ---- the frame cache ----------------------------------------------------------------------
+    # Every rank caches its own frames in its own FrameCache.  Hits, misses, evictions and budget bypasses differ from rank
+    # to rank; they change what a rank computes, never which collectives and point-to-point operations it issues: a skip that
+    # would need a neighbour's cache state is agreed first through a small all-gather that every rank reads alike.
+    AGREE_FIELDS = ("T", "n_text_tokens", "image_size[0]", "image_size[1]", "prompt length", "prompt fingerprint[0]",
+                    "prompt fingerprint[1]", "audio", "seconds", "sample_indices fingerprint[0]",
+                    "sample_indices fingerprint[1]", "pixel geometry fingerprint[0]", "pixel geometry fingerprint[1]",
+                    "cache refuses the engine")
+
+    def _agree(self, T, n_text_tokens, image_size, prompt_ids, audio, sample_indices, px_s, px_d, refused):
+        """step 1 of the cached path: one all-gather of what must be the same sample on every rank (T, text length, image
+        size, prompt ids, audio kind, the per-second vector - which carries T0 and the a1 cap -, the pixel geometry); a
+        mismatch raises ValueError on every rank alike (all of them read the same gathered vectors), so none waits forever
+        on a collective the others never reach"""
+        def fp(b):
+            b = np.frombuffer(bytes(b), dtype=np.uint8)
+            return [int(v) for v in fingerprint_rows_host(b).view(np.int64)[0]] if b.size else [0, 0]
+        pid = None if prompt_ids is None else np.asarray([int(v) for v in prompt_ids], dtype="<i8")
+        kind = 0 if audio is None else 1 + sum(1 << i for i, k in enumerate(("audio_tokens", "beats_windows", "audio_wav"))
+                                               if isinstance(audio, dict) and audio.get(k) is not None)
+        geom = repr((str(px_s.dtype), tuple(px_s.shape[1:]), str(px_d.dtype), tuple(px_d.shape[1:]))).encode()
+        vec = [T, n_text_tokens, int(image_size[0]), int(image_size[1]), -1 if pid is None else len(pid)] + \
+            (fp(b"") if pid is None else fp(pid.tobytes())) + [kind, len(sample_indices)] + \
+            fp(np.asarray([int(v) for v in sample_indices], dtype=np.int8).tobytes()) + fp(geom) + [int(refused is not None)]
+        got = [g.tolist() for g in self.comm.all_gather(torch.tensor(vec, dtype=torch.int64, device=px_s.device))]
+        if any(g[-1] for g in got):
+            raise ValueError("ShardedVideoEncoder.encode_video(cache=...): the frame cache of rank(s) %s was made for other "
+                             "engine settings%s" % ([r for r, g in enumerate(got) if g[-1]],
+                                                    "" if refused is None else " (%s)" % (refused,)))
+        bad = sorted({self.AGREE_FIELDS[j] for g in got for j in range(len(vec)) if g[j] != got[0][j]})
+        if bad:
+            raise ValueError("ShardedVideoEncoder.encode_video(cache=...): the ranks were given different samples (%s differ); "
+                             "every rank must be called with the same video and prompt" % ", ".join(bad))
+
+    def _refined_sims_cached(self, band, px_d, ranges, cache, dk, stats):
+        """_refined_sims with this rank's cache (None: a bypassing rank): band pairs whose precise value the cache holds are not
+        re-encoded.  Whether the right neighbour must send the precise rows of its first frame depends on this rank's cache:
+        one all-gather of per-rank "my boundary pair is in the band and not cached" flags gives every rank the same
+        send / receive list (no flag set: no exchange, on every rank).  dk: the DINOv2 keys of the local frames and, last, of
+        the right neighbour's first frame.  -> the refined values of the whole band in band order, on every rank."""
+        e, rank, world = self.e, self.rank, self.world
+        lo, hi = ranges[rank]
+        dev = px_d.device
+        mine = [i for i in band if lo <= i < hi]
+
+        def pk(i):
+            return ("precise", dk[i - lo], dk[i - lo + 1])
+        vals = {i: (None if cache is None else cache.pair_get(pk(i))) for i in mine}
+        todo = [i for i in mine if vals[i] is None]
+        cross = rank < world - 1 and (hi - 1) in todo
+        flags = torch.cat(self.comm.all_gather(torch.tensor([int(cross)], dtype=torch.int64, device=dev))).tolist()
+        send_first = rank > 0 and flags[rank - 1] == 1
+        frames = {f for i in todo for f in (i, i + 1) if f < hi}
+        if send_first:
+            frames.add(lo)
+        feats = precise_features(e, px_d, sorted(frames), lo) if frames else {}
+        stats["precise_frames_computed"] += len(frames)
+        if any(flags):
+            sends = [(feats[lo].contiguous(), rank - 1)] if send_first else []
+            recvs = []
+            if cross:
+                buf = torch.empty_like(next(iter(feats.values())))
+                feats[hi] = buf
+                recvs = [(buf, rank + 1)]
+            self.comm.exchange(sends, recvs)
+        if todo:
+            for i, v in zip(todo, e.pair_sims(feats, [(i, i + 1) for i in todo]).tolist()):
+                vals[i] = float(v)
+                if cache is not None:
+                    cache.put_computed(pk(i), v)
+        local = torch.tensor([vals[i] for i in mine], dtype=torch.float32, device=dev)
+        counts = [sum(1 for i in band if l <= i < h) for (l, h) in ranges]
+        return self._all_gather_var(local, counts).tolist()
+
+    def _encode_cached(self, cache, px_s, px_d, T, image_size, n_text_tokens, prompt_ids, audio, sample_indices,
+                       recompute_halo, info):
+        """encode_video through this rank's FrameCache, bit for bit the uncached result (pipeline.encode_video_cached, per
+        rank): 1. sample agreement (_agree); 2. the local frames are fingerprinted where they lie, only those the cache lacks
+        run through the towers and the connector (a rank whose frames exceed its budget runs them uncached and stores
+        nothing); 3. local similarities from the cache / the slab, the boundary exchange as in the uncached path plus the
+        128-bit DINOv2 key of the first frame, so the left rank can look the pair across the boundary up; 4. the refinement
+        through the cache (_refined_sims_cached); 5. connector rows out of the slab, BEATs windows through the cache; 6. the
+        prompt-dependent steps as in the uncached path."""
+        e, rank, world = self.e, self.rank, self.world
+        if recompute_halo:
+            raise ValueError("ShardedVideoEncoder.encode_video: recompute_halo=True does not combine with a frame cache "
+                             "(the cached path exchanges the boundary frame's DINOv2 rows and key)")
+        refused = None
+        try:
+            cache.bind(e)
+        except ValueError as ex:           # raised on every rank by _agree: no rank is left waiting in a collective
+            refused = ex
+        cfg = e.cfg
+        ranges = seg.shard_ranges(T, world)
+        lo, hi = ranges[rank]
+        Tl = hi - lo
+        if sample_indices is None:
+            sample_indices = [1] * T
+        dev = px_s.device
+        self._agree(T, n_text_tokens, image_size, prompt_ids, audio, sample_indices, px_s, px_d, refused)  # 1.
+        assert px_s.shape[0] == Tl and px_d.shape[0] == Tl
+        before = cache.stats()
+        stats = dict(rank=rank, bypassed=False, frames=Tl, frames_hit=0, frames_encoded=0, pairs_computed=0, evictions=0,
+                     bytes=before["bytes"], windows_encoded=0, precise_frames_computed=0)
+        if Tl == 0:
+            if info is not None:
+                info["cache"] = stats
+            return self._pass_through(T, image_size, n_text_tokens, audio, ranges, dev)
+        # 2. keys, the frames this rank lacks
+        idx = list(range(Tl))
+        keys, dkeys = cache.frame_keys(e, px_s, px_d, idx, image_size)
+        segmented = T > cfg.get("max_num_segments", 24) + 1
+        early = {}
+
+        def after_dino(new, dino):
+            # local pairs of two new frames: enqueued before the SigLIP tower, read while it runs (encode_video_cached)
+            pos = {k: j for j, k in enumerate(new)}
+            todo = [i for i in range(Tl - 1) if keys[i] in pos and keys[i + 1] in pos and
+                    cache.pair_get((dkeys[i], dkeys[i + 1])) is None]
+            if segmented and todo:
+                slab = dino.view(len(new), dino.shape[0] // len(new), dino.shape[1])
+                early["pairs"] = todo
+                early["read"] = e.slot_sims(slab, [(pos[keys[i]], pos[keys[i + 1]]) for i in todo], defer=True)
+
+        new = encode_missing(e, cache, keys, px_s, px_d, idx, image_size, after_dino) if cache.fits(keys) else None
+        bypass = new is None
+        if bypass:                             # over this rank's budget: its towers run uncached, nothing is stored
+            early.clear()
+            side_sig = start_side_tower(e, px_s)
+            dino_all = e.tower("dino", px_d)
+            sig = join_side_tower(e, side_sig, px_s)
+            P = dino_all.shape[0] // Tl
+        # 3. similarities
+        if not segmented:
+            seg_idx = list(range(T))
+        else:
+            first = dino_all[:P] if bypass else cache.dino_rows(keys[0])
+            Pr, Dp = first.shape
+            sends, recvs = [], []
+            if rank > 0:
+                u = [(v - (1 << 64)) if v >= 1 << 63 else v for v in dkeys[0][0]]
+                sends = [(first, rank - 1), (torch.tensor(u, dtype=torch.int64, device=dev), rank - 1)]
+            pair_buf = key_buf = None
+            if rank < world - 1:
+                pair_buf = torch.empty(2, Pr, Dp, dtype=first.dtype, device=first.device)   # [my last frame, the halo]
+                key_buf = torch.empty(2, dtype=torch.int64, device=dev)
+                recvs = [(pair_buf[1], rank + 1), (key_buf, rank + 1)]
+            self.comm.exchange(sends, recvs)
+            right = None
+            if key_buf is not None:
+                right = (tuple(v & 0xFFFFFFFFFFFFFFFF for v in key_buf.tolist()), dkeys[0][1])
+            if bypass:
+                parts = [e.sims_tensor(dino_all, Tl)] if Tl >= 2 else []
+                if pair_buf is not None:
+                    parts.append(e.sims_tensor(torch.cat([dino_all[(Tl - 1) * P: Tl * P], pair_buf[1]], 0), 2))
+                sims_local = torch.cat(parts, 0) if parts else torch.zeros(0, dtype=torch.float32, device=dev)
+            else:
+                local = cache.adjacent_sims(e, keys, dkeys, early)
+                if right is not None:
+                    pkey = (dkeys[-1], right)
+                    v = cache.pair_get(pkey)
+                    if v is None:
+                        pair_buf[0].copy_(cache.dino_rows(keys[-1]))
+                        v = float(e.slot_sims(pair_buf, [(0, 1)])[0])
+                        cache.put_computed(pkey, v)
+                    local.append(v)
+                sims_local = torch.tensor(local, dtype=torch.float32, device=dev)
+            counts = [(h - l) - (0 if r < world - 1 else 1) for r, (l, h) in enumerate(ranges)]
+            sims = self._all_gather_var(sims_local, counts).tolist()
+            assert len(sims) == T - 1
+            # 4. the selection refinement
+            dk = list(dkeys) + ([right] if right is not None else [])
+            seg_idx = select_segments_with(e, sims, lambda b: self._refined_sims_cached(b, px_d, ranges, None if bypass else cache,
+                                                                                       dk, stats))
+        # 5. connector rows and audio rows of the local frames
+        if bypass:
+            X, _ = e.connector(sig, dino_all[: Tl * P], Tl, [tuple(image_size)] * Tl)
+            N = X.shape[0] // Tl
+            a_local = e.local_audio(audio, sample_indices, T, lo, hi)
+        else:
+            X = cache.assemble(e, keys)
+            N = cache.rows_per_frame
+            a_local = None if audio is None else cached_audio(e, cache, audio, sample_indices, T, lo, hi)
+        Xf, Nf = e.with_audio(X, Tl, N, a_local)
+        out = self._compress_gather(Xf, N, Nf, T, ranges, seg_idx, n_text_tokens, prompt_ids, dev)        # 6.
+        if info is not None:
+            after = cache.stats()
+            fresh = set(new or ())
+            stats.update(bypassed=bypass, frames_hit=0 if bypass else sum(1 for k in keys if k not in fresh),
+                         frames_encoded=Tl if bypass else after["frames_encoded"] - before["frames_encoded"],
+                         pairs_computed=after["pairs_computed"] - before["pairs_computed"],
+                         evictions=after["evictions"] - before["evictions"], bytes=after["bytes"],
+                         windows_encoded=after["windows_encoded"] - before["windows_encoded"])
+            info["cache"] = stats
+        return out

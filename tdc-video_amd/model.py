@@ -370,7 +370,8 @@ class CambrianMetaModel:
         tdc/cambrian_arch.py:698-745);
         `config.tdc_frame_cap` (default 224 = the reference's "in case of OOM" constant, tdc/cambrian_arch.py:907-916,813-822):
         the cap of both frame sub-samplings; `config.tdc_shard_frames`: see prepare_inputs_labels_for_multimodal;
-        `config.tdc_video_cache_bytes`: see tdc_video_cache; `config.tdc_batch_frames`: see tdc_batch_frames.
+        `config.tdc_video_cache_bytes`: see tdc_video_cache; `config.tdc_shard_cache_bytes`: see tdc_shard_cache;
+        `config.tdc_batch_frames`: see tdc_batch_frames.
         bench.py's line is reproduced by dtype=float16, tdc_tower_dtype="bfloat16", tdc_tower_res_dtype="float16",
         tdc_frame_cap=T (its `product_setting` field says so; `bench.py --via-mixin` runs exactly that)."""
         if self._tdc_encoder is None or refresh:
@@ -426,7 +427,8 @@ class CambrianMetaModel:
         """the engine's FrameCache (cache.py) when `config.tdc_video_cache_bytes` is a positive byte budget; None when the key
         is absent or 0.  Videos and single images then skip the towers and the connector for frames whose content the
         cache holds - the results are bit for bit those without it.  Ignored (None) under `config.tdc_shard_frames`:
-        the frame-sharded path does not cache.  A new engine (tdc_engine(refresh=True)) gets a new, empty cache."""
+        the frame-sharded path has a per-rank cache of its own (tdc_shard_cache).  A new engine (tdc_engine(refresh=True))
+        gets a new, empty cache."""
         n = getattr(self.config, "tdc_video_cache_bytes", None)
         if isinstance(n, bool) or not (n is None or isinstance(n, int)) or (n or 0) < 0:
             raise ValueError("config.tdc_video_cache_bytes must be a byte budget (a non-negative int; 0 / absent = off), "
@@ -443,6 +445,31 @@ class CambrianMetaModel:
     def tdc_video_cache_clear(self):
         """empty the frame cache (and release its device memory); no-op when it is off"""
         c = getattr(self, "_tdc_video_cache", None)
+        if c is not None:
+            c.clear()
+
+    def tdc_shard_cache(self):
+        """this rank's FrameCache of the frame-sharded path (dist.ShardedVideoEncoder.encode_video(cache=...)) when
+        `config.tdc_shard_cache_bytes` is a positive per-rank byte budget and `config.tdc_shard_frames` is set; None when the
+        key is absent or 0.  Each rank caches its own frames; a second question on a video skips the towers and the
+        connector on every rank whose frames the cache holds - the results are bit for bit those without it.  A new engine
+        (tdc_engine(refresh=True)) gets a new, empty cache."""
+        n = getattr(self.config, "tdc_shard_cache_bytes", None)
+        if isinstance(n, bool) or not (n is None or isinstance(n, int)) or (n or 0) < 0:
+            raise ValueError("config.tdc_shard_cache_bytes must be a per-rank byte budget (a non-negative int; 0 / absent = "
+                             "off), got %r" % (n,))
+        if not n or not getattr(self.config, "tdc_shard_frames", False):
+            return None
+        eng = self.tdc_engine()
+        c = getattr(self, "_tdc_shard_cache", None)
+        if c is None or getattr(self, "_tdc_shard_cache_engine", None) is not eng or c.max_bytes != n:
+            c = self._tdc_shard_cache = eng.new_cache(n)
+            self._tdc_shard_cache_engine = eng
+        return c
+
+    def tdc_shard_cache_clear(self):
+        """empty this rank's frame cache of the sharded path (and release its device memory); no-op when it is off"""
+        c = getattr(self, "_tdc_shard_cache", None)
         if c is not None:
             c.clear()
 
@@ -659,15 +686,16 @@ class CambrianMetaForCausalLM(ABC):
                     # with the same video - how the reference's eval drivers start their workers, eval/eval_mlvu.py:129-157 -
                     # but here the ranks split the FRAMES of the one video): this rank encodes frames [lo, hi) of the a1
                     # selection, dist.ShardedVideoEncoder exchanges what crosses the rank boundaries and all-gathers the
-                    # emitted tokens, so every rank returns the same 10-tuple as the serial path, bit for bit.  The frame cache
-                    # (config.tdc_video_cache_bytes) is not used here: tdc_video_cache() is None under tdc_shard_frames
+                    # emitted tokens, so every rank returns the same 10-tuple as the serial path, bit for bit.  The serial frame
+                    # cache (config.tdc_video_cache_bytes) is not used here; config.tdc_shard_cache_bytes gives each rank a
+                    # cache of its own frames (tdc_shard_cache)
                     fp = sharded.frame_plan(vid_s.shape[0], btl, cap, vindex)
                     eng.two_streams = model.tdc_side_stream(fp["hi"] - fp["lo"])
                     sel_s = torch.as_tensor(fp["siglip_frames"], dtype=torch.long, device=vid_s.device)
                     sel_d = torch.as_tensor(fp["dino_frames"], dtype=torch.long, device=vid_d.device)
                     vis = sharded.encode_video(vid_s[sel_s].to(eng.dev), vid_d[sel_d].to(eng.dev), fp["T"],
                                                tuple(image_sizes[i]), n_text, prompt_ids, audio=audio,
-                                               sample_indices=fp["sample_indices"])
+                                               sample_indices=fp["sample_indices"], cache=model.tdc_shard_cache(), info=keep)
                     keep["final_size"] = [seg.unpad_newline_map(eng.side, tuple(image_sizes[i]), 0)[1]] * fp["T"]
                     splice = None
                 else:

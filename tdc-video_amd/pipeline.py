@@ -1222,21 +1222,23 @@ def encode_image_cached(e, cache, px_siglip, px_dino, image_size):
     return cache.assemble(e, keys), cache.final_sizes(keys)
 
 
-def cached_audio(e, cache, audio, sample_indices, T):
-    """a20 of encode_video_cached: local_audio(audio, sample_indices, T), with the BEATs windows of a raw waveform taken from
-    the cache where it holds their waveform and mask slices (keys: fingerprints of the slices; window features are item-wise)"""
+def cached_audio(e, cache, audio, sample_indices, T, lo=0, hi=None):
+    """a20 of encode_video_cached: local_audio(audio, sample_indices, T, lo, hi), with the BEATs windows of a raw waveform taken
+    from the cache where it holds their waveform and mask slices (keys: fingerprints of the slices; window features are
+    item-wise).  [lo, hi): the frames of one rank of the frame-sharded path (dist.py) - only their windows are used."""
+    hi = T if hi is None else hi
     if not (isinstance(audio, dict) and audio.get("audio_tokens") is None and audio.get("beats_windows") is None
             and audio.get("audio_wav") is not None and getattr(e, "beats", None) is not None):
-        return e.local_audio(audio, sample_indices, T, 0, T)
+        return e.local_audio(audio, sample_indices, T, lo, hi)
     from .beats import SAMPLE_RATE
     wav, mask = audio["audio_wav"], audio.get("audio_wav_mask")
     n_s = wav.shape[1]
     starts = e.beats.window_starts(n_s)
     sizes = e.beats.window_token_counts(n_s)
     plan = seg.audio_plan(sizes, [int(v) for v in sample_indices])
-    need = sorted({w for i in range(min(T, len(plan))) for (w, _, _) in plan[i][0]})
+    need = sorted({w for i in range(lo, min(hi, T, len(plan))) for (w, _, _) in plan[i][0]})
     if not need:
-        return e.local_audio(audio, sample_indices, T, 0, T)
+        return e.local_audio(audio, sample_indices, T, lo, hi)
     m = None if mask is None else torch.as_tensor(mask).bool().cpu()
     if m is not None and not bool(m.any()):
         m = None                                                  # what window_features does with an all-False mask
@@ -1256,7 +1258,7 @@ def cached_audio(e, cache, audio, sample_indices, T):
             fps[w] = e.fingerprint(wd, [1], keys[w][2] * eb, SAMPLE_RATE * starts[w] * eb)[0]
     keys = {w: keys[w] + (tuple(fps[w]),) for w in need}
     feats = cache.windows(keys, lambda todo: e.beats_windows(wav, mask, only=todo))
-    return e.audio_tokens(feats, sample_indices, T, 0, T, window_sizes=sizes)
+    return e.audio_tokens(feats, sample_indices, T, lo, hi, window_sizes=sizes)
 
 
 def fingerprint_mask(m):
