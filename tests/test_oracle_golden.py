@@ -1,11 +1,13 @@
 """Pins oracle/tdc_oracle.py to the reference: every stage against fixtures produced by running the reference
 (tests/golden/make_golden.py).  CPU only."""
+import os
+
 import numpy as np
 import pytest
 import torch
 
 import synth
-from util import oracle, load_fixture, embed_fn, pipeline_cfg
+from util import GOLDEN, oracle, load_fixture, embed_fn, pipeline_cfg
 
 ATOL = 2e-5
 
@@ -159,3 +161,149 @@ def test_audio_tokens_with_dropped_frames():
     close(out[0], wins[0][0, :50])                                              # kept, next kept -> verbatim
     close(out[1], torch.nn.functional.adaptive_avg_pool2d(wins[0][:, 50:200], (50, 8))[0])   # 1 kept + 2 dropped
     close(out[2], torch.nn.functional.adaptive_avg_pool2d(wins[0][:, 200:300], (50, 8))[0])
+
+
+# ---- full model dimensions: the oracle against digests of the reference's outputs (tests/golden/make_golden_fulldim.py) -----
+# Weights and inputs are rebuilt from synth.fill's hash; the fixtures hold only digests (synth.digest).  Each fixture also has
+# a sensitivity test: one host-side perturbation of the weights or arguments, of the kind of bug the digests are meant for,
+# must fail the same comparison.
+FULLDIM_TOL = 2e-5
+FULLDIM_LAYERS = (4, 4)
+
+
+def test_synth_fill_literal_values():
+    """synth.fill is integer hashing only; these bits must not move with a numpy upgrade (the fixtures depend on them)."""
+    assert synth.name_hash("probe") == 17975714548341171953
+    assert synth.fill("probe", (8,), "pixels").tolist() == [
+        -0.5088361501693726, -0.959699273109436, 0.4637244939804077, 0.5194743871688843, -0.9659587144851685,
+        0.4994715452194214, -0.7230956554412842, -0.28796398639678955]
+    u = synth.fill("vision_tower_aux_list.0.vision_tower.encoder.layers.0.mlp.fc1.weight", (4304, 1152))    # linear
+    assert u[0, :3].tolist() == [-0.04016349837183952, 0.004593810997903347, -0.04890754446387291]
+    assert u[-1, -2:].tolist() == [0.02125607430934906, 0.023045578971505165]
+    assert u.reshape(-1)[(1 << 22) + 5] == np.float32(-0.03494581952691078)          # second chunk of the hash
+    assert synth.fill("vision_tower_aux_list.1.vision_tower.encoder.layer.3.layer_scale2.lambda1", (1536,))[:2].tolist() == [
+        0.729943573474884, 0.8447016477584839]
+
+
+@pytest.fixture(scope="module")
+def fulldim_sd():
+    sd = synth.synth_state_dict(*FULLDIM_LAYERS, prefixes=("vision_tower_aux_list.", "vision_sampler_0.", "vision_query",
+                                                             "Qformer.", "query_proj.", "vision_proj."))
+    return sd, oracle.sub(sd, "vision_tower_aux_list.0.vision_tower."), oracle.sub(sd, "vision_tower_aux_list.1.vision_tower.")
+
+
+def fulldim_errors(name, key, x):
+    z = np.load(os.path.join(GOLDEN, name))
+    return synth.digest_errors(synth.load_digest(z, key), torch.as_tensor(x).double().numpy())
+
+
+def assert_fulldim(name, key, x, tol=FULLDIM_TOL):
+    e = fulldim_errors(name, key, x)
+    print("%s %s: %s" % (name, key, " ".join("%s %.2e" % kv for kv in e.items())))
+    assert max(e.values()) <= tol, e
+    return e
+
+
+def assert_fulldim_fails(name, key, x, tol=FULLDIM_TOL):
+    e = fulldim_errors(name, key, x)
+    worst = max(e, key=e.get)
+    print("%s %s perturbed: fails by %.0fx on %s (%s)" % (name, key, e[worst] / tol, worst,
+                                                          " ".join("%s %.2e" % kv for kv in e.items())))
+    assert e[worst] > 10 * tol, e
+
+
+def fulldim_siglip(Ws):
+    return oracle.siglip_tower(synth.synth_input("pixels/siglip", (2, 3, 384, 384)), Ws, heads=16)
+
+
+def test_fulldim_siglip(fulldim_sd):
+    """1152 wide, 16 heads of 72, MLP 4304, 27^2 patches -> 24^2 (4 layers, 2 frames)."""
+    out, pre = fulldim_siglip(fulldim_sd[1])
+    assert_fulldim("fulldim_siglip.npz", "out_pre_interp", pre)
+    assert_fulldim("fulldim_siglip.npz", "out", out)
+
+
+def test_fulldim_siglip_sensitivity(fulldim_sd):
+    """heads 3 and 11 of the last layer's V projection swapped"""
+    W = dict(fulldim_sd[1])
+    for n in ("weight", "bias"):
+        k = "encoder.layers.3.self_attn.v_proj." + n
+        w = W[k].clone()
+        w[3 * 72:4 * 72], w[11 * 72:12 * 72] = W[k][11 * 72:12 * 72], W[k][3 * 72:4 * 72]
+        W[k] = w
+    assert_fulldim_fails("fulldim_siglip.npz", "out", fulldim_siglip(W)[0])
+
+
+def fulldim_dino(Wd):
+    return oracle.dino_tower(synth.synth_input("pixels/dino", (2, 3, 378, 378)), Wd, heads=24)
+
+
+def test_fulldim_dino(fulldim_sd):
+    """1536 wide, 24 heads, SwiGLU 4096, LayerScale, position table 37^2 -> 27^2 (bicubic), tokens 27^2 -> 24^2 (4 layers)."""
+    out, pre = fulldim_dino(fulldim_sd[2])
+    assert_fulldim("fulldim_dino.npz", "out_pre_interp", pre)
+    assert_fulldim("fulldim_dino.npz", "out", out)
+
+
+def test_fulldim_dino_sensitivity(fulldim_sd):
+    """the 37 x 37 position grid shifted by one column"""
+    W = dict(fulldim_sd[2])
+    pos = W["embeddings.position_embeddings"]
+    grid = pos[:, 1:].reshape(1, 37, 37, -1)
+    W["embeddings.position_embeddings"] = torch.cat([pos[:, :1], torch.roll(grid, 1, dims=2).reshape(1, 37 * 37, -1)], 1)
+    assert_fulldim_fails("fulldim_dino.npz", "out", fulldim_dino(W)[0])
+
+
+def fulldim_sva(sd, size):
+    aux = [synth.synth_input("features/sva_aux%d" % i, (3, 576, 1024)) for i in range(2)]
+    return oracle.sva(aux, sd["vision_query"][0], [size] * 3, sd, side=12)
+
+
+@pytest.mark.parametrize("tag,size", [("square", (384, 384)), ("wide", (360, 640))])
+def test_fulldim_sva(fulldim_sd, tag, size):
+    """C = 1024, 3 layers, 12 x 12 windows of 2 x 2 keys per tower; (360, 640): the window masks of a 16:9 frame."""
+    out, masks = fulldim_sva(fulldim_sd[0], size)
+    z = np.load(os.path.join(GOLDEN, "fulldim_sva.npz"))
+    for i in range(2):
+        assert np.array_equal(masks[i].numpy(), z["mask%d_%s" % (i, tag)])
+    assert z["mask0_" + tag].all() == (tag == "square")
+    assert_fulldim("fulldim_sva.npz", "out_" + tag, out)
+
+
+def test_fulldim_sva_sensitivity(fulldim_sd, monkeypatch):
+    """the last valid key of every partly masked window of the 16:9 frame dropped"""
+    wm = oracle.window_masks
+
+    def short(side, reduce, image_size):
+        m = wm(side, reduce, image_size)
+        for row in m:
+            if not row.all():
+                row[int(torch.nonzero(row)[-1])] = False
+        return m
+    monkeypatch.setattr(oracle, "window_masks", short)
+    assert_fulldim_fails("fulldim_sva.npz", "out_wide", fulldim_sva(fulldim_sd[0], (360, 640))[0])
+
+
+def fulldim_qformer(sd, K, N, queries=None):
+    z = np.load(os.path.join(GOLDEN, "fulldim_qformer.npz"))
+    chunk = synth.synth_input("features/qformer_N%d" % N, (8, N, 3584))
+    ids = torch.from_numpy(z["prompt_ids"])
+    if queries is None:
+        return oracle.compress_chunk(chunk, ids, sd, K, heads=12)[0]
+    last = oracle.qformer_bert(queries(chunk[0])[None].expand(7, -1, -1), chunk[1:], ids, sd, heads=12)
+    return torch.nn.functional.normalize(oracle._lin(last[:, :K], sd, "vision_proj"), dim=-1)
+
+
+@pytest.mark.parametrize("K,N", [(144, 156), (16, 156), (16, 84)])
+def test_fulldim_qformer(fulldim_sd, K, N):
+    """one 8-frame chunk: bert-base Q-Former (12 layers, cross-attention to H = 3584 in the even ones), Lt = 12 prompt ids,
+    K = 144 / 16 pooling windows over N = 156 (square) or 84 (16:9) tokens of the key frame."""
+    assert len(np.load(os.path.join(GOLDEN, "fulldim_qformer.npz"))["prompt_ids"]) == 12
+    assert_fulldim("fulldim_qformer.npz", "out_K%d_N%d" % (K, N), fulldim_qformer(fulldim_sd[0], K, N))
+
+
+def test_fulldim_qformer_sensitivity(fulldim_sd):
+    """K = 16 pooling windows (each query repeated 9 times) where K = 144 is expected"""
+    sd = fulldim_sd[0]
+    q = lambda key: oracle._lin(oracle.adaptive_avg_pool_tokens(key, 16).repeat_interleave(9, 0), sd, "query_proj")
+    assert_fulldim_fails("fulldim_qformer.npz", "out_K144_N156", fulldim_qformer(sd, 144, 156, q))
