@@ -14,6 +14,16 @@
  *  - 16-bit tensors are fp16 (TDC_F16) or bf16 (TDC_BF16), accumulation / LayerNorm / softmax / GELU are fp32;
  *  - activation matrices are row-major [rows, ld] with ld = round_up(cols, 64) and ZERO pad columns; weights are
  *    nn.Linear layout [out, in] padded the same way (prepared once by tdc-video_amd/weights.py).
+ *
+ * Memory contract (pinned by tests/test_hip_memory_contract.py: outputs inside sentinel-filled arenas, inputs surrounded by
+ * 0x00 / 0xFF bytes, results bit-identical under both)
+ *  - a call READS only the rows / elements its description names: rows 0 .. rows-1 (through the row map where there is one -
+ *    never the gaps of a map), columns 0 .. cols-1 plus, where a kernel loads whole 16-byte pieces, the ZERO pad columns up to
+ *    ld that the convention above promises.  Memory behind the last row, in front of the base pointer, rows a map or an index
+ *    array never names, and scratch / workspace contents on entry never reach a result;
+ *  - a call WRITES only what the "writes:" line of its description says.  Pure outputs are fully overwritten there (no
+ *    accumulation into their previous contents).  Where the line says "pad columns: caller", the kernel leaves the columns
+ *    cols .. ld untouched and a consumer that relies on zero pad columns needs them zeroed once by the buffer's owner.
  */
 #ifndef TDC_HIP_H
 #define TDC_HIP_H
@@ -39,7 +49,8 @@ extern "C" {
 typedef struct { int seg, stride, off, inner; } tdc_rowmap;
 
 /* C[c_map(m), n] = act(sum_k A[a_map(m), k] * W[n, k] + bias[n]) + res[r_map(m), n]        (nn.Linear + epilogue)
- * K % 64 == 0, N % 4 == 0 (N % 8 == 0 for SWIGLU, output col = n/2).  Replaces every nn.Linear on the path. */
+ * K % 64 == 0, N % 4 == 0 (N % 8 == 0 for SWIGLU, output col = n/2).  Replaces every nn.Linear on the path.
+ * An activation excludes a residual and an fp32 output (TDC_E_BADARG): the activation epilogues store 16-bit values. */
 typedef struct {
     const void* A; int lda;
     const void* W; int ldw;
@@ -85,6 +96,10 @@ typedef struct {
      * and whose residual stream is kept in fp16 (tdc_vit_model.res_dtype_p1): C = fp16(acc + bias + float(res)), one rounding.
      * Needs 16-bit C (out_f32 == 0), act == NONE, no LayerNorm-fusion / fp8 operand. */
     int c16_dtype_p1;
+    /* writes: C[c_map(m), 0 .. n_out) for m < M, n_out = N (N / 2 for SWIGLU) - and, with c_pad8, possibly the columns
+     * N .. round_up(N, 8) of those rows; never the columns n_out (round_up(N, 8)) .. ldc (pad columns: caller), never a row no
+     * m < M maps to.  In place (C == res) the same set.  x16[m, 0 .. N), ln_part[s][m][0 .. 2) for s < N / 64, out_stats[m][0 .. 2)
+     * for m < M.  reads: A[a_map(m), 0 .. K), W[n, 0 .. K) for n < N, bias[0 .. N), res[r_map(m), 0 .. N), ln_stats[m], ln_c1[0 .. N). */
 } tdc_gemm_desc;
 int tdc_gemm(const tdc_gemm_desc* d, void* stream);
 /* Diagnostics only (tools/, never the product path): 1 = skip the C-tile epilogue (nothing is written), 2 = un-staged
@@ -99,18 +114,22 @@ int tdc_gemm_set_persistent_grid(int workgroups);
 /* per-row e4m3 quantisation of a 16-bit matrix x [rows, ldx] (cols % 8 == 0, cols <= 4608): y8 [rows, ldy8] = x / s_a[r]
  * with s_a[r] = max|x[r]| / 448 (zero bytes up to the next multiple of 128 columns when ldy8 allows), stats[r] =
  * (0, s_a[r] * wscale) - the operands of an fp8-operand tdc_gemm whose input does not come out of a LayerNorm (the
- * attention output, the MLP hidden). */
+ * attention output, the MLP hidden).
+ * writes: y8[r, 0 .. round_up(cols, 128)) when ldy8 >= that, else y8[r, 0 .. cols); stats[r][0 .. 2); r < rows. */
 int tdc_quantize_rows_fp8(const void* x, int ldx, int rows, int cols, int dtype, void* y8, int ldy8, float* stats,
                           float wscale, void* stream);
 /* (mean, M2) partials [slots, rows, 2] of `slots` 64-column slots per row -> stats [rows, 2] = (mean, 1 / sqrt(var + eps)), biased
- * variance over slots * 64 columns (nn.LayerNorm); Chan's parallel combination in a fixed order. */
+ * variance over slots * 64 columns (nn.LayerNorm); Chan's parallel combination in a fixed order.  writes: stats[r][0 .. 2), r < rows. */
 int tdc_ln_finalize(const float* ln_part, int slots, int rows, float eps, float* stats, void* stream);
 
 /* LayerNorm over `cols` real columns of x [rows, ldx] (fp32 or 16-bit), optional additive table before the norm:
  * x'[r] = x[r] + add[(r % add_period) mapped by add_mode]; y = LN(x') * gamma + beta.  Writes y16 (16-bit, pad
  * columns zeroed, may be NULL) and/or y32 (fp32, may alias x, may be NULL).
  * add_mode 0: table row = r % add_period; 1: SVA 2x2 window position ((y&1)*2 + (x&1)) of token r % add_period on a
- * sqrt(add_period)-wide grid (tdc/vision_sampler.py:375-384). */
+ * sqrt(add_period)-wide grid (tdc/vision_sampler.py:375-384).
+ * writes: columns 0 .. round_up(cols, 64) of the rows y_map(r), r < rows, of every output given (y16 / y32 / y8: zeros beyond
+ * cols) when EVERY given output has ld >= round_up(cols, 64), otherwise columns 0 .. cols only (pad columns: caller); columns
+ * beyond round_up(cols, 64) never; y8_stats[y_map(r)][0 .. 2).  reads: x[x_map(r), 0 .. cols), gamma / beta / add rows [0 .. cols). */
 typedef struct {
     const void* x; int ldx; int x_f32;
     void* y16; int ldy16;
@@ -151,6 +170,9 @@ typedef struct {
     /* kernel form: TDC_ATTN_FORM_AUTO (0) picks by shape (the 32x32x16 kernel for long sequences at head dim 64 / 72, the
      * 16x16x32 kernels otherwise); TDC_ATTN_FORM_16X16 keeps the 16x16x32 kernels for every shape (tests compare the forms) */
     int form;
+    /* writes: o element (b, s, h, c) for b < batch, s < sq, h < heads, c < head_dim - nothing else: not the columns beyond
+     * heads * head_dim of a row (pad columns: caller), not row sq of the last query tile.  reads: q rows s < sq, k / v rows
+     * s < sk of every batch item, bias[h][q][0 .. sk), gate[(b*sq+q)][0 .. heads), key_mask[b][0 .. sk). */
 } tdc_attn_desc;
 #define TDC_ATTN_FORM_AUTO 0
 #define TDC_ATTN_FORM_16X16 1
@@ -161,30 +183,35 @@ int tdc_attention(const tdc_attn_desc* d, void* stream);
 /* ---- small data-movement / reduction kernels ------------------------------------------------------------- */
 /* pixels [B,3,H,W] (px_f32: 0 = the 16-bit type `dtype`, 1 = fp32, 2 = the OTHER 16-bit type - fp16 frames into bf16
  * towers) -> patches [B*gh*gw, ldp] 16-bit `dtype` in conv-weight order (c,ky,kx), zero pad.
- * Patch-embed conv as a GEMM (HF:models/siglip/modeling_siglip.py:124-130, dinov2/modeling_dinov2.py:140-151). */
+ * Patch-embed conv as a GEMM (HF:models/siglip/modeling_siglip.py:124-130, dinov2/modeling_dinov2.py:140-151).
+ * writes: WHOLE rows patches[row, 0 .. ldp) (zeros from 3*patch*patch on), B*gh*gw rows. */
 int tdc_im2col(const void* px, int px_f32, void* patches, int ldp, int B, int H, int W, int patch, int dtype,
                void* stream);
-/* x32 [B, S, ld] rows `row` of every batch := vec[ld] (cls token + pos[0]) */
+/* x32 [B, S, ld] rows `row` of every batch := vec[ld] (cls token + pos[0]).  writes: those B rows, all ld columns (vec has ld entries) */
 int tdc_set_rows(float* x32, int ld, int B, int S, int row, const float* vec, void* stream);
 /* the same into a 16-bit matrix x16 [B*S, ld] of type `dtype` (vec stays fp32): the cls row of a 16-bit residual stream */
+/* writes: as tdc_set_rows */
 int tdc_set_rows16(void* x16, int ld, int B, int S, int row, const float* vec, int dtype, void* stream);
 /* separable 2-tap resample of a token grid: x (fp32 or 16-bit `dtype`) [B, tok_off + n_in*n_in, ldx] -> y 16-bit
  * (`out_dtype`: may differ from `dtype` - bf16 towers feeding an fp16 connector) [B, n_out*n_out, ldy]; idx0/idx1/frac are
  * device arrays [n_out] (bilinear, align_corners=False; built by host).
- * siglip_encoder.py:43-69, dino_encoder.py:81-107 (and the cls drop of feature_select :66-79). */
+ * siglip_encoder.py:43-69, dino_encoder.py:81-107 (and the cls drop of feature_select :66-79).
+ * writes: WHOLE rows y[row, 0 .. ldy) (zeros from `cols` on), B*n_out*n_out rows.  reads: x columns 0 .. cols of the token rows. */
 int tdc_resample_tokens(const void* x, int x_f32, int ldx, int tok_off, int n_in, void* y, int ldy, int n_out,
                         const int* idx0, const int* idx1, const float* frac, int B, int cols, int dtype, int out_dtype,
                         void* stream);
 /* adjacent-frame cosine similarity on flattened features f [T, n] 16-bit: sims[t] = cos(f[t], f[t+1]), t < T-1
  * (tdc/cambrian_arch.py:832-842); n % 8 == 0.  scratch: tdc_frame_cossim_scratch_floats(T) floats.  The reduction
- * order is fixed (fp32), so the similarity ranking is reproducible run to run. */
+ * order is fixed (fp32), so the similarity ranking is reproducible run to run.
+ * writes: sims[0 .. T-1) and the scratch (every word of it before it is read: its contents on entry do not matter). */
 int tdc_frame_cossim(const void* f, long long n, int T, float* sims, float* scratch, int dtype, void* stream);
 size_t tdc_frame_cossim_scratch_floats(int T);
 /* cosine similarity of arbitrary slot pairs of a slab of per-frame features (the frame cache's DINOv2 rows): frame s starts
  * at slab + s * slot_stride elements (16-bit, slot_stride % 8 == 0, slab 16-byte aligned), n elements each (n % 8 == 0);
  * pairs: device int32 [n_pairs, 2] (slot_a, slot_b), n_pairs <= 65535.  sims[p] is bit for bit what tdc_frame_cossim gives
  * for the same two frames adjacent in a contiguous buffer (shared chunking and reduction order).
- * scratch: tdc_pair_cossim_scratch_floats(n_pairs) floats. */
+ * scratch: tdc_pair_cossim_scratch_floats(n_pairs) floats.  writes: sims[0 .. n_pairs) and the scratch (as tdc_frame_cossim);
+ * reads: the n elements of the slots the pairs name - not the gap n .. slot_stride behind a slot, not the other slots. */
 int tdc_pair_cossim(const void* slab, long long slot_stride, long long n, const int* pairs, int n_pairs, float* sims,
                     float* scratch, int dtype, void* stream);
 size_t tdc_pair_cossim_scratch_floats(int n_pairs);
@@ -192,30 +219,39 @@ size_t tdc_pair_cossim_scratch_floats(int n_pairs);
  * int32 [n_rows], n_rows <= 65535; any alignment, any length) -> out[2r], out[2r + 1] (device u64).  Words w_i = the row as
  * little-endian u64 (tail zero-padded), x_i = w_i ^ (i * 0x9E3779B97F4A7C15), h_k = mix(sum_i mix(x_i ^ S_k) ^ row_bytes)
  * with the splitmix64 finaliser mix and S_1 = 0x243F6A8885A308D3, S_2 = 0x13198A2E03707344 (sums mod 2^64: the bits do not
- * depend on the reduction order).  Not cryptographic.  scratch: tdc_fingerprint_rows_scratch_bytes(n_rows) bytes. */
+ * depend on the reduction order).  Not cryptographic.  scratch: tdc_fingerprint_rows_scratch_bytes(n_rows) bytes.
+ * writes: out[0 .. 2 n_rows) and the scratch (contents on entry do not matter).  reads: exactly the row_bytes bytes of each row:
+ * the bytes in front of an unaligned row start and behind its end never reach the fingerprint. */
 int tdc_fingerprint_rows(const void* base, long long row_stride, const int* rows, int n_rows, long long row_bytes,
                          unsigned long long* out, void* scratch, void* stream);
 size_t tdc_fingerprint_rows_scratch_bytes(int n_rows);
-/* mean over the token axis: x [B, P, ld] 16-bit -> y [B, ld] 16-bit (global context, cambrian_arch.py:1009) */
+/* mean over the token axis: x [B, P, ld] 16-bit -> y [B, ld] 16-bit (global context, cambrian_arch.py:1009).
+ * reads and writes WHOLE rows of ld elements: y's pad columns are the mean of x's (zero) pad columns */
 int tdc_token_mean(const void* x, int P, int ld, void* y, int B, int dtype, void* stream);
 /* adaptive_avg_pool1d over the token axis: y[b, k] = mean of x rows [floor(kN/K), ceil((k+1)N/K)) of frame
  * src_row[b] (b when NULL); frame f starts at row f*frame_rows (frame_rows >= N: extra rows, e.g. audio tokens, are
- * not pooled - the key frame is pooled BEFORE the audio concat, cambrian_arch.py:1609,1633-1637) */
+ * not pooled - the key frame is pooled BEFORE the audio concat, cambrian_arch.py:1609,1633-1637).
+ * reads rows 0 .. N of the named frames and writes y [B*K, ld], WHOLE rows of ld elements (pad columns as tdc_token_mean) */
 int tdc_adaptive_pool_tokens(const void* x, int N, int frame_rows, int ld, void* y, int K, int B,
                              const int* src_row, int dtype, void* stream);
 /* out[i, :cols] = table_k[row] where (k,row) = src[2i], src[2i+1]; tables: up to 4 16-bit matrices with their ld.
- * Used for unpad+newline (cambrian_arch.py:1195-1293) and token emission (:1668-1709). */
+ * Used for unpad+newline (cambrian_arch.py:1195-1293) and token emission (:1668-1709).
+ * writes: out[i, 0 .. cols) for i < n (pad columns: caller).  reads: the `cols` columns of the table rows `src` names, src[0 .. 2n). */
 typedef struct { const void* base[4]; int ld[4]; } tdc_gather_tables;
 int tdc_gather_rows(const tdc_gather_tables* t, const int* src, void* out, int ldo, int n, int cols, int dtype,
                     void* stream);
 /* every row of out [rows, ld] (16-bit, ld % 8 == 0) := row[0 .. ld) (the SVA queries start as `vision_query` on every
- * window of every frame, cambrian_arch.py:1018-1023) */
+ * window of every frame, cambrian_arch.py:1018-1023).  writes: WHOLE rows, rows * ld elements */
 int tdc_fill_rows(const void* row, void* out, int ld, int rows, void* stream);
-/* rows of x [rows, ld] 16-bit scaled to unit L2 norm over `cols` (F.normalize, eps 1e-12; cambrian_arch.py:1664) */
+/* rows of x [rows, ld] 16-bit scaled to unit L2 norm over `cols` (F.normalize, eps 1e-12; cambrian_arch.py:1664).
+ * reads and writes x[r, 0 .. cols) in place; the pad columns are neither read nor written */
 int tdc_l2_normalize(void* x, int ld, int rows, int cols, int dtype, void* stream);
 /* SVA core (tdc/vision_sampler.py:215-291): per query (frame t, window (i,j)) attend over the 2x2 windows of
  * n_towers towers: q [T*side*side, ldq]; kv[tower] [T*(side*r)^2, ldkv] with K at col 0 and V at col `dim`;
- * mask [T*side*side, n_towers*r*r] uint8; out [T*side*side, ldo].  heads x head_dim = dim. */
+ * mask [T*side*side, n_towers*r*r] uint8; out [T*side*side, ldo].  heads x head_dim = dim.
+ * writes: out[qi, 0 .. dim) for the T*side*side queries (pad columns: caller - tdc-video_amd/ops.py zeroes them at allocation).
+ * Head dims of 8 x a power of two (the path's own: 64) run a fixed-order reduction and are bit-reproducible; any other head dim
+ * runs the element-wise kernel, which sums its scores with LDS atomics: NOT bit-reproducible run to run (last-bit differences). */
 typedef struct {
     const void* q; int ldq;
     const void* kv[2]; int ldkv;
@@ -225,7 +261,8 @@ typedef struct {
 } tdc_sva_attn_desc;
 int tdc_sva_attention(const tdc_sva_attn_desc* d, void* stream);
 /* Q-Former embeddings (tdc/Qformer.py:78-108): h[f, s] = LN(s < K ? query[qsrc[f], s] : word[ids[s-K]] + pos[s-K])
- * -> h32 [F*(K+Lt), ld] fp32 and h16 */
+ * -> h32 [F*(K+Lt), ld] fp32 and h16.  writes: WHOLE rows of both, ld elements (zeros from `cols` on).  reads: the query rows
+ * qsrc names, the `word` rows ids names, pos rows 0 .. Lt. */
 typedef struct {
     const void* query; int ldq; const int* qsrc;
     const float* word; const float* pos; int ldw; const int* ids; int Lt;
@@ -243,7 +280,10 @@ int tdc_qformer_embed(const tdc_qembed_desc* d, void* stream);
  * emits the 16-bit row copy + per-slot statistics and the GEMM after them folds (mean, rstd) into its epilogue -, bilinear resample of the token grid (cls dropped).  Weights are the prepared (padded, fused,
  * LayerScale-folded) tensors of tdc-video_amd/weights.py; all pointers are device pointers except `layers`
  * (host array).  The residual stream is fp32 or 16-bit (res_dtype_p1).  Nothing is allocated: the caller passes a workspace of at least
- * tdc_vit_workspace_bytes() bytes (256-byte aligned). */
+ * tdc_vit_workspace_bytes() bytes (256-byte aligned).  The three composites (tdc_vit_fwd, tdc_qformer_fwd, tdc_connector_fwd)
+ * write `out` (WHOLE rows, ldo elements - pad columns zero) and their workspace, never a byte beyond workspace_bytes as queried;
+ * the workspace needs NO initialisation: whatever it holds on entry (a previous call's state, NaN patterns) never reaches `out` -
+ * buffers inside it that a kernel expects zeroed are zeroed by the composite itself. */
 typedef struct { const void* w; const float* b; int n, k; } tdc_lin;      /* w [n, k] 16-bit (padded), b [n] or NULL */
 typedef struct {
     const float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
@@ -362,9 +402,14 @@ typedef struct {
      * tdc/Qformer.py:285-289 on 16-bit tensors; half the bytes of the launch.  tdc_qformer_fwd uses it in its default form
      * and carries the query rows in 16 bits from here to the LayerNorm behind the layer's query FFN, which writes both copies again.) */
     int res16;
+    /* writes: h16 / h32 [f*S + k, 0 .. dim) for f < F, k < K (h16 only with res16) - the text rows f*S + K .. (f+1)*S, the
+     * columns dim .. ldh and the rows behind F*S keep their bytes.  reads: those query rows, k rows 0 .. F*Nenc (columns
+     * 0 .. dim), vt[c][0 .. round_up(F*Nenc, 8)) - the documented 4 columns past F*Nenc with Nenc % 8 == 4 are loaded and
+     * masked: any bit pattern there, NaN included, leaves the result unchanged -, ctx rows 0 .. F*K. */
 } tdc_xattn_desc;
 int tdc_qformer_xattn_supported(int dim, int heads, int K, int Nenc);
 int tdc_qformer_xattn(const tdc_xattn_desc* d, void* stream);
+/* writes: out[0 .. dim*dim).  reads: w[r, 0 .. dim) for r < dim (dim = 768). */
 int tdc_qformer_xattn_tile_weight(const void* w, int ldw, void* out, int dtype, void* stream);
 int tdc_qformer_fwd(const tdc_qformer_model* m, const void* enc, int ldenc, int F, int Nenc, const void* query, int ldq,
                     const int* qsrc, const int* ids, int Lt, int K, void* out, int ldo, void* workspace,
@@ -407,7 +452,8 @@ int tdc_connector_fwd(const tdc_connector_model* m, const void* sig, int ld_s, c
  * table lut[c*256 + v] = ((v / 255) - mean[c]) / std[c] (fp32, built by the host exactly as the HF image processor
  * computes it) -> out [T, 3, R, R] 16-bit (or fp32).  bounds [R, 2] / coeffs [R, ksize] int32 are Resample.c's
  * precompute_coeffs + normalize_coeffs_8bpc for max(H,W) -> R (tdc-video_amd/preprocess.py).  scratch:
- * tdc_preprocess_scratch_bytes() bytes. */
+ * tdc_preprocess_scratch_bytes() bytes.  writes: out [T, 3, R, R] and the scratch (contents on entry do not matter);
+ * reads: the T frames, bounds / coeffs rows 0 .. R, lut[0 .. 768). */
 size_t tdc_preprocess_scratch_bytes(int T, int H, int W, int R);
 int tdc_preprocess_frames(const unsigned char* frames, int T, int H, int W, int R, const int* bounds, const int* coeffs,
                           int ksize, int pad_r, int pad_g, int pad_b, const float* lut, void* out, int out_f32,
@@ -420,14 +466,16 @@ int tdc_preprocess_frames(const unsigned char* frames, int T, int H, int W, int 
  * (x - mean) * inv_scale.  Host-built fp32 tables: window [400], twiddle [256][2] (cos, sin of 2 pi k / 512), banks
  * [128][257], range [128][2] (non-zero span of each mel row).  Outputs (either may be NULL): plain fp32
  * [B, frames, 128]; patches 16-bit [B * (frames/16) * 8, ldp] = the im2col of the 16x16 / stride-16 patch conv
- * (BEATs.py:145-148), row (frame/16)*8 + mel/16, column (frame%16)*16 + mel%16.  tdc_fbank_frames(n) = frame count. */
+ * (BEATs.py:145-148), row (frame/16)*8 + mel/16, column (frame%16)*16 + mel%16.  tdc_fbank_frames(n) = frame count.
+ * writes: plain [B, frames, 128]; patches rows 0 .. B*(frames/16)*8, columns 0 .. 256.  reads: n_samples samples per item. */
 int tdc_fbank_frames(long long n_samples);
 int tdc_fbank(const void* wav, int wav_f32, long long n_samples, long long wav_bs, int B, const float* window,
               const float* twiddle, const float* banks, const int* range, float* plain, void* patches, int ldp,
               int dtype, float mean, float inv_scale, void* stream);
 /* gate of the gated relative position bias (backbone.py:652-657): q [rows, ldq] 16-bit (heads x head_dim columns, the
  * un-scaled q_proj output); w2 [2, head_dim], b2 [2] = grep_linear rows / biases summed in groups of 4; grep_a
- * [heads]; gate [rows, ldg] fp32 = ga * (gb * grep_a[h] - 1) + 2.  Consumed by tdc_attention's `gate`. */
+ * [heads]; gate [rows, ldg] fp32 = ga * (gb * grep_a[h] - 1) + 2.  Consumed by tdc_attention's `gate`.
+ * writes: gate[r, 0 .. heads) for r < rows (columns heads .. ldg: caller). */
 int tdc_relpos_gate(const void* q, int ldq, int rows, int heads, int head_dim, const float* w2, const float* b2,
                     const float* grep_a, float* gate, int ldg, int dtype, void* stream);
 

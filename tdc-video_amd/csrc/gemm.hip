@@ -63,6 +63,11 @@ extern "C" int tdc_gemm(const tdc_gemm_desc* d, void* stream) {
     if ((d->lda % amul) || (d->ldw % amul) || (d->ldc % 4) || (d->res && (d->ldres % 4)) || d->ldw < d->K) return TDC_E_BADARG;
     /* lda < K is legal: rows of A may overlap (sliding-window views, e.g. the BEATs conv positional embedding) */
     if (d->act != TDC_ACT_NONE && d->res) return TDC_E_BADARG;  /* activation epilogues take no residual */
+    if (d->act != TDC_ACT_NONE && d->out_f32) {   /* ... and store 16-bit values only: they used to write T-typed rows into the
+                                                      fp32 C (half of every row, the rest left as it was) */
+        fprintf(stderr, "[tdc_hip] tdc_gemm: an activation epilogue has no fp32 output (M=%d N=%d K=%d act=%d)\n", d->M, d->N, d->K, d->act);
+        return TDC_E_BADARG;
+    }
     if (d->a_map.seg < 0 || d->c_map.seg < 0 || d->r_map.seg < 0) return TDC_E_BADARG;
     if (d->x16) {   /* LayerNorm fusion, producer: fp32 residual-stream update with identity row maps, whole 64-column slots */
         if (!d->ln_part || !d->out_f32 || !d->res || !d->res_f32 || d->act != TDC_ACT_NONE || d->N % 64 != 0 ||

@@ -130,6 +130,7 @@ def gemm(a, w, bias=None, act=L.ACT_NONE, res=None, out=None, out_f32=False, M=N
         M = a.shape[0]
     assert _map_max(a_map, M) < a.shape[0], "a_map out of range"
     n_out = N // 2 if act == L.ACT_SWIGLU else N
+    assert act == L.ACT_NONE or not out_f32, "an activation epilogue has no fp32 output (tdc_gemm refuses it too)"
     if out is None:
         rows = out_rows if out_rows is not None else M
         out = torch.empty(rows, n_out, device=a.device,
