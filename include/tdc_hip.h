@@ -170,9 +170,22 @@ typedef struct {
     /* kernel form: TDC_ATTN_FORM_AUTO (0) picks by shape (the 32x32x16 kernel for long sequences at head dim 64 / 72, the
      * 16x16x32 kernels otherwise); TDC_ATTN_FORM_16X16 keeps the 16x16x32 kernels for every shape (tests compare the forms) */
     int form;
+    /* optional per-item key count (device int32 [batch], NULL = sk for every item): item b attends to the keys [0, k_len[b]),
+     * 1 <= k_len[b] <= sk.  The item runs the code a uniform launch of the same kernel form with sk = k_len[b] runs - the same
+     * key tiles from key 0, the same masked last tile -, so its output rows are bit for bit that launch's.  Keys at and beyond
+     * k_len[b] are never loaded (row indices are clamped to k_len[b] - 1): any bit pattern there, NaN included, leaves the result
+     * unchanged.  Under TDC_ATTN_FORM_AUTO the form is picked from sq and sk as passed: a caller who wants AUTO's pick for every
+     * item keeps k_len[b] >= 64 where sq >= 256 (below that every shape runs the 16x16x32 kernels anyway). */
+    const int* k_len;
+    /* optional per-item K / V source (device int32 [batch], NULL = b): item b reads its keys / values at k + kv_index[b]*k_bs and
+     * v + kv_index[b]*v_bs; q and o stay at b.  Several items may name one slot (P prompts over one frame's K / V).
+     * Both fields exclude `bias` (TDC_E_BADARG); their entries are NOT checked on the device: the caller range-checks them. */
+    const int* kv_index;
     /* writes: o element (b, s, h, c) for b < batch, s < sq, h < heads, c < head_dim - nothing else: not the columns beyond
      * heads * head_dim of a row (pad columns: caller), not row sq of the last query tile.  reads: q rows s < sq, k / v rows
-     * s < sk of every batch item, bias[h][q][0 .. sk), gate[(b*sq+q)][0 .. heads), key_mask[b][0 .. sk). */
+     * s < sk of every batch item - with k_len the rows s < k_len[b] only, with kv_index the rows of the slots it names only
+     * (a slot no item names is not read) -, k_len[0 .. batch), kv_index[0 .. batch), bias[h][q][0 .. sk),
+     * gate[(b*sq+q)][0 .. heads), key_mask[b][0 .. sk). */
 } tdc_attn_desc;
 #define TDC_ATTN_FORM_AUTO 0
 #define TDC_ATTN_FORM_16X16 1
@@ -262,13 +275,19 @@ typedef struct {
 int tdc_sva_attention(const tdc_sva_attn_desc* d, void* stream);
 /* Q-Former embeddings (tdc/Qformer.py:78-108): h[f, s] = LN(s < K ? query[qsrc[f], s] : word[ids[s-K]] + pos[s-K])
  * -> h32 [F*(K+Lt), ld] fp32 and h16.  writes: WHOLE rows of both, ld elements (zeros from `cols` on).  reads: the query rows
- * qsrc names, the `word` rows ids names, pos rows 0 .. Lt. */
+ * qsrc names, the `word` rows ids names, pos rows 0 .. Lt.
+ * Prompt table (frame_prompt != NULL): ids is a [P, ids_ld] table (ids_ld >= Lt), frame f embeds prompt p = frame_prompt[f]:
+ * row s >= K is LN(word[ids[p*ids_ld + s-K]] + pos[s-K]) when s-K < prompt_len[p] - bit for bit the single-prompt row - and a
+ * WHOLE ZERO row of h32 and h16 otherwise (every frame still occupies K + Lt rows).  writes: the same rows.  reads: frame_prompt
+ * [0 .. F), prompt_len[p] and ids[p][0 .. prompt_len[p]) of the prompts frame_prompt names - never the ids behind prompt_len[p],
+ * never a prompt no frame names.  The entries are NOT checked on the device: the caller range-checks them. */
 typedef struct {
     const void* query; int ldq; const int* qsrc;
     const float* word; const float* pos; int ldw; const int* ids; int Lt;
     const float* gamma; const float* beta; float eps;
     float* h32; void* h16; int ld;
     int F, K, cols, dtype;
+    const int* frame_prompt; const int* prompt_len; int ids_ld;   /* prompt table (all NULL / 0: one prompt for every frame) */
 } tdc_qembed_desc;
 int tdc_qformer_embed(const tdc_qembed_desc* d, void* stream);
 
@@ -351,6 +370,22 @@ typedef struct {
     const void *cross_q_tiled, *cross_out_tiled;           /* fragment-major copies of cross_q.w / cross_out.w for the fused block
                                                               (tdc_qformer_xattn_tile_weight), NULL: the per-kernel sequence */
 } tdc_qformer_layer;
+/* The multi-prompt form of the composite below (tdc_qformer_model.prompts != NULL): P prompts over ONE video in one launch
+ * sequence.  The call's F then counts VIRTUAL frames - the compressed frames of prompt 0, then those of prompt 1, ... -, its
+ * `enc` holds the enc_frames DISTINCT frames [enc_frames*Nenc, ldenc] that the stacked K/V projection runs over ONCE, its `ids`
+ * is the [n_prompts, Lt] table (Lt = the longest prompt) and `out` is [F*K, ldo] in virtual-frame order.  Virtual frame f reads
+ * the K/V of distinct frame kv_src[f], embeds prompt frame_prompt[f] of prompt_len[..] ids and self-attends over
+ * self_len[f] = K + prompt_len[frame_prompt[f]] of its K + Lt rows; the rows behind are zero-embedded padding that the
+ * row-mapped GEMMs / LayerNorms compute and nothing valid reads.  Row block f of `out` is bit for bit what the single-prompt
+ * call over that prompt's frames returns for the frame.  All four arrays are device int32, range-checked by the caller
+ * (kv_src in [0, enc_frames), frame_prompt in [0, n_prompts), prompt_len in [0, Lt]).  The workspace query reads enc_frames
+ * from the model: the K/V buffers are sized by enc_frames, everything else by F.  Runs the default form and xattn_mode 0 / 1;
+ * a model and shape that resolve to xattn_mode 2 return TDC_E_BADARG (the whole-block kernel has no per-frame K/V source).
+ * reads beyond the single form: kv_src / frame_prompt / self_len [0 .. F), prompt_len[0 .. n_prompts); writes: as the single form. */
+typedef struct {
+    int n_prompts, enc_frames;
+    const int *kv_src, *frame_prompt, *prompt_len, *self_len;
+} tdc_qformer_prompts;
 typedef struct {
     int dtype, dim, heads, n_layers, H;
     float eps;
@@ -368,6 +403,7 @@ typedef struct {
      * 0 = per-kernel sequence; 1 = q GEMM + tdc_attention, then output projection + residual + LayerNorm in one kernel
      * (needs cross_out_tiled); 2 = the whole block in one kernel per layer (needs cross_k / cross_v / both tiled weights) */
     int xattn_mode;
+    const tdc_qformer_prompts* prompts;                     /* NULL: one prompt (the form described above) */
 } tdc_qformer_model;
 size_t tdc_qformer_workspace_bytes(const tdc_qformer_model* m, int F, int K, int Lt, int Nenc);
 

@@ -157,6 +157,7 @@ bool qf_fused(const tdc_qformer_model* m, int K, int Nenc) { return qf_mode(m, K
 
 QfWs qf_layout(const tdc_qformer_model* m, int F, int K, int Lt, int Nenc) {
     const size_t S = (size_t)K + Lt, rows = (size_t)F * S, Dp = pad64i(m->dim);
+    const size_t U = m->prompts ? (size_t)m->prompts->enc_frames : (size_t)F;   // frames the K/V projections run over
     const size_t ffn = m->layers_host[0].fq2.k;
     QfWs w;
     size_t off = 0;
@@ -164,11 +165,11 @@ QfWs qf_layout(const tdc_qformer_model* m, int F, int K, int Lt, int Nenc) {
     w.h16 = off;  off += al256(rows * Dp * 2);
     w.vt = 0; w.ldvt = 0;
     if (qf_fused(m, K, Nenc)) {     // keys [F*Nenc, n_cross*dim] and transposed values [n_cross*dim, ldvt]
-        w.ldvt = ((size_t)F * Nenc + 4 + 63) / 64 * 64;     // + 4: the half-valid last key group of a frame is read as 8 columns
-        w.kv = off;   off += al256((size_t)F * Nenc * m->cross_k.n * 2);
+        w.ldvt = (U * Nenc + 4 + 63) / 64 * 64;     // + 4: the half-valid last key group of a frame is read as 8 columns
+        w.kv = off;   off += al256(U * Nenc * m->cross_k.n * 2);
         w.vt = off;   off += al256((size_t)m->cross_v.n * w.ldvt * 2);
     } else {
-        w.kv = off;   off += al256((size_t)F * Nenc * m->cross_kv.n * 2);
+        w.kv = off;   off += al256(U * Nenc * m->cross_kv.n * 2);
     }
     w.qkv = off;  off += al256(rows * m->layers_host[0].qkv.n * 2);
     w.ctx = off;  off += al256(rows * Dp * 2);
@@ -205,6 +206,7 @@ int gemm_full(const void* A, int lda, const tdc_lin& L, void* C, int ldc, int M,
 
 extern "C" size_t tdc_qformer_workspace_bytes(const tdc_qformer_model* m, int F, int K, int Lt, int Nenc) {
     if (!m || !m->layers_host || F <= 0 || K <= 0 || Nenc <= 0) return 0;
+    if (m->prompts && m->prompts->enc_frames <= 0) return 0;
     return qf_layout(m, F, K, Lt, Nenc).total;
 }
 
@@ -212,6 +214,11 @@ extern "C" int tdc_qformer_fwd(const tdc_qformer_model* m, const void* enc, int 
                                const void* query, int ldq, const int* qsrc, const int* ids, int Lt, int K, void* out,
                                int ldo, void* workspace, size_t workspace_bytes, void* stream) {
     if (!m || !enc || !query || !qsrc || !out || !workspace || F <= 0 || K <= 0 || Lt < 0) return TDC_E_BADARG;
+    // multi-prompt form (tdc_qformer_prompts): F virtual frames over U distinct ones
+    const tdc_qformer_prompts* mp = m->prompts;
+    if (mp && (mp->n_prompts <= 0 || mp->enc_frames <= 0 || !mp->kv_src || !mp->frame_prompt || !mp->prompt_len || !mp->self_len))
+        return TDC_E_BADARG;
+    const int U = mp ? mp->enc_frames : F;
     const QfWs w = qf_layout(m, F, K, Lt, Nenc);
     if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return TDC_E_WORKSPACE;
     char* ws = (char*)workspace;
@@ -243,10 +250,15 @@ extern "C" int tdc_qformer_fwd(const tdc_qformer_model* m, const void* enc, int 
         e.query = query; e.ldq = ldq; e.qsrc = qsrc; e.word = m->word; e.pos = m->pos; e.ldw = m->ldw; e.ids = ids;
         e.Lt = Lt; e.gamma = m->emb_ln_g; e.beta = m->emb_ln_b; e.eps = m->eps; e.h32 = h32; e.h16 = h16; e.ld = Dp;
         e.F = F; e.K = K; e.cols = D; e.dtype = dt;
+        if (mp) { e.frame_prompt = mp->frame_prompt; e.prompt_len = mp->prompt_len; e.ids_ld = Lt; }
         RET_IF(tdc_qformer_embed(&e, stream));
     }
     const int mode = qf_mode(m, K, Nenc);
     const bool fused = mode == 2;
+    if (mp && fused) {
+        fprintf(stderr, "[tdc_hip] tdc_qformer_fwd: the multi-prompt form runs xattn_mode 0 / 1 only\n");
+        return TDC_E_BADARG;
+    }
     {
     TdcProfTagGuard tag_kv(TDC_PROF_TAG_XATTN_BLOCK);   // the cross-attention block's launches, for tdc_profile_*
     if (fused) {
@@ -260,7 +272,7 @@ extern "C" int tdc_qformer_fwd(const tdc_qformer_model* m, const void* enc, int 
         d.M = m->cross_v.n; d.N = F * Nenc; d.K = m->cross_v.k; d.dtype = dt; d.c_pad8 = 1;
         RET_IF(tdc_gemm(&d, stream));
     } else {
-        RET_IF(gemm_full(enc, ldenc, m->cross_kv, kv, m->cross_kv.n, F * Nenc, dt, TDC_ACT_NONE, 0, nullptr, 0, 0, ident,
+        RET_IF(gemm_full(enc, ldenc, m->cross_kv, kv, m->cross_kv.n, U * Nenc, dt, TDC_ACT_NONE, 0, nullptr, 0, 0, ident,
                          ident, ident, stream));
     }
     }
@@ -276,6 +288,7 @@ extern "C" int tdc_qformer_fwd(const tdc_qformer_model* m, const void* enc, int 
         a.q_bs = a.k_bs = a.v_bs = (long long)S * L.qkv.n; a.o_bs = (long long)S * Dp;
         a.q_rs = a.k_rs = a.v_rs = L.qkv.n; a.o_rs = Dp;
         a.batch = F; a.heads = m->heads; a.head_dim = hd; a.sq = S; a.sk = S; a.scale = scale; a.dtype = dt;
+        if (mp) a.k_len = mp->self_len;     // a frame's text rows end at K + its own prompt's length
         RET_IF(tdc_attention(&a, stream));
         RET_IF(gemm_full(ctx, Dp, L.attn_out, t32, Dp, rows, dt, TDC_ACT_NONE, 1, h32, Dp, 1, ident, ident, ident,
                          stream));
@@ -303,6 +316,7 @@ extern "C" int tdc_qformer_fwd(const tdc_qformer_model* m, const void* enc, int 
             c.q_bs = (long long)K * Dp; c.k_bs = c.v_bs = (long long)Nenc * m->cross_kv.n; c.o_bs = (long long)K * Dp;
             c.q_rs = Dp; c.k_rs = c.v_rs = m->cross_kv.n; c.o_rs = Dp;
             c.batch = F; c.heads = m->heads; c.head_dim = hd; c.sq = K; c.sk = Nenc; c.scale = scale; c.dtype = dt;
+            if (mp) c.kv_index = mp->kv_src;    // the K / V of the distinct frame this virtual frame stands for
             RET_IF(tdc_attention(&c, stream));
             if (mode == 1) {     // output projection + residual + LayerNorm of the K query rows in one kernel
                 tdc_xattn_desc x;

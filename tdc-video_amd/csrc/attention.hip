@@ -52,8 +52,13 @@ __global__ __launch_bounds__(256, (QT <= 2 ? 2 : 1)) void attn_kernel(AttnArgs p
     const int q0 = blockIdx.x * (64 * QT) + wave * (16 * QT);
     const int d = p.d;
     const T* Q = (const T*)p.q + b * p.q_bs + h * d;
-    const T* K = (const T*)p.k + b * p.k_bs + h * d;
-    const T* V = (const T*)p.v + b * p.v_bs + h * d;
+    // per-item K / V source and key count (tdc_attn_desc.kv_index / k_len): block-uniform values read once.  With k_len the item
+    // runs exactly what a uniform launch with sk = k_len[b] runs - the same tiles from key 0, the same masked last tile - and the
+    // keys at and beyond k_len[b] are never loaded (row indices are clamped to sk - 1 below).
+    const int kvb = p.kv_index ? p.kv_index[b] : b;
+    const int sk = p.k_len ? p.k_len[b] : p.sk;
+    const T* K = (const T*)p.k + kvb * p.k_bs + h * d;
+    const T* V = (const T*)p.v + kvb * p.v_bs + h * d;
     T* O = (T*)p.o + b * p.o_bs + h * d;
 
     // 8 elements row[c0..c0+7].  Loads are UNCONDITIONAL (address clamped into the row) so that the compiler can keep
@@ -108,7 +113,7 @@ __global__ __launch_bounds__(256, (QT <= 2 ? 2 : 1)) void attn_kernel(AttnArgs p
             int idx = tid + i * 256;
             if (!K_EXACT && idx > KT * NCH - 1) idx = KT * NCH - 1;
             const int key = idx / NCH, c = idx - key * NCH;
-            int kr = kv0 + key; if (kr > p.sk - 1) kr = p.sk - 1;
+            int kr = kv0 + key; if (kr > sk - 1) kr = sk - 1;
             kreg[i] = load8(K + (long long)kr * p.k_rs, c * 8);
         }
 #pragma unroll
@@ -116,7 +121,7 @@ __global__ __launch_bounds__(256, (QT <= 2 ? 2 : 1)) void attn_kernel(AttnArgs p
             int idx = tid + i * 256;
             if (!V_EXACT && idx > KT * VCH - 1) idx = KT * VCH - 1;
             const int key = idx / VCH, c = idx - key * VCH;
-            int kr = kv0 + key; if (kr > p.sk - 1) kr = p.sk - 1;
+            int kr = kv0 + key; if (kr > sk - 1) kr = sk - 1;
             vreg[i] = load8(V + (long long)kr * p.v_rs, c * 8);
         }
     };
@@ -157,7 +162,7 @@ __global__ __launch_bounds__(256, (QT <= 2 ? 2 : 1)) void attn_kernel(AttnArgs p
         for (int dt = 0; dt < NDV; ++dt) o_acc[t][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
 
-    const int ntiles = (p.sk + KT - 1) / KT;
+    const int ntiles = (sk + KT - 1) / KT;
     const f32x4 c4 = {p.scale_log2, p.scale_log2, p.scale_log2, p.scale_log2};
     // one KV tile; PARTIAL (keys beyond sk exist) is only instantiated for the last tile so the steady-state loop
     // carries no mask compares
@@ -196,7 +201,7 @@ __global__ __launch_bounds__(256, (QT <= 2 ? 2 : 1)) void attn_kernel(AttnArgs p
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt) {
                 int kc = kv0 + kt * 16 + g * 4;
-                if (PARTIAL && kc > p.sk - 4) kc = p.sk - 4;          // keys beyond sk are masked below anyway
+                if (PARTIAL && kc > sk - 4) kc = sk - 4;          // keys beyond sk are masked below anyway
                 km[kt] = *(const unsigned*)(p.kmask + b * p.kmask_bs + kc);
             }
         }
@@ -209,7 +214,7 @@ __global__ __launch_bounds__(256, (QT <= 2 ? 2 : 1)) void attn_kernel(AttnArgs p
 #pragma unroll
                 for (int kt = 0; kt < 4; ++kt) {
                     int kc = kv0 + kt * 16;
-                    if (PARTIAL && kc + g * 4 > p.sk - 4) kc = p.sk - 4 - g * 4;
+                    if (PARTIAL && kc + g * 4 > sk - 4) kc = sk - 4 - g * 4;
                     const f32x4 bv = *(const f32x4*)(brow[t] + kc);
                     s[t][kt] = __builtin_elementwise_fma(s[t][kt], c4, gg * bv);
                 }
@@ -226,7 +231,7 @@ __global__ __launch_bounds__(256, (QT <= 2 ? 2 : 1)) void attn_kernel(AttnArgs p
                 for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        if (kv0 + kt * 16 + g * 4 + r >= p.sk) s[t][kt][r] = -INFINITY;
+                        if (kv0 + kt * 16 + g * 4 + r >= sk) s[t][kt][r] = -INFINITY;
             }
             float mx = fmaxf(s[t][0][0], s[t][0][1]);                              // v_max3_f32 chain: 8 issues / 16 values
             mx = __builtin_fmaxf(__builtin_fmaxf(mx, s[t][0][2]), s[t][0][3]);
@@ -384,6 +389,11 @@ extern "C" int tdc_attention(const tdc_attn_desc* d, void* stream) {
                (d->o_bs % 4 == 0) && al(d->q, 16) && al(d->k, 16) && al(d->v, 16) && al(d->o, 8);
     a.bias = d->bias; a.bias_hs = d->bias_hs; a.bias_rs = d->bias_rs; a.gate = d->gate; a.gate_rs = d->gate_rs;
     a.kmask = d->key_mask; a.kmask_bs = d->key_mask_bs;
+    a.k_len = d->k_len; a.kv_index = d->kv_index;
+    if ((a.k_len || a.kv_index) && (a.bias || ((uintptr_t)a.k_len & 3) || ((uintptr_t)a.kv_index & 3))) {
+        fprintf(stderr, "[tdc_hip] tdc_attention: k_len / kv_index exclude the biased form and need 4-byte aligned arrays\n");
+        return TDC_E_BADARG;
+    }
     if (a.kmask && (!a.bias || d->key_mask_bs % 4 != 0 || d->key_mask_bs < d->sk || !al(d->key_mask, 4))) {
         fprintf(stderr, "[tdc_hip] tdc_attention: key_mask needs the biased form, key_mask_bs %% 4 == 0 (>= sk) and a 4-byte aligned base\n");
         return TDC_E_BADARG;

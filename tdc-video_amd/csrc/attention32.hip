@@ -84,8 +84,12 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(AttnArgs p) {
     const int q0 = qblk * (128 * QB) + wave * (32 * QB);
     const int d = p.d;
     const T* Q = (const T*)p.q + b * p.q_bs + h * d;
-    const T* K = (const T*)p.k + b * p.k_bs + h * d;
-    const T* V = (const T*)p.v + b * p.v_bs + h * d;
+    // per-item K / V source and key count (tdc_attn_desc.kv_index / k_len), as in attention.hip: the item runs the tiling of a
+    // uniform launch with sk = k_len[b]; keys at and beyond it are never loaded (row indices clamped to sk - 1)
+    const int kvb = p.kv_index ? p.kv_index[b] : b;
+    const int sk = p.k_len ? p.k_len[b] : p.sk;
+    const T* K = (const T*)p.k + kvb * p.k_bs + h * d;
+    const T* V = (const T*)p.v + kvb * p.v_bs + h * d;
     T* O = (T*)p.o + b * p.o_bs + h * d;
 
     // 8 elements row[c0 .. c0+7], address clamped into the row (head dim % 8 == 0: the launcher's vec_ok)
@@ -123,7 +127,7 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(AttnArgs p) {
             int idx = tid + i * 256;
             if (!K_EXACT && idx > KT32 * NCH - 1) idx = KT32 * NCH - 1;
             const int key = idx / NCH, c = idx - key * NCH;
-            int kr = kv0 + key; if (kr > p.sk - 1) kr = p.sk - 1;
+            int kr = kv0 + key; if (kr > sk - 1) kr = sk - 1;
             kreg[i] = load8(K + (long long)kr * p.k_rs, c * 8);
         }
 #pragma unroll
@@ -131,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(AttnArgs p) {
             int idx = tid + i * 256;
             if (!V_EXACT && idx > KT32 * VCH - 1) idx = KT32 * VCH - 1;
             const int key = idx / VCH, c = idx - key * VCH;
-            int kr = kv0 + key; if (kr > p.sk - 1) kr = p.sk - 1;
+            int kr = kv0 + key; if (kr > sk - 1) kr = sk - 1;
             vreg[i] = load8(V + (long long)kr * p.v_rs, c * 8);
         }
     };
@@ -170,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(AttnArgs p) {
             for (int e = 0; e < 16; ++e) o_acc[qb][db][e] = 0.f;
     }
 
-    const int ntiles = (p.sk + KT32 - 1) / KT32;
+    const int ntiles = (sk + KT32 - 1) / KT32;
     const float c = p.scale_log2;
 
     // NQ = query blocks of this wave that hold at least one row < sq (the first NQ ones), NKB = key blocks of the tile that hold
@@ -217,7 +221,7 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(AttnArgs p) {
                 for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
                     for (int e = 0; e < 16; ++e)
-                        if (kv0 + kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh >= p.sk) s[qb][kb][e] = -INFINITY;
+                        if (kv0 + kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh >= sk) s[qb][kb][e] = -INFINITY;
             }
             float mx = fmaxf(s[qb][0][0], s[qb][0][1]);
 #pragma unroll
@@ -317,7 +321,7 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(AttnArgs p) {
     __syncthreads();
     int nq = (p.sq - q0 + 31) >> 5;                              // wave-uniform
     nq = nq < 0 ? 0 : (nq > QB ? QB : nq);
-    const bool last_two = p.sk - (ntiles - 1) * KT32 > 32;       // the last tile's second key block holds valid keys
+    const bool last_two = sk - (ntiles - 1) * KT32 > 32;       // the last tile's second key block holds valid keys
     auto run = [&](auto nq_c) {
         typedef std::integral_constant<int, 2> two;
         typedef std::integral_constant<int, 1> one;

@@ -16,6 +16,8 @@ struct AttnArgs {
     const float* gate; int gate_rs;
     // key padding mask of the biased form: key k of batch b scores -inf when kmask[b*kmask_bs + k] != 0 (NULL = none)
     const unsigned char* kmask; long long kmask_bs;
+    // per-item key count / per-item K, V source (tdc_attn_desc.k_len / kv_index; NULL = sk for every item / item b reads b)
+    const int* k_len; const int* kv_index;
 };
 
 // attention32.hip: returns -1 when the 32x32 form does not apply (bias, short sequences, other head dims)

@@ -232,6 +232,8 @@ struct QeArgs {
     const float* gamma; const float* beta; float eps;
     float* h32; void* h16; int ld;
     int F, K, cols;
+    // prompt table (tdc_qembed_desc.frame_prompt / prompt_len / ids_ld; NULL = one prompt of Lt ids for every frame)
+    const int* frame_prompt; const int* prompt_len; int ids_ld;
 };
 
 template <class T, int NV>
@@ -241,6 +243,18 @@ __global__ __launch_bounds__(256) void qembed_kernel(QeArgs p) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= p.F * S) return;
     const int f = row / S, s = row - f * S;
+    const int* ids = p.ids;
+    if (p.frame_prompt && s >= p.K) {       // wave-uniform: one row per wave
+        const int pr = p.frame_prompt[f];
+        ids += (long long)pr * p.ids_ld;
+        if (s - p.K >= p.prompt_len[pr]) {  // padding row behind this frame's prompt: a whole zero row, no id is read
+            for (int c = lane; c < p.ld; c += 64) {
+                p.h32[(long long)row * p.ld + c] = 0.f;
+                ((T*)p.h16)[(long long)row * p.ld + c] = (T)0.f;
+            }
+            return;
+        }
+    }
     float v[NV];
     float sum = 0.f;
 #pragma unroll
@@ -252,7 +266,7 @@ __global__ __launch_bounds__(256) void qembed_kernel(QeArgs p) {
                 a = (float)((const T*)p.query)[((long long)p.qsrc[f] * p.K + s) * p.ldq + c];
             } else {
                 int t = s - p.K;
-                a = p.word[(long long)p.ids[t] * p.ldw + c] + p.pos[(long long)t * p.ldw + c];
+                a = p.word[(long long)ids[t] * p.ldw + c] + p.pos[(long long)t * p.ldw + c];
             }
         }
         v[i] = a;
@@ -351,6 +365,9 @@ extern "C" int tdc_qformer_embed(const tdc_qembed_desc* d, void* stream) {
     a.gamma = d->gamma; a.beta = d->beta; a.eps = d->eps;
     a.h32 = d->h32; a.h16 = d->h16; a.ld = d->ld;
     a.F = d->F; a.K = d->K; a.cols = d->cols;
+    a.frame_prompt = d->frame_prompt; a.prompt_len = d->prompt_len; a.ids_ld = d->ids_ld;
+    if (d->frame_prompt && d->Lt > 0 && (!d->prompt_len || d->ids_ld < d->Lt)) return TDC_E_BADARG;
+    if (d->Lt <= 0) a.frame_prompt = nullptr;     // no text rows: the table is not read
     const int nv = (d->ld + 63) / 64;
     const int rows = d->F * (d->K + d->Lt);
     dim3 grid((rows + 3) / 4), block(256);

@@ -45,7 +45,8 @@ class AttnDesc(C.Structure):
                 ("scale", C.c_float), ("dtype", C.c_int),
                 ("bias", C.c_void_p), ("bias_hs", C.c_longlong), ("bias_rs", C.c_int),
                 ("gate", C.c_void_p), ("gate_rs", C.c_int),
-                ("key_mask", C.c_void_p), ("key_mask_bs", C.c_longlong), ("form", C.c_int)]
+                ("key_mask", C.c_void_p), ("key_mask_bs", C.c_longlong), ("form", C.c_int),
+                ("k_len", C.c_void_p), ("kv_index", C.c_void_p)]
 
 
 class GatherTables(C.Structure):
@@ -64,7 +65,8 @@ class QEmbedDesc(C.Structure):
                 ("word", C.c_void_p), ("pos", C.c_void_p), ("ldw", C.c_int), ("ids", C.c_void_p), ("Lt", C.c_int),
                 ("gamma", C.c_void_p), ("beta", C.c_void_p), ("eps", C.c_float),
                 ("h32", C.c_void_p), ("h16", C.c_void_p), ("ld", C.c_int),
-                ("F", C.c_int), ("K", C.c_int), ("cols", C.c_int), ("dtype", C.c_int)]
+                ("F", C.c_int), ("K", C.c_int), ("cols", C.c_int), ("dtype", C.c_int),
+                ("frame_prompt", C.c_void_p), ("prompt_len", C.c_void_p), ("ids_ld", C.c_int)]
 
 
 class Lin(C.Structure):
@@ -116,12 +118,18 @@ class QformerLayer(C.Structure):
                 ("cross_q_tiled", C.c_void_p), ("cross_out_tiled", C.c_void_p)]
 
 
+class QformerPrompts(C.Structure):
+    _fields_ = [("n_prompts", C.c_int), ("enc_frames", C.c_int), ("kv_src", C.c_void_p), ("frame_prompt", C.c_void_p),
+                ("prompt_len", C.c_void_p), ("self_len", C.c_void_p)]
+
+
 class QformerModel(C.Structure):
     _fields_ = [("dtype", C.c_int), ("dim", C.c_int), ("heads", C.c_int), ("n_layers", C.c_int), ("H", C.c_int),
                 ("eps", C.c_float), ("word", C.c_void_p), ("pos", C.c_void_p), ("ldw", C.c_int),
                 ("emb_ln_g", C.c_void_p), ("emb_ln_b", C.c_void_p), ("cross_kv", Lin), ("vision_proj", Lin),
                 ("layers_host", C.POINTER(QformerLayer)),
-                ("cross_k", Lin), ("cross_v", Lin), ("cross_bv", C.c_void_p), ("xattn_mode", C.c_int)]
+                ("cross_k", Lin), ("cross_v", Lin), ("cross_bv", C.c_void_p), ("xattn_mode", C.c_int),
+                ("prompts", C.POINTER(QformerPrompts))]
 
 
 class XattnDesc(C.Structure):

@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import lib as L
 from . import segment as seg
-from .pipeline import VideoEncoder, batch_groups, encode_image_cached, frame_indices
+from .pipeline import VideoEncoder, batch_groups, encode_image_cached, frame_indices, same_video_key
 
 IGNORE_INDEX = -100        # tdc/constants.py
 IMAGE_TOKEN_INDEX = -200
@@ -489,6 +489,33 @@ class CambrianMetaModel:
             return 0
         return n
 
+    def tdc_batch_prompts(self):
+        """`config.tdc_batch_prompts`: the most prompts of one compressor pass - the samples of one call (bsz > 1) that carry the
+        same video (equal engine.fingerprint of their a1-selected pixels, equal image_size, equal audio) run through
+        VideoEncoder.encode_video_prompts, bit for bit the per-sample results.  0 / absent: off, every sample on its own.  Set
+        together with `config.tdc_shard_frames` or `config.tdc_batch_frames` it raises: the paths do not compose."""
+        n = getattr(self.config, "tdc_batch_prompts", None)
+        if n is None:
+            return 0
+        if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+            raise ValueError("config.tdc_batch_prompts must be a prompt count (a non-negative int; 0 / absent = off), got %r"
+                             % (n,))
+        if n:
+            for other in ("tdc_shard_frames", "tdc_batch_frames"):
+                if getattr(self.config, other, None):
+                    raise ValueError("config.tdc_batch_prompts and config.%s cannot be set together" % other)
+        return n
+
+    def tdc_prompt_pad_fraction(self):
+        """`config.tdc_prompt_pad_fraction`: the share of a prompt group's rows that may be padding (pipeline.prompt_groups);
+        absent: 1/4."""
+        v = getattr(self.config, "tdc_prompt_pad_fraction", None)
+        if v is None:
+            return 0.25
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v <= 1:
+            raise ValueError("config.tdc_prompt_pad_fraction must be a fraction in [0, 1] (absent = 0.25), got %r" % (v,))
+        return float(v)
+
     def tdc_side_stream(self, frames_per_rank):
         """engine.two_streams (pipeline.start_side_tower): the config's choice, by default on at <= 128 frames per rank"""
         ts = getattr(self.config, "tdc_two_streams", None)
@@ -608,6 +635,8 @@ class CambrianMetaForCausalLM(ABC):
         eng = model.tdc_engine()
         vcache = model.tdc_video_cache()             # config.tdc_video_cache_bytes (validated even when no video comes)
         batch_frames = model.tdc_batch_frames()      # config.tdc_batch_frames (0: every sample on its own)
+        batch_prompts = model.tdc_batch_prompts()    # config.tdc_batch_prompts (0: every sample on its own)
+        pad_fraction = model.tdc_prompt_pad_fraction()
         cfgd = self._cfg()
         K = cfgd.get("context_token_num", 16)
         H = model.config.hidden_size
@@ -727,7 +756,35 @@ class CambrianMetaForCausalLM(ABC):
             vis = eng.encode_batch(samples, frame_cap=model.tdc_frame_cap(), infos=infos)
             return [(v, f["splice"] is not None, info["final_size"]) for v, f, info in zip(vis, fs, infos)]
 
-        if not batch_frames or bsz == 1:
+        def encode_prompts(fs):
+            """config.tdc_batch_prompts: the samples fs carry ONE video (same_video_key) - the towers and the connector once, one
+            compressor pass per group of prompts (VideoEncoder.encode_video_prompts) -> what encode_one returns for each, bit
+            for bit"""
+            f0 = fs[0]
+            infos = [{} for _ in fs]
+            qs = [dict(budget_text_len=f["btl"], n_text_tokens=f["n_text"], prompt_ids=f["prompt_ids"], splice=f["splice"])
+                  for f in fs]
+            eng.two_streams = model.tdc_side_stream(min(f0["vid_s"].shape[0], f0["cap"]))
+            vis = eng.encode_video_prompts(f0["vid_s"].to(eng.dev), f0["vid_d"].to(eng.dev), tuple(image_sizes[f0["i"]]), qs,
+                                           audio=f0["audio"], frame_cap=f0["cap"], video_index=f0["vindex"], infos=infos,
+                                           cache=vcache, max_prompts=batch_prompts, pad_fraction=pad_fraction)
+            return [(v, f["splice"] is not None, info["final_size"]) for v, f, info in zip(vis, fs, infos)]
+
+        if batch_prompts and bsz > 1 and is_video:
+            # config.tdc_batch_prompts: every sample's host-side facts first, then the samples that carry the same video (in
+            # order of its first sample) through encode_prompts; a video that only one sample carries runs encode_one
+            fs = [facts(i) for i in range(bsz)]
+            same = {}
+            for f in fs:
+                key = same_video_key(eng, f["vid_s"], f["vid_d"], tuple(image_sizes[f["i"]]), f["btl"], f["cap"], f["audio"],
+                                     f["vindex"])
+                same.setdefault(key, []).append(f)
+            results = [None] * bsz
+            for members in same.values():
+                rs = [encode_one(members[0])] if len(members) == 1 else encode_prompts(members)
+                for f, r in zip(members, rs):
+                    results[f["i"]] = r
+        elif not batch_frames or bsz == 1:
             results = (encode_one(facts(i)) for i in range(bsz))
         else:
             # config.tdc_batch_frames: every sample's host-side facts first (the same exceptions as the loop above, raised

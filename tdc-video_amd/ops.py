@@ -270,22 +270,50 @@ def layernorm(x, gamma, beta, eps, cols, dtype, y16=None, y32=None, add=None, ad
     return y16, y32
 
 
+def index_tensor(values, lo, hi, device, what):
+    """a HOST list of ints -> device int32 tensor, every entry range-checked against [lo, hi) first: the kernels trust their
+    index arrays, and a faulting kernel can take the whole GPU node down."""
+    vals = [int(v) for v in values]
+    if not vals or min(vals) < lo or max(vals) >= hi:
+        raise ValueError("%s: entries must lie in [%d, %d), got %s" % (what, lo, hi, vals[:16]))
+    return torch.tensor(vals, dtype=torch.int32, device=device)
+
+
 def attention(q, k, v, out, batch, heads, head_dim, sq, sk, scale, q_bs, k_bs, v_bs, o_bs, bias=None, gate=None,
-              key_mask=None, form=0):
+              key_mask=None, form=0, k_len=None, kv_index=None):
     """q/k/v/out: 2-D views [tokens, ld] whose element (b, s, h, c) sits at base + b*bs + s*stride(0) + h*head_dim + c.
     Tensors may be column-offset views of a fused QKV buffer.  bias fp32 [heads, sq, sk] + gate fp32 [batch*sq, >=heads]
     add gate[b*sq+q, h] * bias[h, q, k] to the scaled scores (BEATs gated relative position bias); key_mask uint8 / bool
-    [batch, sk] (biased form only): non-zero = key excluded from the softmax (key padding mask)."""
+    [batch, sk] (biased form only): non-zero = key excluded from the softmax (key padding mask).
+    k_len / kv_index (tdc_attn_desc): HOST lists of `batch` ints - item b attends to its first k_len[b] <= sk keys / reads the
+    K, V of slot kv_index[b] (k and v then hold max(kv_index) + 1 or more slots); range-checked here, then uploaded."""
+    if k_len is not None or kv_index is not None:
+        if bias is not None:
+            raise ValueError("attention: k_len / kv_index exclude the biased form")
+        if k_len is not None:
+            assert len(k_len) == batch
+            if form == 0 and sq >= 256 and sk >= 64 and min(int(v_) for v_ in k_len) < 64:
+                raise ValueError("attention: k_len below 64 at sq >= 256 would not run the kernel form a uniform launch picks")
+            k_len = index_tensor(k_len, 1, sk + 1, q.device, "attention k_len")
+        if kv_index is not None:
+            assert len(kv_index) == batch
     for t in (q, k, v, out):
         assert t.is_cuda and t.dim() == 2 and t.stride(1) == 1
     assert q.dtype == k.dtype == v.dtype == out.dtype
     assert heads * head_dim <= q.shape[1] and heads * head_dim <= out.shape[1]
 
-    def last(t, bs, s):
-        return (batch - 1) * bs + (s - 1) * t.stride(0) + heads * head_dim
-    for t, bs, s in ((q, q_bs, sq), (k, k_bs, sk), (v, v_bs, sk), (out, o_bs, sq)):
+    kv_slots = batch
+    if kv_index is not None:
+        span_k = min((t.shape[0] - 1) * t.stride(0) + t.shape[1] for t in (k, v))
+        assert k_bs > 0 and v_bs > 0
+        kv_slots = min((span_k - (sk - 1) * t.stride(0) - heads * head_dim) // bs + 1 for t, bs in ((k, k_bs), (v, v_bs)))
+        kv_index = index_tensor(kv_index, 0, max(kv_slots, 0), q.device, "attention kv_index")
+
+    def last(t, bs, s, n):
+        return (n - 1) * bs + (s - 1) * t.stride(0) + heads * head_dim
+    for t, bs, s, n in ((q, q_bs, sq, batch), (k, k_bs, sk, kv_slots), (v, v_bs, sk, kv_slots), (out, o_bs, sq, batch)):
         span = (t.shape[0] - 1) * t.stride(0) + t.shape[1]
-        assert last(t, bs, s) <= span, "attention view out of range"
+        assert last(t, bs, s, n) <= span, "attention view out of range"
     d = L.AttnDesc()
     d.q, d.k, d.v, d.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
     d.q_bs, d.k_bs, d.v_bs, d.o_bs = q_bs, k_bs, v_bs, o_bs
@@ -304,6 +332,10 @@ def attention(q, k, v, out, batch, heads, head_dim, sq, sk, scale, q_bs, k_bs, v
         assert key_mask.is_cuda and key_mask.dtype in (torch.uint8, torch.bool) and key_mask.is_contiguous()
         assert tuple(key_mask.shape) == (batch, sk)
         d.key_mask, d.key_mask_bs = key_mask.data_ptr(), sk
+    if k_len is not None:
+        d.k_len = k_len.data_ptr()
+    if kv_index is not None:
+        d.kv_index = kv_index.data_ptr()
     L.check(L.load().tdc_attention(C.byref(d), _stream()), "tdc_attention")
     return out
 
@@ -518,9 +550,32 @@ def sva_attention(q, kv_list, mask, T, side, r, dim, heads, out=None):
     return out
 
 
-def qformer_embed(query, qsrc, word, pos, ids, gamma, beta, eps, F, K, cols, dtype):
+def prompt_table(prompts, vocab, max_len, device, pad_id=0):
+    """HOST id lists of P prompts -> (ids [P, Lmax] device int32 padded with pad_id, prompt_len [P] device int32, Lmax); every id
+    is range-checked against the vocabulary here (the padding entries are never read by the kernel: any pad_id will do)."""
+    rows = [[int(v) for v in (p or [])] for p in prompts]
+    Lmax = max(len(r) for r in rows)
+    assert Lmax <= max_len, "prompt longer than the position table"
+    for r in rows:
+        if r and (min(r) < 0 or max(r) >= vocab):
+            raise ValueError("prompt id out of range [0, %d)" % vocab)
+    tab = torch.tensor([r + [int(pad_id)] * (Lmax - len(r)) for r in rows], dtype=torch.int32, device=device).reshape(len(rows), Lmax)
+    return tab, torch.tensor([len(r) for r in rows], dtype=torch.int32, device=device), Lmax
+
+
+def qformer_embed(query, qsrc, word, pos, ids, gamma, beta, eps, F, K, cols, dtype, frame_prompt=None, pad_id=0):
+    """frame_prompt (HOST list of F ints): the prompt-table form of tdc_qembed_desc - `ids` is then a HOST list of P id lists,
+    frame f embeds prompt frame_prompt[f] and every frame occupies K + Lmax rows (zero rows behind a shorter prompt)."""
     _chk2d(query, "query")
-    Lt = 0 if ids is None else ids.numel()
+    fp = plen = None
+    if frame_prompt is not None:
+        assert len(frame_prompt) == F
+        fp = index_tensor(frame_prompt, 0, len(ids), query.device, "qformer_embed frame_prompt")
+        ids, plen, Lt = prompt_table(ids, word.shape[0], pos.shape[0], query.device, pad_id)
+        if Lt == 0:
+            ids = fp = plen = None
+    else:
+        Lt = 0 if ids is None else ids.numel()
     ld = pad64(cols)
     rows = F * (K + Lt)
     h32 = torch.empty(rows, ld, device=query.device, dtype=torch.float32)
@@ -530,8 +585,10 @@ def qformer_embed(query, qsrc, word, pos, ids, gamma, beta, eps, F, K, cols, dty
     d.query, d.ldq, d.qsrc = query.data_ptr(), query.stride(0), qsrc.data_ptr()
     if Lt:
         assert ids.dtype == torch.int32 and word.dtype == torch.float32 and pos.dtype == torch.float32
-        assert int(ids.max()) < word.shape[0] and Lt <= pos.shape[0] and word.stride(0) == pos.stride(0)
+        assert (fp is not None or int(ids.max()) < word.shape[0]) and Lt <= pos.shape[0] and word.stride(0) == pos.stride(0)
         d.word, d.pos, d.ldw, d.ids = word.data_ptr(), pos.data_ptr(), word.stride(0), ids.data_ptr()
+        if fp is not None:
+            d.frame_prompt, d.prompt_len, d.ids_ld = fp.data_ptr(), plen.data_ptr(), ids.stride(0)
     d.Lt = Lt
     d.gamma, d.beta, d.eps = gamma.data_ptr(), beta.data_ptr(), eps
     d.h32, d.h16, d.ld = h32.data_ptr(), h16.data_ptr(), ld

@@ -572,19 +572,35 @@ class VideoEncoder:
         return X, sizes
 
     # ------------------------------------------------------------------------------------------------ a11-a19
-    def qformer(self, enc, F, Nenc, query, qsrc, prompt_ids):
+    def qformer(self, enc, F, Nenc, query, qsrc, prompt_ids, multi=None):
         """Batched Q-Former (tdc/Qformer.py:804-965) over F compressed frames.
         enc [F*Nenc, Hp] 16-bit; query [nC*K, Dq_pad] (query_proj output per chunk); qsrc int32 [F] chunk of frame.
-        Returns last hidden state rows of the K query tokens as the combined buffer h16 [F*S, Dq_pad] and S."""
+        Returns last hidden state rows of the K query tokens as the combined buffer h16 [F*S, Dq_pad] and S.
+        multi (the multi-prompt form): dict of HOST lists kv_src [F], frame_prompt [F] and the int
+        enc_frames = U; prompt_ids is then a list of P id lists, F counts virtual frames, enc holds U frames and S = K + Lmax."""
         qf, dt = self.c.qformer, self.dtype
         Dq = qf.dim
         K = self.K
         heads = self.qheads
         hd = Dq // heads
-        ids = self._prompt_tensor(prompt_ids)
-        Lt = 0 if ids is None else ids.numel()
+        U, self_len, kv_src = F, None, None
+        if multi is not None:
+            if not self.multi_prompt_ok(Nenc):                    # refused before any launch
+                raise ValueError("the multi-prompt Q-Former runs xattn_mode 0 / 1 only")
+            U = int(multi["enc_frames"])
+            assert enc.shape[0] >= U * Nenc
+            lens = [len(p or []) for p in prompt_ids]
+            Lt = max(lens)
+            ops.index_tensor(multi["kv_src"], 0, U, "cpu", "qformer kv_src")
+            kv_src = [int(v) for v in multi["kv_src"]]
+            h32, h16 = ops.qformer_embed(query, qsrc, qf.word, qf.pos, prompt_ids, qf.emb_ln[0], qf.emb_ln[1], 1e-12, F, K, Dq,
+                                         dt, frame_prompt=multi["frame_prompt"])
+            self_len = [K + lens[int(p)] for p in multi["frame_prompt"]] if Lt else None
+        else:
+            ids = self._prompt_tensor(prompt_ids)
+            Lt = 0 if ids is None else ids.numel()
+            h32, h16 = ops.qformer_embed(query, qsrc, qf.word, qf.pos, ids, qf.emb_ln[0], qf.emb_ln[1], 1e-12, F, K, Dq, dt)
         S = K + Lt
-        h32, h16 = ops.qformer_embed(query, qsrc, qf.word, qf.pos, ids, qf.emb_ln[0], qf.emb_ln[1], 1e-12, F, K, Dq, dt)
         # the cross-attention block (SURVEY D7): fused form = key GEMM + transposed value GEMM + one kernel per cross layer
         mode = int(getattr(self, "xattn_mode", 1)) if qf.cross_k is not None else 0
         fused = mode >= 2 and ops.qformer_xattn_supported(Dq, heads, K, Nenc)
@@ -597,7 +613,7 @@ class VideoEncoder:
             vt_all = torch.empty(qf.cross_v.w.shape[0], pad64(F * Nenc + 4), device=self.dev, dtype=dt)   # ldvt >= round_up(F*Nenc, 8)
             ops.gemm(qf.cross_v.w, enc[:F * Nenc], out=vt_all, c_pad8=True)   # V^T = Wv enc^T: [n_cross*Dq, F*Nenc]
         else:
-            kv_all = ops.gemm(enc, qf.cross_kv.w, qf.cross_kv.b)              # [F*Nenc, n_cross*2*Dq]
+            kv_all = ops.gemm(enc, qf.cross_kv.w, qf.cross_kv.b, M=U * Nenc)  # [F*Nenc, n_cross*2*Dq] (multi: U frames)
         ops.profile_tag(0)
         Dp = h16.shape[1]
         ctx = torch.zeros(F * S, Dp, device=self.dev, dtype=dt)
@@ -612,7 +628,7 @@ class VideoEncoder:
             qkv = ops.gemm(h16, Lr.qkv.w, Lr.qkv.b)
             ld = qkv.stride(0)
             ops.attention(qkv[:, 0:Dq], qkv[:, Dq:2 * Dq], qkv[:, 2 * Dq:3 * Dq], ctx, F, heads, hd, S, S, scale,
-                          S * ld, S * ld, S * ld, S * ctx.stride(0))
+                          S * ld, S * ld, S * ld, S * ctx.stride(0), k_len=self_len)
             ops.gemm(ctx, Lr.attn_out.w, Lr.attn_out.b, res=h32, out=t32, out_f32=True)
             ops.layernorm(t32, Lr.attn_ln[0], Lr.attn_ln[1], 1e-12, Dq, dt, y16=h16, y32=h32)
             ops.profile_tag(L.PROF_TAG_XATTN_BLOCK)
@@ -628,7 +644,7 @@ class VideoEncoder:
                 vv = kv_all[:, j * 2 * Dq + Dq: (j + 1) * 2 * Dq]
                 ldk = kv_all.stride(0)
                 ops.attention(cq[:, :Dq], kk, vv, ctx_q, F, heads, hd, K, Nenc, scale, K * cq.stride(0), Nenc * ldk,
-                              Nenc * ldk, K * ctx_q.stride(0))
+                              Nenc * ldk, K * ctx_q.stride(0), kv_index=kv_src)
                 if out_fused:
                     # the residual of this kernel and of the query FFN behind it is the 16-bit hidden state (the reference's
                     # half-precision arithmetic, tdc/Qformer.py:285-289,335-341): the fp32 copy of the query rows is neither
@@ -816,13 +832,38 @@ class VideoEncoder:
             hit = self._tables[key] = torch.tensor(key[1], dtype=torch.int32, device=self.dev)
         return hit
 
-    def _compress_native(self, enc, F, Nf, qtable, qs, prompt_ids):
+    def _compress_native(self, enc, F, Nf, qtable, qs, prompt_ids, multi=None):
         import ctypes as C
         m = self._qformer_struct()[0]
-        ids = self._prompt_tensor(prompt_ids)
-        Lt = 0 if ids is None else ids.numel()
         K = self.K
         assert qs.dtype == torch.int32 and qs.numel() >= F        # value range checked on the host list (compress_frames)
+        if multi is not None:
+            # the multi-prompt form (tdc_qformer_prompts): a copy of the model struct carries the block, the cached one stays as is
+            qf = self.c.qformer
+            U = int(multi["enc_frames"])
+            ids, plen, Lt = ops.prompt_table(prompt_ids, qf.word.shape[0], qf.pos.shape[0], self.dev)
+            lens = [len(p or []) for p in prompt_ids]
+            assert len(multi["kv_src"]) == F and len(multi["frame_prompt"]) == F and U >= 1
+            pr = L.QformerPrompts()
+            pr.n_prompts, pr.enc_frames = len(prompt_ids), U
+            kv_t = ops.index_tensor(multi["kv_src"], 0, U, self.dev, "kv_src")
+            fp_t = ops.index_tensor(multi["frame_prompt"], 0, len(prompt_ids), self.dev, "frame_prompt")
+            sl_t = ops.index_tensor([K + lens[int(p)] for p in multi["frame_prompt"]], K, K + Lt + 1, self.dev, "self_len")
+            pr.kv_src, pr.frame_prompt, pr.prompt_len, pr.self_len = kv_t.data_ptr(), fp_t.data_ptr(), plen.data_ptr(), \
+                sl_t.data_ptr()
+            mm = L.QformerModel()
+            C.pointer(mm)[0] = m
+            mm.prompts = C.pointer(pr)
+            assert enc.shape[0] >= U * Nf and enc.shape[1] >= m.cross_kv.k and qtable.shape[1] >= pad64(m.dim)
+            lib = L.load()
+            ws = self._workspace("_qf_ws", lib.tdc_qformer_workspace_bytes(C.byref(mm), F, K, Lt, Nf))
+            out = torch.empty(F * K, pad64(self.c.H), device=self.dev, dtype=self.dtype)
+            L.check(lib.tdc_qformer_fwd(C.byref(mm), ops._ptr(enc), enc.stride(0), F, Nf, ops._ptr(qtable), qtable.stride(0),
+                                        ops._ptr(qs), ops._ptr(ids if Lt else None), Lt, K, ops._ptr(out), out.stride(0),
+                                        ops._ptr(ws), ws.numel(), ops._stream()), "tdc_qformer_fwd")
+            return out
+        ids = self._prompt_tensor(prompt_ids)
+        Lt = 0 if ids is None else ids.numel()
         assert enc.shape[0] >= F * Nf and enc.shape[1] >= m.cross_kv.k and qtable.shape[1] >= pad64(m.dim)
         lib = L.load()
         ws = self._workspace("_qf_ws", lib.tdc_qformer_workspace_bytes(C.byref(m), F, K, Lt, Nf))
@@ -832,25 +873,40 @@ class VideoEncoder:
                                     ws.numel(), ops._stream()), "tdc_qformer_fwd")
         return out
 
-    def compress_frames(self, Xf, Nf, frame_rows, qtable, qsrc, prompt_ids, keep=None):
-        """a13-a18 for the frames `frame_rows` of Xf: Q-Former against queries qtable[qsrc[f]] -> [F*K, >=H] unit rows."""
+    def multi_prompt_ok(self, Nf):
+        """whether compress_frames takes the multi-prompt form here: not under the whole-block cross-attention kernel
+        (xattn_mode 2 where its shape support holds) - the callers then run one pass per prompt"""
+        qf = self.c.qformer
+        return not (int(getattr(self, "xattn_mode", 1)) >= 2 and qf.cross_k is not None and
+                    ops.qformer_xattn_supported(qf.dim, self.qheads, self.K, Nf))
+
+    def compress_frames(self, Xf, Nf, frame_rows, qtable, qsrc, prompt_ids, keep=None, multi=None):
+        """a13-a18 for the frames `frame_rows` of Xf: Q-Former against queries qtable[qsrc[f]] -> [F*K, >=H] unit rows.
+        multi = dict(kv_src, frame_prompt) (prompt_maps): frame_rows are the U DISTINCT frames, gathered and projected to K/V
+        once; qsrc / kv_src / frame_prompt have one entry per virtual frame, prompt_ids is the list of the prompts' id lists;
+        -> [F*K, >=H] in virtual-frame order, each row block bit for bit that of the prompt's own call."""
         c, dev = self.c, self.dev
         K, H = self.K, c.H
-        F = len(frame_rows)
+        U = len(frame_rows)
+        F = U if multi is None else len(qsrc)
         Hp = Xf.shape[1]
         assert F == len(qsrc) and (max(qsrc) + 1) * K <= qtable.shape[0] and min(qsrc) >= 0
         assert min(frame_rows) >= 0 and (max(frame_rows) + 1) * Nf <= Xf.shape[0]
         fr = torch.tensor(frame_rows, dtype=torch.int32, device=dev)
-        enc_idx = torch.zeros(F * Nf, 2, dtype=torch.int32, device=dev)
+        enc_idx = torch.zeros(U * Nf, 2, dtype=torch.int32, device=dev)
         enc_idx[:, 1] = (fr[:, None] * Nf + torch.arange(Nf, dtype=torch.int32, device=dev)[None, :]).reshape(-1)
-        enc = ops.gather_rows([Xf], enc_idx, F * Nf, Hp, validated=True)      # frame_rows range-checked above
+        enc = ops.gather_rows([Xf], enc_idx, U * Nf, Hp, validated=True)      # frame_rows range-checked above
         qs = torch.tensor(qsrc, dtype=torch.int32, device=dev)
+        if multi is not None:
+            if not self.multi_prompt_ok(Nf):
+                raise ValueError("compress_frames: the multi-prompt form runs xattn_mode 0 / 1 only (multi_prompt_ok)")
+            multi = dict(multi, enc_frames=U)
         if getattr(self, "native_qformer", True):
-            comp = self._compress_native(enc, F, Nf, qtable, qs, prompt_ids)
+            comp = self._compress_native(enc, F, Nf, qtable, qs, prompt_ids, multi)
             if keep is not None:
                 keep.update(compressed=comp)
             return comp
-        h16, S = self.qformer(enc, F, Nf, qtable, qs, prompt_ids)
+        h16, S = self.qformer(enc, F, Nf, qtable, qs, prompt_ids, multi)
         comp = ops.gemm(h16, c.vision_proj.w, c.vision_proj.b, M=F * K, a_map=(K, S, 0, 1))
         ops.l2_normalize(comp, F * K, H)
         if keep is not None:
@@ -916,6 +972,13 @@ class VideoEncoder:
         return encode_video_with(self, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids,
                                  audio, frame_cap, keep, splice, video_index, info)
 
+    def encode_video_prompts(self, px_siglip, px_dino, image_size, prompts, audio=None, frame_cap=224, video_index=None,
+                             infos=None, cache=None, max_prompts=8, pad_fraction=0.25):
+        """Several prompts about ONE video: prompts = dicts of budget_text_len, n_text_tokens, prompt_ids, optional splice
+        -> one result per prompt, bit for bit what encode_video returns for it (encode_video_prompts_with)."""
+        return encode_video_prompts_with(self, px_siglip, px_dino, image_size, prompts, audio, frame_cap, video_index, infos,
+                                         cache, max_prompts, pad_fraction)
+
     def encode_batch(self, samples, frame_cap=224, infos=None):
         """Several videos / single images in one tower and connector pass: samples = dicts of encode_video's arguments
         (px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio, video_index, splice) plus
@@ -948,6 +1011,11 @@ def text_prompt(cfg, prompt_ids):
 def compress_with(e, X, T, N, seg_indices, prompt_ids, max_visual_len, audio=None, keep=None, splice=None, info=None):
     Xf, Nf = e.with_audio(X, T, N, audio)
     plan, learned = emission_plan(e, T, Nf, seg_indices, max_visual_len)
+    return compress_planned(e, Xf, N, Nf, plan, learned, prompt_ids, keep, splice, info)
+
+
+def compress_planned(e, Xf, N, Nf, plan, learned, prompt_ids, keep=None, splice=None, info=None):
+    """compress_with after its planning: one prompt's Q-Former pass and emission over the rows Xf (with_audio) by `plan`"""
     comp = None
     if plan["comp_frames"]:
         if learned:
@@ -964,6 +1032,173 @@ def compress_with(e, X, T, N, seg_indices, prompt_ids, max_visual_len, audio=Non
     if splice is not None:
         return e.emit(Xf, comp, pairs, splice)
     return e.emit(Xf, comp, pairs)
+
+
+# ---- several prompts about one video in one compressor pass ------------------------------------------
+MULTI_PROMPT_MAX_ROWS = 255     # K + Lmax of a group: below the 256 query rows from which tdc_attention's AUTO form changes kernels
+
+
+def prompt_groups(selections, text_lens, frames, K, max_prompts, pad_fraction=0.25, max_rows=MULTI_PROMPT_MAX_ROWS):
+    """`config.tdc_batch_prompts`: prompts p = 0 .. P-1 grouped greedily in call order.  A prompt joins the open group of its
+    a1 selection (selections[p], any hashable) while the group holds fewer than max_prompts, its frame stride K + Lmax stays
+    within max_rows, and its padding rows sum_p (Lmax - text_lens[p]) * frames[p] stay within pad_fraction of its
+    sum_p (K + Lmax) * frames[p] rows; otherwise that group is closed and the prompt opens a new one.  -> lists of prompt
+    indices ordered by their first member; a group of one runs the single-prompt path (compress_with)."""
+    if max_prompts < 1:
+        raise ValueError("max_prompts must be >= 1")
+    groups, open_of = [], {}
+    for p, key in enumerate(selections):
+        g = open_of.get(key)
+        if g is not None and len(g) < max_prompts:
+            members = g + [p]
+            Lmax = max(text_lens[i] for i in members)
+            pad = sum((Lmax - text_lens[i]) * frames[i] for i in members)
+            rows = sum((K + Lmax) * frames[i] for i in members)
+            if K + Lmax <= max_rows and pad <= pad_fraction * rows:
+                g.append(p)
+                continue
+        g = [p]
+        groups.append(g)
+        open_of[key] = g
+    return groups
+
+
+def prompt_maps(plans, learned=False):
+    """The index maps of one group (the prompts' seg.emit_plan Plans over ONE video): the distinct compressed frames
+    `enc_frames` and distinct key frames `key_frames` (both ascending), and per VIRTUAL frame - the compressed frames of prompt
+    0, then prompt 1, ... - kv_src (position of its frame in enc_frames), qsrc (position of its chunk's key frame in
+    key_frames; 0 with the shared learned query block), frame_prompt; offsets[p] = first virtual frame of prompt p."""
+    enc_frames = sorted({f for pl in plans for f in pl["comp_frames"]})
+    key_frames = sorted({pl["key_frames"][c] for pl in plans for c in pl["comp_chunk"]})
+    upos = {f: i for i, f in enumerate(enc_frames)}
+    kpos = {f: i for i, f in enumerate(key_frames)}
+    kv_src, qsrc, frame_prompt, offsets = [], [], [], []
+    for p, pl in enumerate(plans):
+        offsets.append(len(kv_src))
+        for f, c in zip(pl["comp_frames"], pl["comp_chunk"]):
+            kv_src.append(upos[f])
+            qsrc.append(0 if learned else kpos[pl["key_frames"][c]])
+            frame_prompt.append(p)
+    offsets.append(len(kv_src))
+    return dict(enc_frames=enc_frames, key_frames=key_frames, kv_src=kv_src, qsrc=qsrc, frame_prompt=frame_prompt,
+                offsets=offsets)
+
+
+def compress_many_with(e, X, T, N, seg_indices, prompts, audio=None, infos=None, max_prompts=8, pad_fraction=0.25):
+    """a11-a19 for several prompts over ONE video's connector rows X (audio: the a20 tokens, as compress_with takes them):
+    prompts = dicts of n_text_tokens, prompt_ids, optional splice -> one emitted tensor per prompt, bit for bit compress_with's.
+    Per group (prompt_groups) the distinct compressed frames are gathered and projected to K/V once, the distinct key frames
+    pooled once, and ONE Q-Former pass runs over the prompts' virtual frames (prompt_maps); a group of one, and every group on
+    an engine whose compress_frames cannot take the form (multi_prompt_ok), runs compress_with."""
+    cfg = getattr(e, "cfg", {})
+    K = e.K
+    P = len(prompts)
+    pids = [text_prompt(cfg, p["prompt_ids"]) for p in prompts]
+    Xf, Nf = e.with_audio(X, T, N, audio)
+    planned = [emission_plan(e, T, Nf, seg_indices, visual_budget(cfg, p["n_text_tokens"])) for p in prompts]
+    plans, learned = [pl for pl, _ in planned], (planned[0][1] if planned else False)
+    lens = [len(i) if i is not None else 0 for i in pids]
+    groups = prompt_groups([0] * P, lens, [len(pl["comp_frames"]) for pl in plans], K, max_prompts, pad_fraction)
+    ok = getattr(e, "multi_prompt_ok", lambda nf: True)(Nf)
+    out = [None] * P
+    for gi, g in enumerate(groups):
+        gplans = [plans[p] for p in g]
+        multi = ok and len(g) > 1 and all(pl["comp_frames"] for pl in gplans)
+        Lmax = max(lens[p] for p in g)
+        maps = prompt_maps(gplans, learned) if multi else None
+        if multi:
+            qtable = e.learned_queries() if learned else e.make_queries(Xf, N, Nf, maps["key_frames"])
+            comp = e.compress_frames(Xf, Nf, maps["enc_frames"], qtable, maps["qsrc"], [pids[p] or [] for p in g], None,
+                                     dict(kv_src=maps["kv_src"], frame_prompt=maps["frame_prompt"]))
+        for j, p in enumerate(g):
+            info = infos[p] if infos is not None else None
+            splice = prompts[p].get("splice")
+            if not multi:                                         # today's path, on the plan made above
+                out[p] = compress_planned(e, Xf, N, Nf, plans[p], learned, pids[p], None, splice, info)
+                if info is not None:
+                    info["prompts"] = dict(group=gi, group_size=1, pad_rows=0, shared_kv_frames=len(plans[p]["comp_frames"]))
+                continue
+            lo, hi = maps["offsets"][j], maps["offsets"][j + 1]
+            pairs = seg.emit_pairs(plans[p], Nf, K)
+            out[p] = e.emit(Xf, comp[lo * K:hi * K], pairs, splice) if splice is not None else \
+                e.emit(Xf, comp[lo * K:hi * K], pairs)
+            if info is not None:
+                info["n_visual"] = len(pairs)
+                info["prompts"] = dict(group=gi, group_size=len(g), pad_rows=(Lmax - lens[p]) * len(plans[p]["comp_frames"]),
+                                       shared_kv_frames=len(maps["enc_frames"]))
+    return out
+
+
+def encode_video_prompts_with(e, px_siglip, px_dino, image_size, prompts, audio=None, frame_cap=224, video_index=None,
+                              infos=None, cache=None, max_prompts=8, pad_fraction=0.25):
+    """Several prompts about ONE video -> one result per prompt, bit for bit what encode_video(...) returns for it.  The towers,
+    a5 and the connector run once per distinct a1 selection (through `cache` when one is given); the prompts of a selection go
+    through compress_many_with.  prompts: dicts of budget_text_len, n_text_tokens, prompt_ids, optional splice.  infos: one dict
+    per prompt, filled as encode_video's info= plus info["prompts"] (the selection's front facts - info["cache"] among them -
+    are those of the ONE front pass the selection's prompts share)."""
+    cfg = e.cfg
+    T0 = px_siglip.shape[0]
+    sels, order = {}, []
+    for p, pr in enumerate(prompts):
+        key = tuple(frame_indices(cfg, T0, pr["budget_text_len"], frame_cap))                       # a1
+        if key not in sels:
+            sels[key] = []
+            order.append(key)
+        sels[key].append(p)
+    out = [None] * len(prompts)
+    base = 0
+    for key in order:
+        members = sels[key]
+        btl = prompts[members[0]]["budget_text_len"]
+        finfo = {} if infos is not None else None
+        f = None
+        if cache is not None:
+            f = video_front_cached(e, cache, px_siglip, px_dino, image_size, btl, audio, frame_cap, video_index, finfo)
+        if f is None:
+            f = video_front_with(e, px_siglip, px_dino, image_size, btl, audio, frame_cap, None, video_index, finfo)
+        sub = [infos[p] for p in members] if infos is not None else None
+        res = compress_many_with(e, f["X"], f["T"], f["N"], f["seg_idx"], [prompts[p] for p in members], f["audio"], sub,
+                                 max_prompts, pad_fraction)
+        for p, r in zip(members, res):
+            out[p] = r
+            if infos is not None:
+                info = infos[p]
+                info.update(finfo)
+                info.update(frame_indices=f["idx"], selected=list(range(f["T"])), seg_indices=f["seg_idx"],
+                            final_size=f["final_size"])
+                if "cache_info" in f:
+                    info["cache"] = f["cache_info"]()
+                info["prompts"]["group"] += base
+        if infos is not None and members:
+            base = max(infos[p]["prompts"]["group"] for p in members) + 1
+    return out
+
+
+def content_key(e, v):
+    """hashable identity of an audio entry's content: tensors by shape, type and the 128-bit fingerprint of their bytes"""
+    if torch.is_tensor(v):
+        if v.numel() == 0:
+            return ("tensor", str(v.dtype), tuple(v.shape))
+        d = v.detach().to(e.dev).contiguous().view(-1)
+        return ("tensor", str(v.dtype), tuple(v.shape), tuple(e.fingerprint(d, [0], d.numel() * d.element_size(), 0)[0]))
+    if isinstance(v, dict):
+        return ("dict",) + tuple((k, content_key(e, v[k])) for k in sorted(v))
+    if isinstance(v, (list, tuple)):
+        return ("list",) + tuple(content_key(e, x) for x in v)
+    return ("value", repr(v))
+
+
+def same_video_key(e, px_siglip, px_dino, image_size, budget_text_len, frame_cap, audio=None, video_index=None):
+    """`config.tdc_batch_prompts`: what two samples of one call must share to be questions about the SAME video - the frame
+    cache's key material (FrameCache.frame_keys: the fingerprints of their a1-selected pixels, pixel geometry, image_size), and
+    the content of their audio with the seconds it is sampled at.  Frames a1 drops are never read, so they do not count."""
+    from .cache import FrameCache
+    idx = frame_indices(e.cfg, px_siglip.shape[0], budget_text_len, frame_cap)
+    keys, _ = FrameCache.frame_keys(e, px_siglip.to(e.dev), px_dino.to(e.dev), idx, image_size)
+    akey = None
+    if audio is not None:
+        akey = (content_key(e, audio), tuple(sample_indicator(px_siglip.shape[0], idx, video_index)))
+    return (px_siglip.shape[0], tuple(idx), tuple(keys), akey)
 
 
 def frame_indices(cfg, T0, budget_text_len, frame_cap):
@@ -1034,8 +1269,10 @@ def precise_features(e, px_dino, frames, lo=0):
     return {f: fp[j * Pp:(j + 1) * Pp] for j, f in enumerate(frames)}
 
 
-def encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio=None,
-                      frame_cap=224, keep=None, splice=None, video_index=None, info=None):
+def video_front_with(e, px_siglip, px_dino, image_size, budget_text_len, audio=None, frame_cap=224, keep=None,
+                     video_index=None, info=None):
+    """the prompt-independent part of encode_video_with (a1-a10, a20): -> dict(X, T, N, seg_idx, audio, idx, final_size, sig,
+    dino).  Only a1 reads the prompt (through budget_text_len)."""
     cfg = e.cfg
     T0 = px_siglip.shape[0]
     idx = frame_indices(cfg, T0, budget_text_len, frame_cap)                                        # a1
@@ -1065,13 +1302,21 @@ def encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text
     sizes = [tuple(image_size)] * T
     X, final_size = e.connector(sig, dino, T, sizes, keep)                                          # a6-a10
     N = X.shape[0] // T
-    max_visual_len = visual_budget(cfg, n_text_tokens)
-    pid = text_prompt(cfg, prompt_ids)
     if audio is not None:                                                                           # a20
         audio = e.local_audio(audio, sample_indicator(T0, idx, video_index), T, 0, T)
-    vis = compress_with(e, X, T, N, seg_idx, pid, max_visual_len, audio, keep, splice, info)        # a11-a19 (+a21)
+    return dict(X=X, T=T, N=N, seg_idx=seg_idx, audio=audio, idx=idx, final_size=final_size, sig=sig, dino=dino)
+
+
+def encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio=None,
+                      frame_cap=224, keep=None, splice=None, video_index=None, info=None):
+    cfg = e.cfg
+    f = video_front_with(e, px_siglip, px_dino, image_size, budget_text_len, audio, frame_cap, keep, video_index, info)
+    X, T, N, seg_idx, idx, final_size = f["X"], f["T"], f["N"], f["seg_idx"], f["idx"], f["final_size"]
+    max_visual_len = visual_budget(cfg, n_text_tokens)
+    pid = text_prompt(cfg, prompt_ids)
+    vis = compress_with(e, X, T, N, seg_idx, pid, max_visual_len, f["audio"], keep, splice, info)   # a11-a19 (+a21)
     if keep is not None:                    # selected: what a5's second frame cap keeps - every frame (frame_indices)
-        keep.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, siglip_feat=sig, dino_feat=dino,
+        keep.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, siglip_feat=f["sig"], dino_feat=f["dino"],
                     final_size=final_size, X=X)
     if info is not None:
         info.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, final_size=final_size)
@@ -1267,15 +1512,11 @@ def fingerprint_mask(m):
     return fingerprint_rows_host(m.to(torch.uint8).numpy()[None])[0]
 
 
-def encode_video_cached(e, cache, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio=None,
-                        frame_cap=224, splice=None, video_index=None, info=None):
-    """encode_video_with through a FrameCache (cache.py), bit for bit the same result: a1 as there; the a1-selected frames are
-    fingerprinted where they lie; only the frames the cache lacks run through the towers and the connector (frames are
-    independent through a3-a10) and are stored; the a5 similarities come from the cache or from the cached DINOv2 rows
-    (tdc_pair_cossim), the refinement's precise values from the cache or from the pixels passed; the connector rows of the kept
-    frames are gathered out of the slab; a20 and the prompt-dependent a11-a19 run as in encode_video_with.  A call whose
-    distinct frames exceed the budget runs encode_video_with and stores nothing.  info["cache"]: what this call reused and
-    encoded.  The tower batches see the HBM the cache holds as taken (auto_tower_batch): the rate may change, not the bits."""
+def video_front_cached(e, cache, px_siglip, px_dino, image_size, budget_text_len, audio=None, frame_cap=224,
+                       video_index=None, info=None):
+    """the prompt-independent part of encode_video_cached (a1-a10, a20 through the cache): -> video_front_with's dict plus
+    `cache_info()` (the info["cache"] entry, read after the compressor ran), or None when the call's frames exceed the budget
+    (info["cache"] says bypassed; nothing stored)."""
     cfg = e.cfg
     cache.bind(e)
     T0 = px_siglip.shape[0]
@@ -1303,8 +1544,7 @@ def encode_video_cached(e, cache, px_siglip, px_dino, image_size, budget_text_le
     if new is None:
         if info is not None:
             info["cache"] = dict(bypassed=True, frames=T, frames_hit=0, frames_encoded=T, pairs_computed=0)
-        return encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio,
-                                 frame_cap, None, splice, video_index, info)
+        return None
     if not segmented:                                                                               # a5
         seg_idx = list(range(T))
     else:
@@ -1318,18 +1558,39 @@ def encode_video_cached(e, cache, px_siglip, px_dino, image_size, budget_text_le
     X = cache.assemble(e, keys)
     N = cache.rows_per_frame
     final_size = cache.final_sizes(keys)
-    max_visual_len = visual_budget(cfg, n_text_tokens)
-    pid = text_prompt(cfg, prompt_ids)
     if audio is not None:                                                                           # a20
         audio = cached_audio(e, cache, audio, sample_indicator(T0, idx, video_index), T)
-    vis = compress_with(e, X, T, N, seg_idx, pid, max_visual_len, audio, None, splice, info)        # a11-a19 (+a21)
-    if info is not None:
+
+    def cache_info():
         after = cache.stats()
-        info.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, final_size=final_size)
         fresh = set(new)
-        info["cache"] = dict(bypassed=False, frames=T, frames_hit=sum(1 for k in keys if k not in fresh),
-                             frames_encoded=after["frames_encoded"] - before["frames_encoded"],
-                             pairs_computed=after["pairs_computed"] - before["pairs_computed"],
-                             evictions=after["evictions"] - before["evictions"], bytes=after["bytes"],
-                             windows_encoded=after["windows_encoded"] - before["windows_encoded"])
+        return dict(bypassed=False, frames=T, frames_hit=sum(1 for k in keys if k not in fresh),
+                    frames_encoded=after["frames_encoded"] - before["frames_encoded"],
+                    pairs_computed=after["pairs_computed"] - before["pairs_computed"],
+                    evictions=after["evictions"] - before["evictions"], bytes=after["bytes"],
+                    windows_encoded=after["windows_encoded"] - before["windows_encoded"])
+    return dict(X=X, T=T, N=N, seg_idx=seg_idx, audio=audio, idx=idx, final_size=final_size, cache_info=cache_info)
+
+
+def encode_video_cached(e, cache, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio=None,
+                        frame_cap=224, splice=None, video_index=None, info=None):
+    """encode_video_with through a FrameCache (cache.py), bit for bit the same result: a1 as there; the a1-selected frames are
+    fingerprinted where they lie; only the frames the cache lacks run through the towers and the connector (frames are
+    independent through a3-a10) and are stored; the a5 similarities come from the cache or from the cached DINOv2 rows
+    (tdc_pair_cossim), the refinement's precise values from the cache or from the pixels passed; the connector rows of the kept
+    frames are gathered out of the slab; a20 and the prompt-dependent a11-a19 run as in encode_video_with.  A call whose
+    distinct frames exceed the budget runs encode_video_with and stores nothing.  info["cache"]: what this call reused and
+    encoded.  The tower batches see the HBM the cache holds as taken (auto_tower_batch): the rate may change, not the bits."""
+    cfg = e.cfg
+    f = video_front_cached(e, cache, px_siglip, px_dino, image_size, budget_text_len, audio, frame_cap, video_index, info)
+    if f is None:
+        return encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio,
+                                 frame_cap, None, splice, video_index, info)
+    X, T, N, seg_idx, idx, final_size = f["X"], f["T"], f["N"], f["seg_idx"], f["idx"], f["final_size"]
+    max_visual_len = visual_budget(cfg, n_text_tokens)
+    pid = text_prompt(cfg, prompt_ids)
+    vis = compress_with(e, X, T, N, seg_idx, pid, max_visual_len, f["audio"], None, splice, info)   # a11-a19 (+a21)
+    if info is not None:
+        info.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, final_size=final_size)
+        info["cache"] = f["cache_info"]()
     return vis
