@@ -15,6 +15,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # -fno-honor-nans: fmaxf without the canonicalising v_max x,x (scores are finite; -inf only enters through the mask)
 FILE_FLAGS = {"attention.hip": ["-mllvm", "--amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
               "attention32.hip": ["-mllvm", "--amdgpu-mfma-vgpr-form", "-fno-honor-nans"]}
+# build switches of attention32.hip for same-box A/B runs (tools/lib_ab.sh), e.g. TDC_ATTN32_FLAGS=-DATTN32_D72_QB1
+FILE_FLAGS["attention32.hip"] += os.environ.get("TDC_ATTN32_FLAGS", "").split()
 
 
 def sources():

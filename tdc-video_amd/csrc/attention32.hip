@@ -18,7 +18,15 @@
 //                            16 s + 8 (j >> 2) + 4 h + (j & 3), the order the S accumulator has), B = P^T = exp2(S^T c - m)
 //                            converted pairwise in place
 // Head dim 72 runs with the QK^T contraction padded to 80 (5 k-steps of 16; the 16x16x32 form pads to 96) and 3 output
-// blocks of 32.
+// blocks of 32.  Two query blocks per wave need 96 (O) + 64 (S) + 40 (Q) registers, which leaves none for staging, so at
+// head dim exactly 72 (DMA = true) K / V go global -> LDS directly (global_load_lds_dwordx4, 16 bytes per lane).  A
+// wave-instruction writes 64 consecutive chunks, so the LDS image is linear in the staging index and the layout is chosen
+// through each lane's source address: K in 9-chunk (144-byte) rows, V in its 12-chunk rows.  Tile t+1's pieces are issued
+// at the top of tile t into the other buffer and awaited (s_waitcnt vmcnt(0), in asm like the loads: the compiler does not
+// see them) before the tile's single barrier.  P converts in place over S as above (the pf / s arrays share registers by
+// liveness); Q fragments stay in registers.  The masked last tile takes the two query blocks one after the other.  Per-row
+// arithmetic, tile order and the rounding of P are those of the register-staged one-block form, which head dim 80 still
+// runs and -DATTN32_D72_QB1 selects for head dim 72 (A/B runs); -DATTN32_D64_DMA: the same staging at head dim 64 (A/B only).
 #include "common.h"
 #include "../../include/tdc_hip.h"
 #include "attention_args.h"
@@ -46,22 +54,49 @@ __device__ __forceinline__ float other_half(float v) {
 }
 
 constexpr int KT32 = 64;   // keys per tile (2 key blocks of 32)
+
+// a pointer the compiler can prove wave-uniform (scalar registers): the base of an LDS-DMA load
+__device__ __forceinline__ const char* uniform_ptr(const void* p) {
+    const unsigned long long v = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return (const char*)(((unsigned long long)hi << 32) | lo);
+}
+
+// One LDS-DMA piece: lane l's 16 bytes at base + off go to LDS byte address lds_dst + 16 l (global_load_lds_dwordx4; the
+// destination base travels in M0, written and restored in the same statement because the compiler owns M0).  As asm the load
+// is outside hipcc's wait bookkeeping: it neither drains it early (toolchain lesson 4) nor waits for it at all - the
+// caller's own s_waitcnt vmcnt(0) and a barrier stand between a piece and the first read of its bytes.  The leading s_nop
+// covers a base that a v_readfirstlane has only just written.
+__device__ __forceinline__ void glds16(const char* base, unsigned off, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(off), "s"(base), "s"(lds_dst) : "memory");
+}
+// The DMA form calls do_tile from more places; not inlined it passes its register arrays through scratch and the DMA's scalar
+// operands lose their uniformity (toolchain lesson 9).
+#define ATTN32_INLINE __attribute__((always_inline))
 #ifndef ATTN32_THR
 #define ATTN32_THR 8.0f
 #endif
 
-// DK: QK^T contraction width (64 or 80), NDB: output blocks of 32 columns (2 or 3), QB: 32-row query blocks per wave
-template <class T, int DK, int NDB, int QB>
+// DK: QK^T contraction width (64 or 80), NDB: output blocks of 32 columns (2 or 3), QB: 32-row query blocks per wave,
+// DMA: K / V tiles by LDS-DMA (head dim exactly 64 or 72) instead of through registers
+template <class T, int DK, int NDB, int QB, bool DMA>
 __global__ __launch_bounds__(256, 2) void attn32_kernel(AttnArgs p) {
     typedef typename VecOf<T>::v8 v8;
     typedef typename VecOf<T>::v4 v4;
     constexpr int KS = DK / 16;                              // k-steps of the QK^T product
-    constexpr int NCH = DK / 8;                              // real 16-B chunks per K row
+    constexpr int DREAL = DK == 80 ? 72 : 64;                // DMA: the head dim itself, a compile-time constant
+    constexpr int NCH = DMA ? DREAL / 8 : DK / 8;            // 16-B chunks staged per K row
     // chunks per K row in LDS: 8 (128-byte rows, XOR swizzle) at head dim 64; at head dim 72 an ODD number of chunks (11 = 176-byte
     // rows, no swizzle): the 16 lanes a ds_read_b128 cycle serves hold 16 keys that are distinct mod 16, and 11 key mod 16 is a
     // permutation, so they hit 16 distinct 16-byte slots - and the staging writes (consecutive lanes = consecutive chunks of
     // consecutive keys) wrap onto an occupied slot once per 16 lanes instead of six times as with round 4's 256-byte rows, where
     // every row started on bank 0 (the d = 72 launches' 3.5 M conflict cycles, profiles/r04_attention_pmc_summary.txt)
+    // DMA, head dim 72: 9 chunks = 144-byte rows holding exactly the row's 72 columns.  9 is odd like 11, so the same
+    // argument keeps the ds_read_b128 cycles conflict free; the tile shrinks from 11 to 9 KiB.  The fifth k-step's upper half
+    // (columns 72-79, which meet zeroed Q columns) re-reads chunk 8 where the register path reads its clamped duplicate of
+    // chunk 8: the same bits, and no read leaves the row.
     constexpr int KCH = (NCH <= 8) ? 8 : (NCH | 1);
     constexpr int KROW = KCH * 8;
     constexpr int VCH = NDB * 4;                             // 16-B chunks per V row (64 B per output block)
@@ -162,6 +197,69 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(AttnArgs p) {
         }
     };
 
+    // ---- DMA staging: a wave-instruction writes 64 consecutive 16-byte chunks, so the LDS image is linear in the staging index
+    //      idx = 64 piece + lane = KCH key + physical chunk (VCH for V), and the layouts above are reached through each lane's
+    //      SOURCE address: physical chunk pc of a row holds logical chunk kswz(key, pc) / vswz(key, pc) (both are involutions).
+    //      V keeps its 192-byte rows at head dim 72 (chunks 9-11: clamped duplicates of columns 64-71, as on the register path):
+    //      the four keys of one ds_read_b64_tr_b16 sit 192 bytes apart, on four different 64-byte bank groups of the 256-byte
+    //      bank cycle (0, 192, 128, 64); 160-byte rows (10 chunks) would put them at 0, 160, 64, 224, where the fourth wraps onto
+    //      the first's banks, and 144-byte rows at 0, 144, 32, 176, which overlap pairwise.
+    //      K: KT32 * KCH / 64 pieces (9 at head dim 72: wave 0 takes three, the others two), V: KT32 * VCH / 64 (12: three each).
+    //      No staging registers: what stays live across the tile loop is one 32-bit source offset per piece.
+    constexpr int KPC = KT32 * KCH / 64, VPC = KT32 * VCH / 64;
+    constexpr int KPW = (KPC + 3) / 4, VPW = (VPC + 3) / 4;
+    static_assert(!DMA || ((KT32 * KCH) % 64 == 0 && (KT32 * VCH) % 64 == 0 && NCH == KCH), "DMA pieces are whole wave-instructions");
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const char* Kb = nullptr; const char* Vb = nullptr;
+    unsigned lds0 = 0;
+    unsigned koff[KPW], voff[VPW];
+    auto k_src = [&](int i, int kmax) __attribute__((always_inline)) -> unsigned {          // byte offset of this lane's chunk of K piece wave + 4 i within the tile
+        const int idx = (wave_u + 4 * i) * 64 + lane;
+        int key = idx / KCH;
+        const int cc = kswz(key, idx - key * KCH);
+        if (key > kmax) key = kmax;
+        return (unsigned)(key * p.k_rs + cc * 8) * 2u;
+    };
+    auto v_src = [&](int i, int kmax) __attribute__((always_inline)) -> unsigned {
+        const int idx = (wave_u + 4 * i) * 64 + lane;
+        int key = idx / VCH;
+        int c0 = vswz(key, idx - key * VCH) * 8;
+        if (c0 > DREAL - 8) c0 = DREAL - 8;
+        if (key > kmax) key = kmax;
+        return (unsigned)(key * p.v_rs + c0) * 2u;
+    };
+    if (DMA) {
+        Kb = uniform_ptr(K); Vb = uniform_ptr(V);
+        lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem_raw);
+#pragma unroll
+        for (int i = 0; i < KPW; ++i) koff[i] = k_src(i, KT32 - 1);
+#pragma unroll
+        for (int i = 0; i < VPW; ++i) voff[i] = v_src(i, KT32 - 1);
+    }
+    // tile `tile` -> buffer tile & 1.  Keys at and beyond sk are never loaded: in the (at most one) tile that holds some, the row
+    // index is clamped to sk - 1 as on the register path and the offsets are computed afresh.
+    auto dma_tile = [&](int tile) __attribute__((always_inline)) {
+        const int kv0 = tile * KT32, buf = tile & 1;
+        const char* kb = Kb + (long long)kv0 * p.k_rs * 2;
+        const char* vb = Vb + (long long)kv0 * p.v_rs * 2;
+        const unsigned kd = lds0 + buf * (KT32 * KROW * 2), vd = lds0 + (2 * KT32 * KROW + buf * KT32 * VROW) * 2;
+        if (kv0 + KT32 <= sk) {
+#pragma unroll
+            for (int i = 0; i < KPW; ++i)
+                if (4 * i + 3 < KPC || wave_u + 4 * i < KPC) glds16(kb, koff[i], kd + (wave_u + 4 * i) * 1024);
+#pragma unroll
+            for (int i = 0; i < VPW; ++i)
+                if (4 * i + 3 < VPC || wave_u + 4 * i < VPC) glds16(vb, voff[i], vd + (wave_u + 4 * i) * 1024);
+        } else {
+#pragma unroll
+            for (int i = 0; i < KPW; ++i)
+                if (4 * i + 3 < KPC || wave_u + 4 * i < KPC) glds16(kb, k_src(i, sk - 1 - kv0), kd + (wave_u + 4 * i) * 1024);
+#pragma unroll
+            for (int i = 0; i < VPW; ++i)
+                if (4 * i + 3 < VPC || wave_u + 4 * i < VPC) glds16(vb, v_src(i, sk - 1 - kv0), vd + (wave_u + 4 * i) * 1024);
+        }
+    };
+
     f32x16 o_acc[QB][NDB];
     float m_run[QB], l_run[QB];
 #pragma unroll
@@ -180,24 +278,37 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(AttnArgs p) {
     // NQ = query blocks of this wave that hold at least one row < sq (the first NQ ones), NKB = key blocks of the tile that hold
     // at least one key < sk: S = 729 / 730 / 577 leave 32-row blocks past the end of the sequence on both sides (the last
     // workgroup of a head, the last tile of the keys), whose MFMAs and softmax are skipped whole
-    auto do_tile = [&](const int tile, auto partial_c, auto nq_c, auto nkb_c) {
+    // Query blocks Q0 .. NQ - 1 of the wave are worked on: all of them at once but for the masked last tile at two blocks per
+    // wave and head dim 72, see run below.
+    auto do_tile = [&](const int tile, auto partial_c, auto q0_c, auto nq_c, auto nkb_c) ATTN32_INLINE {
         constexpr bool PARTIAL = decltype(partial_c)::value;
-        constexpr int NQ = decltype(nq_c)::value, NKB = decltype(nkb_c)::value;
+        constexpr int Q0 = decltype(q0_c)::value, NQ = decltype(nq_c)::value, NKB = decltype(nkb_c)::value;
+        // second pass over the masked tile: lane terms recomputed instead of being kept, and spilled, across the first pass
+        // (toolchain lesson 7)
+        int ln = lane;
+        if (PARTIAL && DMA && QB > 1 && (Q0 > 0 || NKB == 2)) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+        const int r = ln & 31, hh = ln >> 5;
         const int buf = tile & 1;
         const T* kt_ = Ks + buf * (KT32 * KROW);
         const T* vt_ = Vs + buf * (KT32 * VROW);
         const int kv0 = tile * KT32;
         // tile t+1 (in registers since the previous iteration) -> the other buffer; every wave passed the barrier that ended
         // iteration t-1, so nobody reads that buffer any more.  Then the loads of tile t+2 go out.
+        // DMA: there are no registers to park tile t+2 in, so what goes out here is tile t+1, straight into the other buffer
+        // (free for the same reason), and it has this whole tile's compute to land in.
         if (!PARTIAL) {
-            write_lds(buf ^ 1);
-            if (tile + 2 < ntiles) issue_loads((tile + 2) * KT32);
+            if (DMA) {
+                dma_tile(tile + 1);
+            } else {
+                write_lds(buf ^ 1);
+                if (tile + 2 < ntiles) issue_loads((tile + 2) * KT32);
+            }
         }
 
         // ---- S^T = K Q^T: s[qb][kb] holds, for query r, keys kv0 + 32 kb + (e & 3) + 8 (e >> 2) + 4 hh
         f32x16 s[QB][2];
 #pragma unroll
-        for (int qb = 0; qb < NQ; ++qb)
+        for (int qb = Q0; qb < NQ; ++qb)
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
@@ -207,15 +318,16 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(AttnArgs p) {
             const int key = kb * 32 + r;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                const v8 kf = *(const v8*)(kt_ + key * KROW + (kswz(key, ks * 2 + hh) << 3));
+                const int ch = (DMA && ks * 2 + 1 > NCH - 1) ? NCH - 1 : ks * 2 + hh;
+                const v8 kf = *(const v8*)(kt_ + key * KROW + (kswz(key, ch) << 3));
 #pragma unroll
-                for (int qb = 0; qb < NQ; ++qb) s[qb][kb] = mfma32(kf, qf[qb][ks], s[qb][kb]);
+                for (int qb = Q0; qb < NQ; ++qb) s[qb][kb] = mfma32(kf, qf[qb][ks], s[qb][kb]);
             }
         }
         // ---- online softmax in base 2 on the raw scores; P^T fragments in place
         v8 pf[QB][2][2];
 #pragma unroll
-        for (int qb = 0; qb < NQ; ++qb) {
+        for (int qb = Q0; qb < NQ; ++qb) {
             if (PARTIAL) {
 #pragma unroll
                 for (int kb = 0; kb < NKB; ++kb)
@@ -260,6 +372,13 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(AttnArgs p) {
                         pf[qb][kb][st][j] = e16[0];
                         pf[qb][kb][st][j + 1] = e16[1];
                     }
+            // masked tile at two query blocks per wave: the scheduler otherwise sinks the row-sum adds below the PV product and
+            // spills the exponentials they wait for; the V reads stay below this point
+            if (PARTIAL && DMA && QB > 1) asm volatile("" : "+v"(rs0), "+v"(rs1) : : "memory");
+            if (PARTIAL && DMA && QB > 1) {      // ... and the conversions of P below the O rescale's branch
+#pragma unroll
+                for (int kb = 0; kb < NKB; ++kb) asm volatile("" : "+v"(pf[qb][kb][0]), "+v"(pf[qb][kb][1]));
+            }
             l_run[qb] = l_run[qb] * alpha + (rs0 + rs1);
 #else
             // exponent arguments and row sums on register pairs (v_pk_fma_f32 / v_pk_add_f32: one issue slot per two values)
@@ -292,7 +411,7 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(AttnArgs p) {
         //      32 kb + 16 st + 4 hh (+ 8), columns 32 db + 16 (r >> 4): lane 4 q + pp supplies row q, columns 4 pp ..
 #pragma unroll
         for (int db = 0; db < NDB; ++db) {
-            if (NQ == 0) break;
+            if (NQ == Q0) break;
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
@@ -308,26 +427,47 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(AttnArgs p) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
 #pragma unroll
-                    for (int qb = 0; qb < NQ; ++qb) o_acc[qb][db] = mfma32(vf, pf[qb][kb][st], o_acc[qb][db]);
+                    for (int qb = Q0; qb < NQ; ++qb) o_acc[qb][db] = mfma32(vf, pf[qb][kb][st], o_acc[qb][db]);
                 }
         }
-        __syncthreads();    // tile t+1 is visible; everyone is done reading tile t
+        // this wave's pieces of tile t+1 have landed (the DMA is invisible to the compiler's own waits); past the barrier so have
+        // everyone's
+        if (DMA && !PARTIAL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (!(DMA && PARTIAL)) __syncthreads();    // tile t+1 is visible; everyone is done reading tile t
     };
 
-    // prologue: tile 0 -> buffer 0, tile 1 in registers
-    issue_loads(0);
-    write_lds(0);
-    if (ntiles > 1) issue_loads(KT32);
+    // prologue: tile 0 -> buffer 0, tile 1 in registers (DMA: tile 0 only)
+    if (DMA) {
+        dma_tile(0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else {
+        issue_loads(0);
+        write_lds(0);
+        if (ntiles > 1) issue_loads(KT32);
+    }
     __syncthreads();
     int nq = (p.sq - q0 + 31) >> 5;                              // wave-uniform
     nq = nq < 0 ? 0 : (nq > QB ? QB : nq);
     const bool last_two = sk - (ntiles - 1) * KT32 > 32;       // the last tile's second key block holds valid keys
-    auto run = [&](auto nq_c) {
+    auto run = [&](auto nq_c) ATTN32_INLINE {
         typedef std::integral_constant<int, 2> two;
         typedef std::integral_constant<int, 1> one;
-        for (int tile = 0; tile < ntiles - 1; ++tile) do_tile(tile, std::false_type(), nq_c, two());
-        if (last_two) do_tile(ntiles - 1, std::true_type(), nq_c, two());
-        else do_tile(ntiles - 1, std::true_type(), nq_c, one());
+        typedef std::integral_constant<int, 0> zero;
+        constexpr int NQ = decltype(nq_c)::value;
+        for (int tile = 0; tile < ntiles - 1; ++tile) do_tile(tile, std::false_type(), zero(), nq_c, two());
+        if (DMA && NQ == 2 && NDB == 3) {
+            // 96 O + 64 S + 40 Q registers leave no room for the mask's terms beside two blocks' scores (39 spilled VGPRs): the
+            // masked tile - one in twelve at S = 729, and nothing follows it - takes the wave's two query blocks one after the
+            // other, re-reading its K / V fragments.  Per-row arithmetic is what it is in the other order.
+            // (the tile index is made opaque per call: what the four bodies have in common - the first K fragment reads, the
+            // mask's compares - is otherwise hoisted above the branch into registers of its own, toolchain lesson 8)
+            auto last = [&]() __attribute__((always_inline)) { int t = ntiles - 1; asm volatile("" : "+s"(t)); return t; };
+            if (last_two) { do_tile(last(), std::true_type(), zero(), one(), two()); __builtin_amdgcn_sched_barrier(0); do_tile(last(), std::true_type(), one(), two(), two()); }
+            else { do_tile(last(), std::true_type(), zero(), one(), one()); __builtin_amdgcn_sched_barrier(0); do_tile(last(), std::true_type(), one(), two(), one()); }
+        } else {
+            if (last_two) do_tile(ntiles - 1, std::true_type(), zero(), nq_c, two());
+            else do_tile(ntiles - 1, std::true_type(), zero(), nq_c, one());
+        }
     };
     if (nq >= QB) run(std::integral_constant<int, QB>());
     else if (QB > 1 && nq == 1) run(std::integral_constant<int, 1>());
@@ -357,20 +497,21 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(AttnArgs p) {
     }
 }
 
-template <class T, int DK, int NDB, int QB>
+template <class T, int DK, int NDB, int QB, bool DMA>
 int launch32(const AttnArgs& a, int batch, hipStream_t st) {
-    constexpr int KCH = (DK / 8 <= 8) ? 8 : ((DK / 8) | 1);
+    constexpr int NCH = DMA ? (DK == 80 ? 9 : 8) : DK / 8;
+    constexpr int KCH = (NCH <= 8) ? 8 : (NCH | 1);
     constexpr int lds = 2 * KT32 * (KCH * 8 + NDB * 32) * 2;
     static bool attr_dev[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     if (!attr_dev[dev]) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn32_kernel<T, DK, NDB, QB>,
+        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn32_kernel<T, DK, NDB, QB, DMA>,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr_dev[dev] = true;
     }
     dim3 grid(((a.sq + 128 * QB - 1) / (128 * QB)) * a.heads * batch);   // 1-D: the kernel maps ids to (batch, head, query block)
-    hipLaunchKernelGGL((attn32_kernel<T, DK, NDB, QB>), grid, dim3(256), lds, st, a);
+    hipLaunchKernelGGL((attn32_kernel<T, DK, NDB, QB, DMA>), grid, dim3(256), lds, st, a);
     return (int)hipGetLastError();
 }
 
@@ -379,7 +520,14 @@ int launch32(const AttnArgs& a, int batch, hipStream_t st) {
 // entry for attention.hip: returns -1 when this form does not apply (the caller falls through to the 16x16 kernels)
 int tdc_attention32(const AttnArgs& a, int batch, int dtype, hipStream_t st) {
     if (a.bias || !a.vec_ok || a.sq < 256 || a.sk < 64) return -1;
-    if (a.d == 64) return dtype == TDC_F16 ? launch32<f16, 64, 2, 2>(a, batch, st) : launch32<bf16, 64, 2, 2>(a, batch, st);
-    if (a.d > 64 && a.d <= 80) return dtype == TDC_F16 ? launch32<f16, 80, 3, 1>(a, batch, st) : launch32<bf16, 80, 3, 1>(a, batch, st);
+#ifdef ATTN32_D64_DMA       // A/B only: head dim 64 with DMA staging (NOTES 2, tower attention)
+    if (a.d == 64) return dtype == TDC_F16 ? launch32<f16, 64, 2, 2, true>(a, batch, st) : launch32<bf16, 64, 2, 2, true>(a, batch, st);
+#else
+    if (a.d == 64) return dtype == TDC_F16 ? launch32<f16, 64, 2, 2, false>(a, batch, st) : launch32<bf16, 64, 2, 2, false>(a, batch, st);
+#endif
+#ifndef ATTN32_D72_QB1      // -DATTN32_D72_QB1: head dim 72 on the register-staged one-block form below, for A/B runs
+    if (a.d == 72) return dtype == TDC_F16 ? launch32<f16, 80, 3, 2, true>(a, batch, st) : launch32<bf16, 80, 3, 2, true>(a, batch, st);
+#endif
+    if (a.d > 64 && a.d <= 80) return dtype == TDC_F16 ? launch32<f16, 80, 3, 1, false>(a, batch, st) : launch32<bf16, 80, 3, 1, false>(a, batch, st);
     return -1;
 }
