@@ -1,4 +1,4 @@
-"""Content-keyed frame cache: encode a video once, answer many prompts (pipeline.encode_video_cached).
+"""Content-keyed frame cache: encode a video once, answer many prompts (encode.encode_video_cached).
 
 Everything from the pixels up to the connector rows (a3/a4 towers, a5 similarities, a6-a10 connector) depends on the frame
 pixels and image_size alone, and frames are independent through it, bit for bit.  FrameCache keeps, per frame content:
@@ -263,6 +263,28 @@ class FrameCache:
         """pair_put of a similarity this call computed (counted in pairs_computed)"""
         self.pair_put(key, value)
         self._counts["pairs_computed"] += 1
+
+    def early_sims(self, e, keys, dkeys, new, dino, segmented=True):
+        """encode_missing's after_dino: a5 of the adjacent pairs of `keys` whose frames are both `new`, from their fresh DINOv2
+        rows, enqueued BEFORE the SigLIP tower and read while it runs (as encode.towers_and_selection does); pairs with a
+        stored frame come from the slab later.  -> the `early` dict of adjacent_sims ({}: not segmented, or no such pair)"""
+        pos = {k: j for j, k in enumerate(new)}
+        todo = [i for i in range(len(keys) - 1) if keys[i] in pos and keys[i + 1] in pos and
+                self.pair_get((dkeys[i], dkeys[i + 1])) is None]
+        if not (segmented and todo):
+            return {}
+        slab = dino.view(len(new), dino.shape[0] // len(new), dino.shape[1])
+        return dict(pairs=todo, read=e.slot_sims(slab, [(pos[keys[i]], pos[keys[i + 1]]) for i in todo], defer=True))
+
+    @staticmethod
+    def call_info(before, after, keys, new):
+        """info["cache"] of one call over the frames `keys`, of which it encoded the `new` ones: stats() before and after it"""
+        fresh = set(new)
+        return dict(bypassed=False, frames=len(keys), frames_hit=sum(1 for k in keys if k not in fresh),
+                    frames_encoded=after["frames_encoded"] - before["frames_encoded"],
+                    pairs_computed=after["pairs_computed"] - before["pairs_computed"],
+                    evictions=after["evictions"] - before["evictions"], bytes=after["bytes"],
+                    windows_encoded=after["windows_encoded"] - before["windows_encoded"])
 
     def adjacent_sims(self, e, keys, dkeys, early=None):
         """a5: the T - 1 adjacent-frame similarities of the frames `keys` - stored values, those already enqueued (early:

@@ -27,8 +27,8 @@ import torch
 
 from . import segment as seg
 from .cache import fingerprint_rows_host
-from .pipeline import (cached_audio, emission_plan, encode_missing, frame_indices, join_side_tower, precise_features,
-                       sample_indicator, select_segments_with, start_side_tower, text_prompt, visual_budget)
+from .encode import (cached_audio, emission_plan, encode_missing, frame_indices, join_side_tower, precise_features,
+                     sample_indicator, select_segments_with, start_side_tower, text_prompt, visual_budget)
 
 
 def owner_of(frame, ranges):
@@ -74,10 +74,7 @@ class TorchComm:
         self._host_side = None
 
     def _sync_if_host_side(self, t):
-        if self._host_side is None:
-            import torch.distributed as dist
-            self._host_side = dist.get_backend(self.group) != "nccl"
-        if self._host_side and t is not None and t.is_cuda:
+        if self._host_side_now() and t is not None and t.is_cuda:
             torch.cuda.synchronize(t.device)
 
     def _host_side_now(self):
@@ -199,7 +196,7 @@ class ShardedVideoEncoder:
         return e.compact_rows(recv, idx, cols)
 
     def _refined_sims(self, band, px_dino_local_halo, ranges, recompute_halo):
-        """the `refine` of pipeline.select_segments_with, sharded: the pairs of `band` - the same list on every rank - are
+        """the `refine` of encode.select_segments_with, sharded: the pairs of `band` - the same list on every rank - are
         re-encoded by the engine's precise DINOv2 tower.  Pair i belongs to the rank that owns frame i; it needs frame i + 1 as
         well, which for the last local frame is the right neighbour's first: that rank sends the precise feature rows of its
         first frame (as the boundary exchange of step 1 does for the fast tower), unless the caller handed this rank the halo
@@ -259,21 +256,15 @@ class ShardedVideoEncoder:
         if T <= cfg.get("max_num_segments", 24) + 1:
             seg_idx = list(range(T))
         else:
-            # T > 25 >= 3 * world: every rank owns frames.  Local pairs, then the pair across the right-hand boundary.
-            sims_parts = []
+            # T > 25 >= 3 * world: every rank owns frames
             if not recompute_halo:
                 first = dino_all[:P].contiguous()
                 halo_rows = torch.empty_like(first) if rank < world - 1 else None
                 self.comm.exchange([(first, rank - 1)] if rank > 0 else [],
                                    [(halo_rows, rank + 1)] if rank < world - 1 else [])
-                if Tl >= 2:
-                    sims_parts.append(e.sims_tensor(dino_all, Tl))
-                if halo_rows is not None:
-                    sims_parts.append(e.sims_tensor(torch.cat([dino_all[(Tl - 1) * P: Tl * P], halo_rows], 0), 2))
-            elif n_d >= 2:
-                sims_parts.append(e.sims_tensor(dino_all, n_d))
-            sims_local = torch.cat(sims_parts, 0) if sims_parts else \
-                torch.zeros(0, dtype=torch.float32, device=dino_all.device)
+                sims_local = self._local_sims(dino_all, Tl, P, halo_rows)
+            else:                             # the halo frame is the last of the n_d frames encoded here
+                sims_local = self._local_sims(dino_all, n_d, P, None)
             # the local SigLIP tower is enqueued before the exchange: the device works while the similarities travel - on a
             # side stream that waits only for the similarity kernels (engine.mark / after), so neither the collective nor
             # the host read queues behind the tower (with a host-side transport - gloo - the device is synchronised anyway)
@@ -300,6 +291,14 @@ class ShardedVideoEncoder:
             sample_indices = [1] * T
         Xf, Nf = e.with_audio(X, Tl, N, e.local_audio(audio, sample_indices, T, lo, hi))
         return self._compress_gather(Xf, N, Nf, T, ranges, seg_idx, n_text_tokens, prompt_ids, X.device)
+
+    def _local_sims(self, dino_all, n, P, halo_rows):
+        """this rank's share of the T - 1 similarities from the DINOv2 rows of its n frames: the local pairs, then the pair
+        across the right-hand boundary (halo_rows: the right neighbour's first frame, None on the last rank)"""
+        parts = [self.e.sims_tensor(dino_all, n)] if n >= 2 else []
+        if halo_rows is not None:
+            parts.append(self.e.sims_tensor(torch.cat([dino_all[(n - 1) * P: n * P], halo_rows], 0), 2))
+        return torch.cat(parts, 0) if parts else torch.zeros(0, dtype=torch.float32, device=dino_all.device)
 
     def _pass_through(self, T, image_size, n_text_tokens, audio, ranges, device):
         """a rank without frames: more ranks than frames (T < world <= 8 < max_num_segments + 1: the pass-through case, no
@@ -445,7 +444,7 @@ class ShardedVideoEncoder:
 
     def _encode_cached(self, cache, px_s, px_d, T, image_size, n_text_tokens, prompt_ids, audio, sample_indices,
                        recompute_halo, info):
-        """encode_video through this rank's FrameCache, bit for bit the uncached result (pipeline.encode_video_cached, per
+        """encode_video through this rank's FrameCache, bit for bit the uncached result (encode.encode_video_cached, per
         rank): 1. sample agreement (_agree); 2. the local frames are fingerprinted where they lie, only those the cache lacks
         run through the towers and the connector (a rank whose frames exceed its budget runs them uncached and stores
         nothing); 3. local similarities from the cache / the slab, the boundary exchange as in the uncached path plus the
@@ -481,19 +480,9 @@ class ShardedVideoEncoder:
         idx = list(range(Tl))
         keys, dkeys = cache.frame_keys(e, px_s, px_d, idx, image_size)
         segmented = T > cfg.get("max_num_segments", 24) + 1
-        early = {}
-
-        def after_dino(new, dino):
-            # local pairs of two new frames: enqueued before the SigLIP tower, read while it runs (encode_video_cached)
-            pos = {k: j for j, k in enumerate(new)}
-            todo = [i for i in range(Tl - 1) if keys[i] in pos and keys[i + 1] in pos and
-                    cache.pair_get((dkeys[i], dkeys[i + 1])) is None]
-            if segmented and todo:
-                slab = dino.view(len(new), dino.shape[0] // len(new), dino.shape[1])
-                early["pairs"] = todo
-                early["read"] = e.slot_sims(slab, [(pos[keys[i]], pos[keys[i + 1]]) for i in todo], defer=True)
-
-        new = encode_missing(e, cache, keys, px_s, px_d, idx, image_size, after_dino) if cache.fits(keys) else None
+        early = {}                             # local pairs of two new frames, enqueued BEFORE the SigLIP tower
+        new = encode_missing(e, cache, keys, px_s, px_d, idx, image_size, lambda new, dino: early.update(
+            cache.early_sims(e, keys, dkeys, new, dino, segmented))) if cache.fits(keys) else None
         bypass = new is None
         if bypass:                             # over this rank's budget: its towers run uncached, nothing is stored
             early.clear()
@@ -521,10 +510,7 @@ class ShardedVideoEncoder:
             if key_buf is not None:
                 right = (tuple(v & 0xFFFFFFFFFFFFFFFF for v in key_buf.tolist()), dkeys[0][1])
             if bypass:
-                parts = [e.sims_tensor(dino_all, Tl)] if Tl >= 2 else []
-                if pair_buf is not None:
-                    parts.append(e.sims_tensor(torch.cat([dino_all[(Tl - 1) * P: Tl * P], pair_buf[1]], 0), 2))
-                sims_local = torch.cat(parts, 0) if parts else torch.zeros(0, dtype=torch.float32, device=dev)
+                sims_local = self._local_sims(dino_all, Tl, P, None if pair_buf is None else pair_buf[1])
             else:
                 local = cache.adjacent_sims(e, keys, dkeys, early)
                 if right is not None:
@@ -555,12 +541,8 @@ class ShardedVideoEncoder:
         Xf, Nf = e.with_audio(X, Tl, N, a_local)
         out = self._compress_gather(Xf, N, Nf, T, ranges, seg_idx, n_text_tokens, prompt_ids, dev)        # 6.
         if info is not None:
-            after = cache.stats()
-            fresh = set(new or ())
-            stats.update(bypassed=bypass, frames_hit=0 if bypass else sum(1 for k in keys if k not in fresh),
-                         frames_encoded=Tl if bypass else after["frames_encoded"] - before["frames_encoded"],
-                         pairs_computed=after["pairs_computed"] - before["pairs_computed"],
-                         evictions=after["evictions"] - before["evictions"], bytes=after["bytes"],
-                         windows_encoded=after["windows_encoded"] - before["windows_encoded"])
+            stats.update(cache.call_info(before, cache.stats(), keys, new or ()))
+            if bypass:
+                stats.update(bypassed=True, frames_hit=0, frames_encoded=Tl)
             info["cache"] = stats
         return out

@@ -23,7 +23,8 @@ import torch.nn as nn
 
 from . import lib as L
 from . import segment as seg
-from .pipeline import VideoEncoder, batch_groups, encode_image_cached, frame_indices, same_video_key
+from .encode import batch_groups, encode_image_cached, frame_indices, same_video_key
+from .pipeline import VideoEncoder
 
 IGNORE_INDEX = -100        # tdc/constants.py
 IMAGE_TOKEN_INDEX = -200
@@ -507,7 +508,7 @@ class CambrianMetaModel:
         return n
 
     def tdc_prompt_pad_fraction(self):
-        """`config.tdc_prompt_pad_fraction`: the share of a prompt group's rows that may be padding (pipeline.prompt_groups);
+        """`config.tdc_prompt_pad_fraction`: the share of a prompt group's rows that may be padding (encode.prompt_groups);
         absent: 1/4."""
         v = getattr(self.config, "tdc_prompt_pad_fraction", None)
         if v is None:
@@ -517,7 +518,7 @@ class CambrianMetaModel:
         return float(v)
 
     def tdc_side_stream(self, frames_per_rank):
-        """engine.two_streams (pipeline.start_side_tower): the config's choice, by default on at <= 128 frames per rank"""
+        """engine.two_streams (encode.start_side_tower): the config's choice, by default on at <= 128 frames per rank"""
         ts = getattr(self.config, "tdc_two_streams", None)
         return bool(ts) if ts is not None else frames_per_rank <= 128
 

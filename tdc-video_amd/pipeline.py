@@ -15,7 +15,15 @@ from . import lib as L
 from . import ops
 from . import segment as seg
 from . import weights as Wt
+# the orchestration over an engine (encode.py): what the methods below call, and the names this module has always offered
+from .encode import (batch_groups, cached_audio, compress_many_with, compress_with, emission_plan,  # noqa: F401
+                     encode_batch_with, encode_image_cached, encode_missing, encode_video_cached, encode_video_prompts_with,
+                     encode_video_with, frame_indices, gather_frames, join_side_tower, precise_features, prompt_groups,
+                     prompt_maps, same_video_key, sample_indicator, select_segments_with, start_side_tower, text_prompt,
+                     visual_budget)
 from .weights import pad64
+
+ACT_CODES = {"gelu_tanh": L.ACT_GELU_TANH, "gelu_erf": L.ACT_GELU_ERF, "swiglu": L.ACT_SWIGLU}
 
 
 def _lin(l):
@@ -51,6 +59,21 @@ class _LRU(dict):
 
 
 class VideoEncoder:
+    """defaults first: what __init__ may leave unset, and what encoders assembled field by field (tests) do not set"""
+    native_towers = True          # towers through the C++ composite tdc_vit_fwd (per-kernel Python path when False)
+    native_connector = True       # a6-a9 through tdc_connector_fwd
+    native_qformer = True         # Q-Former through the C++ composite tdc_qformer_fwd
+    # cross-attention block of the Q-Former (SURVEY D7): 2 = one kernel per layer (tdc_qformer_xattn), 1 = q GEMM + tdc_attention,
+    # then output projection + residual + LayerNorm in one kernel, 0 = per-kernel sequence; applies when the shape allows it
+    # (bert-base width, K % 16 == 0; mode 2 also Nenc % 4 == 0, Nenc <= 224)
+    xattn_mode = 1
+    two_streams = False
+    tower_res_dtype = None
+    beats = None                  # beats.BeatsEncoder for raw-waveform audio input (SURVEY 8(f)-1)
+    selection_eps = None
+    selection_max_fraction = 0.125
+    _tower_dtype = _conn_struct = _qf_struct = _tower_stream = _side_stream = None
+
     def __init__(self, sd, cfg, dtype=torch.float16, device="cuda", siglip_heads=16, dino_heads=24,
                  qformer_heads=12, tower_batch=None, fp8_towers=False, tower_dtype=None, ln_fuse=False,
                  tower_res_dtype=None, dino_dtype=None, selection_refine=None, selection_eps=1e-3, selection_max_fraction=0.125):
@@ -108,7 +131,6 @@ class VideoEncoder:
         # similarities decide the selection (select_segments_with, on the serial and the sharded path)
         if selection_refine is None:
             selection_refine = bool(d_sd) and (dino_dtype or tower_dtype) == torch.bfloat16 and not fp8_towers
-        self.selection_eps = None
         if selection_refine and d_sd and (dino_dtype or tower_dtype) != torch.float16:
             tp = Wt.prep_dino(d_sd, dino_heads, torch.float16, self.dev)
             tp["dtype"] = torch.float16
@@ -124,22 +146,18 @@ class VideoEncoder:
         self._tables = _LRU(32)
         self.K = cfg.get("context_token_num", 16)
         self.H = cfg["hidden_size"]
-        self.two_streams = False
-        self.native_qformer = True    # Q-Former through the C++ composite tdc_qformer_fwd
-        # cross-attention block of the Q-Former: 2 = one kernel per layer (tdc_qformer_xattn), 1 = q GEMM + tdc_attention,
-        # then output projection + residual + LayerNorm in one kernel, 0 = per-kernel sequence; applies when the shape allows it
-        # (bert-base width, K % 16 == 0; mode 2 also Nenc % 4 == 0, Nenc <= 224)
-        self.xattn_mode = 1
-        self.native_towers = True     # towers through the C++ composite tdc_vit_fwd (per-kernel Python path when False)
-        self.beats = None             # beats.BeatsEncoder for raw-waveform audio input
 
     @property
     def tower_dtype(self):
-        return self.__dict__.get("_tower_dtype") or self.dtype
+        return self._tower_dtype or self.dtype
 
     def _tdt(self, t):
         """operand type of tower `t` (its weights' type): tower_dtype unless dino_dtype set the DINOv2 tower apart"""
         return t.get("dtype") or self.tower_dtype
+
+    def _res_dtype(self, t):
+        """type of tower `t`'s residual stream: its own "res_dtype" (the precise DINOv2 copy) or the engine's; None = fp32"""
+        return t["res_dtype"] if "res_dtype" in t else self.tower_res_dtype
 
     # ------------------------------------------------------------------------------------------------ towers
     def _bil(self, n_in, n_out):
@@ -174,7 +192,7 @@ class VideoEncoder:
         if free_bytes is None:
             free, _total = torch.cuda.mem_get_info(self.dev)
             unused = torch.cuda.memory_reserved(self.dev) - torch.cuda.memory_allocated(self.dev)
-            ws = getattr(self, self._vit_ws_key(t), None)
+            ws = vars(self).get(self._vit_ws_key(t))
             free_bytes = free + max(0, unused) + (ws.numel() if ws is not None else 0)
         budget = 0.6 * free_bytes
         while B > 1 and lib.tdc_vit_workspace_bytes(C.byref(m), B, Hpx, Wpx) > budget:
@@ -183,14 +201,14 @@ class VideoEncoder:
 
     def _workspace(self, key, nbytes):
         """the native composite's device workspace in attribute `key`, grown to nbytes (kept for the engine's life)"""
-        ws = getattr(self, key, None)
+        ws = vars(self).get(key)
         if ws is None or ws.numel() < nbytes:
             ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
             setattr(self, key, ws)
         return ws
 
     def _vit_ws_key(self, t):       # one workspace per tower when the towers run concurrently on two streams
-        return "_vit_ws_" + t.kind if getattr(self, "two_streams", False) else "_vit_ws"
+        return "_vit_ws_" + t.kind if self.two_streams else "_vit_ws"
 
     # ---- native composite (csrc/api.cpp: tdc_vit_fwd): the whole tower batch is one C call ------------------------------
     def _vit_struct(self, t, gh, gw):
@@ -215,11 +233,11 @@ class VideoEncoder:
                                    Lr.out.wscale or 0.0, Lr.fc2.wscale or 0.0, Lr.fc1.w2max, Lr.fc1.bmax)
         m = L.VitModel()
         m.dtype, m.out_dtype_p1 = ops._dtcode(self._tdt(t)), ops._dtcode(self.dtype) + 1
-        rd = t["res_dtype"] if "res_dtype" in t else getattr(self, "tower_res_dtype", None)
+        rd = self._res_dtype(t)
         m.res_dtype_p1 = 0 if rd is None else ops._dtcode(rd) + 1
         m.dim, m.heads, m.head_dim, m.n_layers, m.patch, m.has_cls = t.dim, t.heads, t.head_dim, len(t.layers), t.patch, \
             t.has_cls
-        m.act = {"gelu_tanh": L.ACT_GELU_TANH, "gelu_erf": L.ACT_GELU_ERF, "swiglu": L.ACT_SWIGLU}[t.act]
+        m.act = ACT_CODES[t.act]
         m.eps = t.eps
         m.patch_lin = _lin(t.patch_lin)
         m.pos, m.ldpos = pos.data_ptr(), pos.stride(0)
@@ -253,10 +271,10 @@ class VideoEncoder:
         """One tower batch.  Default: the C++ composite (tdc_vit_fwd).  With `native_towers = False`: the SAME launches issued one
         by one from Python - the form the tests compare the composite with, bit for bit - over either residual stream
         (`tower_res_dtype`: None = fp32, read-modify-written as 8 B per element; a 16-bit type = tdc_vit_model.res_dtype_p1)."""
-        if getattr(self, "native_towers", True) and len(t.layers) > 0:
+        if self.native_towers and len(t.layers) > 0:
             return self._tower_batch_native(t, px, out_grid)
         dt, dev = self._tdt(t), self.dev
-        rd = t["res_dtype"] if "res_dtype" in t else getattr(self, "tower_res_dtype", None)
+        rd = self._res_dtype(t)
         s32 = rd is None                         # fp32 residual stream
         B = px.shape[0]
         D, Dp = t.dim, pad64(t.dim)
@@ -281,7 +299,7 @@ class VideoEncoder:
         h16 = torch.empty(B * S, Dp, device=dev, dtype=dt)
         qkv = torch.empty(B * S, t.layers[0].qkv.w.shape[0], device=dev, dtype=dt) if t.layers else None
         attn = torch.zeros(B * S, Dp, device=dev, dtype=dt)
-        act = {"gelu_tanh": L.ACT_GELU_TANH, "gelu_erf": L.ACT_GELU_ERF, "swiglu": L.ACT_SWIGLU}[t.act]
+        act = ACT_CODES[t.act]
         mlp_w = t.layers[0].fc2.w.shape[1] if t.layers else 0
         mlp = torch.empty(B * S, mlp_w, device=dev, dtype=dt) if t.layers else None
         scale = t.head_dim ** -0.5
@@ -372,13 +390,13 @@ class VideoEncoder:
     def tower_stream(self):
         """the ONE side stream the SigLIP tower runs on under `two_streams` (kept for the engine's life: its per-tower workspace
         `_vit_ws_siglip` and the cached tables are allocated under it once and never migrate between pool streams)"""
-        st = self.__dict__.get("_tower_stream")
+        st = self._tower_stream
         if st is None:
             st = self._tower_stream = torch.cuda.Stream(device=self.dev)
         return st
 
     def after(self, ev):
-        side = self.__dict__.get("_side_stream")
+        side = self._side_stream
         if side is None:
             side = self._side_stream = torch.cuda.Stream(device=self.dev)
         side.wait_event(ev)
@@ -498,7 +516,7 @@ class VideoEncoder:
     # ---- native composite (csrc/api.cpp: tdc_connector_fwd): a6-a9 in one C call ------------------------------------------
     def _connector_struct(self):
         """ctypes mirror of tdc_connector_model (cached; keeps the arrays alive)."""
-        if getattr(self, "_conn_struct", None) is not None:
+        if self._conn_struct is not None:
             return self._conn_struct
         c = self.c
         layers = (L.SvaLayer * len(c.sva))()
@@ -560,7 +578,7 @@ class VideoEncoder:
         return out
 
     def connector(self, sig_feat, dino_feat, T, image_sizes, keep=None):
-        if keep is None and getattr(self, "native_connector", True):
+        if keep is None and self.native_connector:
             feat = self._connector_native(sig_feat, dino_feat, T, image_sizes)
             return self.unpad_newline(feat, T, image_sizes)
         aux = [self.aux_project(sig_feat, 0), self.aux_project(dino_feat, 1)]
@@ -602,7 +620,7 @@ class VideoEncoder:
             h32, h16 = ops.qformer_embed(query, qsrc, qf.word, qf.pos, ids, qf.emb_ln[0], qf.emb_ln[1], 1e-12, F, K, Dq, dt)
         S = K + Lt
         # the cross-attention block: fused form = key GEMM + transposed value GEMM + one kernel per cross layer
-        mode = int(getattr(self, "xattn_mode", 1)) if qf.cross_k is not None else 0
+        mode = int(self.xattn_mode) if qf.cross_k is not None else 0
         fused = mode >= 2 and ops.qformer_xattn_supported(Dq, heads, K, Nenc)
         out_fused = not fused and mode >= 1 and ops.qformer_xattn_supported(Dq, heads, K, 8)
         if fused or out_fused:
@@ -712,7 +730,7 @@ class VideoEncoder:
         """tdc/cambrian_arch.py:1552-1560: BEATs features of the consecutive 10-s windows of wav [1, n] (16 kHz).
         `self.beats` is a beats.BeatsEncoder (set by the owner of the weights, e.g. model.initialize_audio).
         only = set of window indices -> dict {window: features} of just those windows."""
-        if getattr(self, "beats", None) is None:
+        if self.beats is None:
             raise RuntimeError("raw audio given but no BEATs encoder is attached (VideoEncoder.beats)")
         return self.beats.window_features(wav, only=only, mask=mask)
 
@@ -731,7 +749,7 @@ class VideoEncoder:
         if wins is not None:
             return self.audio_tokens(wins, sample_indices, T, lo, hi)
         wav = audio["audio_wav"]                               # raw 16 kHz waveform: BEATs on the device (8(f)-1)
-        if getattr(self, "beats", None) is None:
+        if self.beats is None:
             raise RuntimeError("raw audio given but no BEATs encoder is attached (VideoEncoder.beats)")
         sizes = self.beats.window_token_counts(wav.shape[1])
         plan = seg.audio_plan(sizes, [int(v) for v in sample_indices])
@@ -783,8 +801,8 @@ class VideoEncoder:
 
     def _qformer_struct(self):
         """ctypes mirror of tdc_qformer_model (cached)."""
-        fused_on = int(getattr(self, "xattn_mode", 1))
-        if getattr(self, "_qf_struct", None) is not None and self._qf_struct[2] == fused_on:
+        fused_on = int(self.xattn_mode)
+        if self._qf_struct is not None and self._qf_struct[2] == fused_on:
             return self._qf_struct
         c, qf = self.c, self.c.qformer
         self._tile_cross_weights()
@@ -837,6 +855,7 @@ class VideoEncoder:
         m = self._qformer_struct()[0]
         K = self.K
         assert qs.dtype == torch.int32 and qs.numel() >= F        # value range checked on the host list (compress_frames)
+        U = F
         if multi is not None:
             # the multi-prompt form (tdc_qformer_prompts): a copy of the model struct carries the block, the cached one stays as is
             qf = self.c.qformer
@@ -854,30 +873,24 @@ class VideoEncoder:
             mm = L.QformerModel()
             C.pointer(mm)[0] = m
             mm.prompts = C.pointer(pr)
-            assert enc.shape[0] >= U * Nf and enc.shape[1] >= m.cross_kv.k and qtable.shape[1] >= pad64(m.dim)
-            lib = L.load()
-            ws = self._workspace("_qf_ws", lib.tdc_qformer_workspace_bytes(C.byref(mm), F, K, Lt, Nf))
-            out = torch.empty(F * K, pad64(self.c.H), device=self.dev, dtype=self.dtype)
-            L.check(lib.tdc_qformer_fwd(C.byref(mm), ops._ptr(enc), enc.stride(0), F, Nf, ops._ptr(qtable), qtable.stride(0),
-                                        ops._ptr(qs), ops._ptr(ids if Lt else None), Lt, K, ops._ptr(out), out.stride(0),
-                                        ops._ptr(ws), ws.numel(), ops._stream()), "tdc_qformer_fwd")
-            return out
-        ids = self._prompt_tensor(prompt_ids)
-        Lt = 0 if ids is None else ids.numel()
-        assert enc.shape[0] >= F * Nf and enc.shape[1] >= m.cross_kv.k and qtable.shape[1] >= pad64(m.dim)
+            m = mm
+        else:
+            ids = self._prompt_tensor(prompt_ids)
+            Lt = 0 if ids is None else ids.numel()
+        assert enc.shape[0] >= U * Nf and enc.shape[1] >= m.cross_kv.k and qtable.shape[1] >= pad64(m.dim)
         lib = L.load()
         ws = self._workspace("_qf_ws", lib.tdc_qformer_workspace_bytes(C.byref(m), F, K, Lt, Nf))
         out = torch.empty(F * K, pad64(self.c.H), device=self.dev, dtype=self.dtype)
         L.check(lib.tdc_qformer_fwd(C.byref(m), ops._ptr(enc), enc.stride(0), F, Nf, ops._ptr(qtable), qtable.stride(0),
-                                    ops._ptr(qs), ops._ptr(ids), Lt, K, ops._ptr(out), out.stride(0), ops._ptr(ws),
-                                    ws.numel(), ops._stream()), "tdc_qformer_fwd")
+                                    ops._ptr(qs), ops._ptr(ids if Lt else None), Lt, K, ops._ptr(out), out.stride(0),
+                                    ops._ptr(ws), ws.numel(), ops._stream()), "tdc_qformer_fwd")
         return out
 
     def multi_prompt_ok(self, Nf):
         """whether compress_frames takes the multi-prompt form here: not under the whole-block cross-attention kernel
         (xattn_mode 2 where its shape support holds) - the callers then run one pass per prompt"""
         qf = self.c.qformer
-        return not (int(getattr(self, "xattn_mode", 1)) >= 2 and qf.cross_k is not None and
+        return not (int(self.xattn_mode) >= 2 and qf.cross_k is not None and
                     ops.qformer_xattn_supported(qf.dim, self.qheads, self.K, Nf))
 
     def compress_frames(self, Xf, Nf, frame_rows, qtable, qsrc, prompt_ids, keep=None, multi=None):
@@ -901,7 +914,7 @@ class VideoEncoder:
             if not self.multi_prompt_ok(Nf):
                 raise ValueError("compress_frames: the multi-prompt form runs xattn_mode 0 / 1 only (multi_prompt_ok)")
             multi = dict(multi, enc_frames=U)
-        if getattr(self, "native_qformer", True):
+        if self.native_qformer:
             comp = self._compress_native(enc, F, Nf, qtable, qs, prompt_ids, multi)
             if keep is not None:
                 keep.update(compressed=comp)
@@ -966,11 +979,8 @@ class VideoEncoder:
         cache: a FrameCache (new_cache): frames whose content it holds skip the towers and the connector, new ones are stored -
         the result is bit for bit that of cache=None (encode_video_cached).  keep= bypasses the cache (its per-kernel
         connector form is what produces the stage tensors)."""
-        if cache is not None and keep is None:
-            return encode_video_cached(self, cache, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens,
-                                       prompt_ids, audio, frame_cap, splice, video_index, info)
         return encode_video_with(self, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids,
-                                 audio, frame_cap, keep, splice, video_index, info)
+                                 audio, frame_cap, keep, splice, video_index, info, cache)
 
     def encode_video_prompts(self, px_siglip, px_dino, image_size, prompts, audio=None, frame_cap=224, video_index=None,
                              infos=None, cache=None, max_prompts=8, pad_fraction=0.25):
@@ -985,612 +995,3 @@ class VideoEncoder:
         `image`; -> one result per sample, bit for bit what encode_video (an image: the mixin's image branch) returns for it.
         infos: one info dict per sample (encode_batch_with).  All samples share the pixel geometry and type."""
         return encode_batch_with(self, samples, frame_cap, infos)
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# Orchestration over an "engine" (VideoEncoder on GPUs; the gloo tests of dist.py plug in a CPU test double that
-# implements tower / sims_tensor / connector / with_audio / make_queries / compress_frames / emit / query_width).
-# Each policy decision of the video path has one function below, called by the serial and the sharded (dist.py) path.
-def visual_budget(cfg, n_text_tokens):
-    """max_visual_len of a sample with n_text_tokens non-image tokens (tdc/cambrian_arch.py:1499-1505)"""
-    return cfg["tokenizer_model_max_length"] - cfg.get("inference_max_length", 16) - n_text_tokens
-
-
-def emission_plan(e, T, Nf, seg_indices, max_visual_len):
-    """a11-a19 -> (segment.emit_plan, whether all chunks share the learned query block: cambrian_arch.py:1639-1640)"""
-    cfg = getattr(e, "cfg", {})
-    return (seg.emit_plan(T, Nf, e.K, seg_indices, max_visual_len, cfg.get("add_static", True)),
-            cfg.get("query_type", "Avg_pool") == "learned")
-
-
-def text_prompt(cfg, prompt_ids):
-    """the Q-Former's text prompt: the sample's BERT ids, or none when `text_input` is off"""
-    return prompt_ids if cfg.get("text_input", True) else None
-
-
-def compress_with(e, X, T, N, seg_indices, prompt_ids, max_visual_len, audio=None, keep=None, splice=None, info=None):
-    Xf, Nf = e.with_audio(X, T, N, audio)
-    plan, learned = emission_plan(e, T, Nf, seg_indices, max_visual_len)
-    return compress_planned(e, Xf, N, Nf, plan, learned, prompt_ids, keep, splice, info)
-
-
-def compress_planned(e, Xf, N, Nf, plan, learned, prompt_ids, keep=None, splice=None, info=None):
-    """compress_with after its planning: one prompt's Q-Former pass and emission over the rows Xf (with_audio) by `plan`"""
-    comp = None
-    if plan["comp_frames"]:
-        if learned:
-            qtable, qsrc = e.learned_queries(), [0] * len(plan["comp_frames"])
-        else:
-            qtable, qsrc = e.make_queries(Xf, N, Nf, plan["key_frames"]), plan["comp_chunk"]
-        comp = e.compress_frames(Xf, Nf, plan["comp_frames"], qtable, qsrc, prompt_ids, keep)
-    pairs = seg.emit_pairs(plan, Nf, e.K)
-    if keep is not None:
-        keep["plan"] = plan
-        keep["n_visual"] = len(pairs)
-    if info is not None:
-        info["n_visual"] = len(pairs)
-    if splice is not None:
-        return e.emit(Xf, comp, pairs, splice)
-    return e.emit(Xf, comp, pairs)
-
-
-# ---- several prompts about one video in one compressor pass (DESIGN.md section 12) ------------------------------------------
-MULTI_PROMPT_MAX_ROWS = 255     # K + Lmax of a group: below the 256 query rows from which tdc_attention's AUTO form changes kernels
-
-
-def prompt_groups(selections, text_lens, frames, K, max_prompts, pad_fraction=0.25, max_rows=MULTI_PROMPT_MAX_ROWS):
-    """`config.tdc_batch_prompts`: prompts p = 0 .. P-1 grouped greedily in call order.  A prompt joins the open group of its
-    a1 selection (selections[p], any hashable) while the group holds fewer than max_prompts, its frame stride K + Lmax stays
-    within max_rows, and its padding rows sum_p (Lmax - text_lens[p]) * frames[p] stay within pad_fraction of its
-    sum_p (K + Lmax) * frames[p] rows; otherwise that group is closed and the prompt opens a new one.  -> lists of prompt
-    indices ordered by their first member; a group of one runs the single-prompt path (compress_with)."""
-    if max_prompts < 1:
-        raise ValueError("max_prompts must be >= 1")
-    groups, open_of = [], {}
-    for p, key in enumerate(selections):
-        g = open_of.get(key)
-        if g is not None and len(g) < max_prompts:
-            members = g + [p]
-            Lmax = max(text_lens[i] for i in members)
-            pad = sum((Lmax - text_lens[i]) * frames[i] for i in members)
-            rows = sum((K + Lmax) * frames[i] for i in members)
-            if K + Lmax <= max_rows and pad <= pad_fraction * rows:
-                g.append(p)
-                continue
-        g = [p]
-        groups.append(g)
-        open_of[key] = g
-    return groups
-
-
-def prompt_maps(plans, learned=False):
-    """The index maps of one group (the prompts' seg.emit_plan Plans over ONE video): the distinct compressed frames
-    `enc_frames` and distinct key frames `key_frames` (both ascending), and per VIRTUAL frame - the compressed frames of prompt
-    0, then prompt 1, ... - kv_src (position of its frame in enc_frames), qsrc (position of its chunk's key frame in
-    key_frames; 0 with the shared learned query block), frame_prompt; offsets[p] = first virtual frame of prompt p."""
-    enc_frames = sorted({f for pl in plans for f in pl["comp_frames"]})
-    key_frames = sorted({pl["key_frames"][c] for pl in plans for c in pl["comp_chunk"]})
-    upos = {f: i for i, f in enumerate(enc_frames)}
-    kpos = {f: i for i, f in enumerate(key_frames)}
-    kv_src, qsrc, frame_prompt, offsets = [], [], [], []
-    for p, pl in enumerate(plans):
-        offsets.append(len(kv_src))
-        for f, c in zip(pl["comp_frames"], pl["comp_chunk"]):
-            kv_src.append(upos[f])
-            qsrc.append(0 if learned else kpos[pl["key_frames"][c]])
-            frame_prompt.append(p)
-    offsets.append(len(kv_src))
-    return dict(enc_frames=enc_frames, key_frames=key_frames, kv_src=kv_src, qsrc=qsrc, frame_prompt=frame_prompt,
-                offsets=offsets)
-
-
-def compress_many_with(e, X, T, N, seg_indices, prompts, audio=None, infos=None, max_prompts=8, pad_fraction=0.25):
-    """a11-a19 for several prompts over ONE video's connector rows X (audio: the a20 tokens, as compress_with takes them):
-    prompts = dicts of n_text_tokens, prompt_ids, optional splice -> one emitted tensor per prompt, bit for bit compress_with's.
-    Per group (prompt_groups) the distinct compressed frames are gathered and projected to K/V once, the distinct key frames
-    pooled once, and ONE Q-Former pass runs over the prompts' virtual frames (prompt_maps); a group of one, and every group on
-    an engine whose compress_frames cannot take the form (multi_prompt_ok), runs compress_with."""
-    cfg = getattr(e, "cfg", {})
-    K = e.K
-    P = len(prompts)
-    pids = [text_prompt(cfg, p["prompt_ids"]) for p in prompts]
-    Xf, Nf = e.with_audio(X, T, N, audio)
-    planned = [emission_plan(e, T, Nf, seg_indices, visual_budget(cfg, p["n_text_tokens"])) for p in prompts]
-    plans, learned = [pl for pl, _ in planned], (planned[0][1] if planned else False)
-    lens = [len(i) if i is not None else 0 for i in pids]
-    groups = prompt_groups([0] * P, lens, [len(pl["comp_frames"]) for pl in plans], K, max_prompts, pad_fraction)
-    ok = getattr(e, "multi_prompt_ok", lambda nf: True)(Nf)
-    out = [None] * P
-    for gi, g in enumerate(groups):
-        gplans = [plans[p] for p in g]
-        multi = ok and len(g) > 1 and all(pl["comp_frames"] for pl in gplans)
-        Lmax = max(lens[p] for p in g)
-        maps = prompt_maps(gplans, learned) if multi else None
-        if multi:
-            qtable = e.learned_queries() if learned else e.make_queries(Xf, N, Nf, maps["key_frames"])
-            comp = e.compress_frames(Xf, Nf, maps["enc_frames"], qtable, maps["qsrc"], [pids[p] or [] for p in g], None,
-                                     dict(kv_src=maps["kv_src"], frame_prompt=maps["frame_prompt"]))
-        for j, p in enumerate(g):
-            info = infos[p] if infos is not None else None
-            splice = prompts[p].get("splice")
-            if not multi:                                         # today's path, on the plan made above
-                out[p] = compress_planned(e, Xf, N, Nf, plans[p], learned, pids[p], None, splice, info)
-                if info is not None:
-                    info["prompts"] = dict(group=gi, group_size=1, pad_rows=0, shared_kv_frames=len(plans[p]["comp_frames"]))
-                continue
-            lo, hi = maps["offsets"][j], maps["offsets"][j + 1]
-            pairs = seg.emit_pairs(plans[p], Nf, K)
-            out[p] = e.emit(Xf, comp[lo * K:hi * K], pairs, splice) if splice is not None else \
-                e.emit(Xf, comp[lo * K:hi * K], pairs)
-            if info is not None:
-                info["n_visual"] = len(pairs)
-                info["prompts"] = dict(group=gi, group_size=len(g), pad_rows=(Lmax - lens[p]) * len(plans[p]["comp_frames"]),
-                                       shared_kv_frames=len(maps["enc_frames"]))
-    return out
-
-
-def encode_video_prompts_with(e, px_siglip, px_dino, image_size, prompts, audio=None, frame_cap=224, video_index=None,
-                              infos=None, cache=None, max_prompts=8, pad_fraction=0.25):
-    """Several prompts about ONE video -> one result per prompt, bit for bit what encode_video(...) returns for it.  The towers,
-    a5 and the connector run once per distinct a1 selection (through `cache` when one is given); the prompts of a selection go
-    through compress_many_with.  prompts: dicts of budget_text_len, n_text_tokens, prompt_ids, optional splice.  infos: one dict
-    per prompt, filled as encode_video's info= plus info["prompts"] (the selection's front facts - info["cache"] among them -
-    are those of the ONE front pass the selection's prompts share)."""
-    cfg = e.cfg
-    T0 = px_siglip.shape[0]
-    sels, order = {}, []
-    for p, pr in enumerate(prompts):
-        key = tuple(frame_indices(cfg, T0, pr["budget_text_len"], frame_cap))                       # a1
-        if key not in sels:
-            sels[key] = []
-            order.append(key)
-        sels[key].append(p)
-    out = [None] * len(prompts)
-    base = 0
-    for key in order:
-        members = sels[key]
-        btl = prompts[members[0]]["budget_text_len"]
-        finfo = {} if infos is not None else None
-        f = None
-        if cache is not None:
-            f = video_front_cached(e, cache, px_siglip, px_dino, image_size, btl, audio, frame_cap, video_index, finfo)
-        if f is None:
-            f = video_front_with(e, px_siglip, px_dino, image_size, btl, audio, frame_cap, None, video_index, finfo)
-        sub = [infos[p] for p in members] if infos is not None else None
-        res = compress_many_with(e, f["X"], f["T"], f["N"], f["seg_idx"], [prompts[p] for p in members], f["audio"], sub,
-                                 max_prompts, pad_fraction)
-        for p, r in zip(members, res):
-            out[p] = r
-            if infos is not None:
-                info = infos[p]
-                info.update(finfo)
-                info.update(frame_indices=f["idx"], selected=list(range(f["T"])), seg_indices=f["seg_idx"],
-                            final_size=f["final_size"])
-                if "cache_info" in f:
-                    info["cache"] = f["cache_info"]()
-                info["prompts"]["group"] += base
-        if infos is not None and members:
-            base = max(infos[p]["prompts"]["group"] for p in members) + 1
-    return out
-
-
-def content_key(e, v):
-    """hashable identity of an audio entry's content: tensors by shape, type and the 128-bit fingerprint of their bytes"""
-    if torch.is_tensor(v):
-        if v.numel() == 0:
-            return ("tensor", str(v.dtype), tuple(v.shape))
-        d = v.detach().to(e.dev).contiguous().view(-1)
-        return ("tensor", str(v.dtype), tuple(v.shape), tuple(e.fingerprint(d, [0], d.numel() * d.element_size(), 0)[0]))
-    if isinstance(v, dict):
-        return ("dict",) + tuple((k, content_key(e, v[k])) for k in sorted(v))
-    if isinstance(v, (list, tuple)):
-        return ("list",) + tuple(content_key(e, x) for x in v)
-    return ("value", repr(v))
-
-
-def same_video_key(e, px_siglip, px_dino, image_size, budget_text_len, frame_cap, audio=None, video_index=None):
-    """`config.tdc_batch_prompts`: what two samples of one call must share to be questions about the SAME video - the frame
-    cache's key material (FrameCache.frame_keys: the fingerprints of their a1-selected pixels, pixel geometry, image_size), and
-    the content of their audio with the seconds it is sampled at.  Frames a1 drops are never read, so they do not count."""
-    from .cache import FrameCache
-    idx = frame_indices(e.cfg, px_siglip.shape[0], budget_text_len, frame_cap)
-    keys, _ = FrameCache.frame_keys(e, px_siglip.to(e.dev), px_dino.to(e.dev), idx, image_size)
-    akey = None
-    if audio is not None:
-        akey = (content_key(e, audio), tuple(sample_indicator(px_siglip.shape[0], idx, video_index)))
-    return (px_siglip.shape[0], tuple(idx), tuple(keys), akey)
-
-
-def frame_indices(cfg, T0, budget_text_len, frame_cap):
-    """a1 (tdc/cambrian_arch.py:899-916): the input frames kept, at most frame_cap (a5's second cap, :813-822, keeps all)"""
-    return seg.uniform_indices(T0, min(seg.get_max_num_frames(budget_text_len, cfg), frame_cap))
-
-
-def sample_indicator(T0, idx, video_index=None):
-    """`sample_indices` of tdc/cambrian_arch.py:916-930: one 0/1 entry per second of the video's audio, 1 where a frame
-    that survives the a1 cap was sampled.  video_index = the caller's `video_indices[i]` (0/1 per second, 1 = a frame was
-    decoded there; None: input frame t is second t)."""
-    if video_index is None:
-        samp = [0] * T0
-        for i in idx:
-            samp[i] = 1
-        return samp
-    vi = [int(v) for v in (video_index.tolist() if hasattr(video_index, "tolist") else video_index)]
-    if len(idx) == T0:
-        return vi
-    pos = [i for i, v in enumerate(vi) if v == 1]
-    samp = [0] * len(vi)
-    for i in idx:
-        samp[pos[i]] = 1
-    return samp
-
-
-def start_side_tower(e, px_siglip):
-    """`two_streams`, before the DINOv2 tower: SigLIP on the engine's side stream fills the partly filled last tile rounds of
-    the other tower's GEMMs (T = 64: +0.6-1.1 %).  -> (stream, features) for join_side_tower, or None (off, host tensors)."""
-    if not (getattr(e, "two_streams", False) and px_siglip.is_cuda):
-        return None
-    side = e.tower_stream() if hasattr(e, "tower_stream") else torch.cuda.Stream(device=px_siglip.device)
-    side.wait_stream(torch.cuda.current_stream(px_siglip.device))
-    with torch.cuda.stream(side):
-        return side, e.tower("siglip", px_siglip)
-
-
-def join_side_tower(e, started, px_siglip):
-    """-> the SigLIP features for the compute stream: start_side_tower's, joined, or enqueued now if it started none"""
-    if started is None:
-        return e.tower("siglip", px_siglip)
-    side, sig = started
-    torch.cuda.current_stream(sig.device).wait_stream(side)
-    sig.record_stream(torch.cuda.current_stream(sig.device))
-    return sig
-
-
-def select_segments_with(e, sims, refine, info=None):
-    """a5 (tdc/cambrian_arch.py:832-849) on the T - 1 host similarities.  With engine.selection_eps, the pairs whose order that
-    error leaves open (segment.selection_band) are re-ranked on refine(band) -> their fp16-tower similarities in band order,
-    unless the band is a plateau (segment.band_allowed).  info receives refined_pairs and refine_skipped_pairs."""
-    mns = e.cfg.get("max_num_segments", 24)
-    eps = getattr(e, "selection_eps", None)
-    band = seg.selection_band(sims, mns, eps) if eps else []
-    if band and not seg.band_allowed(band, len(sims) + 1, getattr(e, "selection_max_fraction", 0.125)):
-        if info is not None:
-            info["refine_skipped_pairs"] = len(band)
-        band = []
-    if info is not None:
-        info["refined_pairs"] = list(band)
-    return seg.select_refined(sims, mns, eps, band, refine(band)) if band else seg.select_segments(sims, mns)
-
-
-def precise_features(e, px_dino, frames, lo=0):
-    """{frame: its feature rows from the fp16-operand DINOv2 tower} for the ascending `frames` (pixels: px_dino[frame - lo])"""
-    fp = e.precise_dino(px_dino[torch.tensor([f - lo for f in frames], device=px_dino.device)])
-    Pp = fp.shape[0] // len(frames)
-    return {f: fp[j * Pp:(j + 1) * Pp] for j, f in enumerate(frames)}
-
-
-def video_front_with(e, px_siglip, px_dino, image_size, budget_text_len, audio=None, frame_cap=224, keep=None,
-                     video_index=None, info=None):
-    """the prompt-independent part of encode_video_with (a1-a10, a20): -> dict(X, T, N, seg_idx, audio, idx, final_size, sig,
-    dino).  Only a1 reads the prompt (through budget_text_len)."""
-    cfg = e.cfg
-    T0 = px_siglip.shape[0]
-    idx = frame_indices(cfg, T0, budget_text_len, frame_cap)                                        # a1
-    if len(idx) != T0:
-        sel = torch.tensor(idx, device=px_siglip.device)
-        px_siglip, px_dino = px_siglip[sel], px_dino[sel]
-    T = len(idx)
-    side_sig = start_side_tower(e, px_siglip)
-    dino = e.tower("dino", px_dino)                                                                 # a4
-    sig = None
-    if T <= cfg.get("max_num_segments", 24) + 1:                                                    # a5
-        seg_idx = list(range(T))
-    else:
-        sims_dev = e.sims_tensor(dino, T)
-        ev = e.mark() if hasattr(e, "mark") and sims_dev.is_cuda else None
-        if side_sig is None:
-            # the SigLIP tower does not depend on the selection: enqueue it BEFORE the one host read of the similarities, so
-            # the device keeps working while the host ranks them (a3) - read on a side stream (fetch): no wait for the tower
-            sig = e.tower("siglip", px_siglip)
-        sims = e.fetch(sims_dev, ev) if ev is not None else sims_dev.tolist()
-
-        def refine(band):
-            return e.pair_sims(precise_features(e, px_dino, seg.band_frames(band)), [(i, i + 1) for i in band]).tolist()
-        seg_idx = select_segments_with(e, sims, refine, info)
-    if sig is None:
-        sig = join_side_tower(e, side_sig, px_siglip)                                               # a3
-    sizes = [tuple(image_size)] * T
-    X, final_size = e.connector(sig, dino, T, sizes, keep)                                          # a6-a10
-    N = X.shape[0] // T
-    if audio is not None:                                                                           # a20
-        audio = e.local_audio(audio, sample_indicator(T0, idx, video_index), T, 0, T)
-    return dict(X=X, T=T, N=N, seg_idx=seg_idx, audio=audio, idx=idx, final_size=final_size, sig=sig, dino=dino)
-
-
-def encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio=None,
-                      frame_cap=224, keep=None, splice=None, video_index=None, info=None):
-    cfg = e.cfg
-    f = video_front_with(e, px_siglip, px_dino, image_size, budget_text_len, audio, frame_cap, keep, video_index, info)
-    X, T, N, seg_idx, idx, final_size = f["X"], f["T"], f["N"], f["seg_idx"], f["idx"], f["final_size"]
-    max_visual_len = visual_budget(cfg, n_text_tokens)
-    pid = text_prompt(cfg, prompt_ids)
-    vis = compress_with(e, X, T, N, seg_idx, pid, max_visual_len, f["audio"], keep, splice, info)   # a11-a19 (+a21)
-    if keep is not None:                    # selected: what a5's second frame cap keeps - every frame (frame_indices)
-        keep.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, siglip_feat=f["sig"], dino_feat=f["dino"],
-                    final_size=final_size, X=X)
-    if info is not None:
-        info.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, final_size=final_size)
-    return vis
-
-
-def batch_groups(frames, ceiling, keys=None):
-    """`config.tdc_batch_frames`: the samples of one call grouped greedily in batch order, the a1-selected frames of a group
-    (frames[i]; images count 1) summing to at most `ceiling`; a sample above the ceiling forms its own group, and so does a
-    change of keys[i] (the pixel geometry: frames of one group share one tower input).  -> lists of sample indices"""
-    groups, cur, n = [], [], 0
-    for i, f in enumerate(frames):
-        if cur and (n + f > ceiling or (keys is not None and keys[i] != keys[cur[-1]])):
-            groups.append(cur)
-            cur, n = [], 0
-        cur.append(i)
-        n += f
-    if cur:
-        groups.append(cur)
-    return groups
-
-
-def gather_frames(pxs, plans, device):
-    """the frames plans[j] of every pixel tensor pxs[j], in order, as one [sum, 3, H, W] tensor on `device`.  Each kept frame is
-    copied once: from a host tensor that copy is the upload itself, on the device it is the a1 index copy (whole tensors when
-    every frame is kept)."""
-    px0 = pxs[0]
-    out = torch.empty((sum(len(p) for p in plans),) + tuple(px0.shape[1:]), dtype=px0.dtype, device=device)
-    o = 0
-    for px, idx in zip(pxs, plans):
-        if tuple(px.shape[1:]) != tuple(px0.shape[1:]) or px.dtype != px0.dtype:
-            raise ValueError("a batch shares one tower input: pixels %s %s and %s %s differ"
-                             % (tuple(px0.shape[1:]), px0.dtype, tuple(px.shape[1:]), px.dtype))
-        dst = out[o:o + len(idx)]
-        if len(idx) == px.shape[0]:
-            dst.copy_(px)
-        elif px.device == out.device:
-            torch.index_select(px, 0, torch.tensor(idx, device=px.device), out=dst)
-        else:
-            dst.copy_(px[torch.tensor(idx)])
-        o += len(idx)
-    return out
-
-
-def encode_batch_with(e, samples, frame_cap, infos=None):
-    """Several samples in one tower and connector pass (`config.tdc_batch_frames`), each result bit for bit that of its own
-    encode_video_with call (an image: its connector rows [:, :H], as prepare_inputs_labels_for_multimodal's image branch).
-    samples: dicts of encode_video's arguments - px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids,
-    audio, video_index, splice - and `image` (True: one static frame, no a1 / a5 / Q-Former).  infos: one dict per sample
-    (or None) that receives what encode_video's info= does (images: final_size).  -> list of per-sample results.
-    a1 runs per sample; the kept frames of all samples go through one DINOv2 and one SigLIP pass; a5 takes the in-sample
-    adjacent pairs of one similarity launch over the group (the cross-sample pairs are dropped) read to the host once, and
-    selects (and refines, on the sample's own pixels) per sample; one connector call takes every frame's image_size and its
-    rows are split by the returned sizes; a20, a11-a19 and the a21 hand-off run per sample.  This rests on tower batch
-    invariance, the per-pair cos-sim reduction and the per-frame connector."""
-    cfg = e.cfg
-    mns = cfg.get("max_num_segments", 24)
-    plans = [[0] if s.get("image") else frame_indices(cfg, s["px_siglip"].shape[0], s["budget_text_len"], frame_cap)
-             for s in samples]                                                                      # a1
-    offs = [0]
-    for idx in plans:
-        offs.append(offs[-1] + len(idx))
-    Tg = offs[-1]
-    dev = getattr(e, "dev", samples[0]["px_siglip"].device)
-    px_s = gather_frames([s["px_siglip"] for s in samples], plans, dev)
-    px_d = gather_frames([s["px_dino"] for s in samples], plans, dev)
-    segmented = [not s.get("image") and len(idx) > mns + 1 for s, idx in zip(samples, plans)]
-    side_sig = start_side_tower(e, px_s)
-    dino = e.tower("dino", px_d)                                                                    # a4
-    sig = None
-    sims = None
-    if any(segmented):                                                                              # a5
-        sims_dev = e.sims_tensor(dino, Tg)
-        ev = e.mark() if hasattr(e, "mark") and sims_dev.is_cuda else None
-        if side_sig is None:
-            sig = e.tower("siglip", px_s)           # enqueued before the one host read, as in encode_video_with
-        sims = e.fetch(sims_dev, ev) if ev is not None else sims_dev.tolist()
-    seg_idx = []
-    for j, idx in enumerate(plans):
-        T, o = len(idx), offs[j]
-        if not segmented[j]:
-            seg_idx.append(list(range(T)))
-            continue
-
-        def refine(band, o=o):
-            return e.pair_sims(precise_features(e, px_d, seg.band_frames(band), -o), [(i, i + 1) for i in band]).tolist()
-        seg_idx.append(select_segments_with(e, sims[o:o + T - 1], refine, infos[j] if infos is not None else None))
-    if sig is None:
-        sig = join_side_tower(e, side_sig, px_s)                                                    # a3
-    sizes = [tuple(s["image_size"]) for s, idx in zip(samples, plans) for _ in idx]
-    X, final_size = e.connector(sig, dino, Tg, sizes)                                               # a6-a10
-    out, r = [], 0
-    for j, (s, idx) in enumerate(zip(samples, plans)):
-        T, o = len(idx), offs[j]
-        fs = final_size[o:o + T]
-        n = sum(h * (w + 1) for h, w in fs)          # unpad_newline: h rows of w tokens + a newline each
-        Xs = X[r:r + n]
-        r += n
-        info = infos[j] if infos is not None else None
-        if s.get("image"):
-            out.append(Xs[:, :e.H])
-            if info is not None:
-                info["final_size"] = fs
-            continue
-        audio = s.get("audio")
-        if audio is not None:                                                                       # a20
-            audio = e.local_audio(audio, sample_indicator(s["px_siglip"].shape[0], idx, s.get("video_index")), T, 0, T)
-        out.append(compress_with(e, Xs, T, n // T, seg_idx[j], text_prompt(cfg, s["prompt_ids"]),   # a11-a19 (+a21)
-                                 visual_budget(cfg, s["n_text_tokens"]), audio, None, s.get("splice"), info))
-        if info is not None:
-            info.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx[j], final_size=fs)
-    assert r == X.shape[0], "connector rows %d, split %d" % (X.shape[0], r)
-    return out
-
-
-def encode_missing(e, cache, keys, px_siglip, px_dino, idx, image_size, after_dino=None):
-    """the frames idx[j] whose keys[j] the cache lacks (one per distinct key) through the towers and the connector, stored
-    -> those keys, or None when this call's frames do not fit the budget (nothing stored).  after_dino(new keys, their DINOv2
-    rows) is called between the two towers (encode_video_cached enqueues the a5 similarities there)."""
-    new = cache.lookup(keys)
-    if new:
-        first = {}
-        for j, k in enumerate(keys):
-            first.setdefault(k, j)
-        rows = [idx[first[k]] for k in new]
-        if rows == list(range(px_siglip.shape[0])):          # every input frame, in order: no gather copy
-            ps, pd = px_siglip, px_dino
-        else:
-            sel = torch.tensor(rows, device=px_siglip.device)
-            ps, pd = px_siglip[sel], px_dino[sel]
-        dino = e.tower("dino", pd)
-        if after_dino is not None:
-            after_dino(new, dino)
-        sig = e.tower("siglip", ps)
-        Xn, fsz = e.connector(sig, dino, len(new), [tuple(image_size)] * len(new))
-        if not cache.store(new, Xn, dino, fsz, set(keys)):
-            return None
-    return new
-
-
-def encode_image_cached(e, cache, px_siglip, px_dino, image_size):
-    """a single image ([1, 3, H, W] each) through the frame cache: (connector rows [N, Hp], [final size]) - what
-    e.connector(e.tower(...), e.tower(...), 1, [image_size]) returns, bit for bit"""
-    cache.bind(e)
-    keys, _ = cache.frame_keys(e, px_siglip, px_dino, [0], image_size)
-    if encode_missing(e, cache, keys, px_siglip, px_dino, [0], image_size) is None:
-        return e.connector(e.tower("siglip", px_siglip), e.tower("dino", px_dino), 1, [tuple(image_size)])
-    return cache.assemble(e, keys), cache.final_sizes(keys)
-
-
-def cached_audio(e, cache, audio, sample_indices, T, lo=0, hi=None):
-    """a20 of encode_video_cached: local_audio(audio, sample_indices, T, lo, hi), with the BEATs windows of a raw waveform taken
-    from the cache where it holds their waveform and mask slices (keys: fingerprints of the slices; window features are
-    item-wise).  [lo, hi): the frames of one rank of the frame-sharded path (dist.py) - only their windows are used."""
-    hi = T if hi is None else hi
-    if not (isinstance(audio, dict) and audio.get("audio_tokens") is None and audio.get("beats_windows") is None
-            and audio.get("audio_wav") is not None and getattr(e, "beats", None) is not None):
-        return e.local_audio(audio, sample_indices, T, lo, hi)
-    from .beats import SAMPLE_RATE
-    wav, mask = audio["audio_wav"], audio.get("audio_wav_mask")
-    n_s = wav.shape[1]
-    starts = e.beats.window_starts(n_s)
-    sizes = e.beats.window_token_counts(n_s)
-    plan = seg.audio_plan(sizes, [int(v) for v in sample_indices])
-    need = sorted({w for i in range(lo, min(hi, T, len(plan))) for (w, _, _) in plan[i][0]})
-    if not need:
-        return e.local_audio(audio, sample_indices, T, lo, hi)
-    m = None if mask is None else torch.as_tensor(mask).bool().cpu()
-    if m is not None and not bool(m.any()):
-        m = None                                                  # what window_features does with an all-False mask
-    n, eb = SAMPLE_RATE * 10, wav.element_size()
-    wd = wav if wav.is_cuda else wav.to(e.dev)                    # fingerprinted on the device (a host waveform is copied)
-    keys = {}
-    for w in need:
-        a, b = SAMPLE_RATE * starts[w], min(n_s, SAMPLE_RATE * (starts[w] + 10))
-        mk = None if m is None else tuple(int(v) for v in fingerprint_mask(m[0, a:b]))
-        keys[w] = ("beats", str(wav.dtype), b - a, mk)
-    full = [w for w in need if keys[w][2] == n]
-    fps = {}
-    if full:
-        fps.update(zip(full, e.fingerprint(wd, full, n * eb, n * eb)))
-    for w in need:
-        if w not in fps:
-            fps[w] = e.fingerprint(wd, [1], keys[w][2] * eb, SAMPLE_RATE * starts[w] * eb)[0]
-    keys = {w: keys[w] + (tuple(fps[w]),) for w in need}
-    feats = cache.windows(keys, lambda todo: e.beats_windows(wav, mask, only=todo))
-    return e.audio_tokens(feats, sample_indices, T, lo, hi, window_sizes=sizes)
-
-
-def fingerprint_mask(m):
-    """host fingerprint of a boolean mask slice (the mask lives on the host: window_features reads it there)"""
-    from .cache import fingerprint_rows_host
-    return fingerprint_rows_host(m.to(torch.uint8).numpy()[None])[0]
-
-
-def video_front_cached(e, cache, px_siglip, px_dino, image_size, budget_text_len, audio=None, frame_cap=224,
-                       video_index=None, info=None):
-    """the prompt-independent part of encode_video_cached (a1-a10, a20 through the cache): -> video_front_with's dict plus
-    `cache_info()` (the info["cache"] entry, read after the compressor ran), or None when the call's frames exceed the budget
-    (info["cache"] says bypassed; nothing stored)."""
-    cfg = e.cfg
-    cache.bind(e)
-    T0 = px_siglip.shape[0]
-    idx = frame_indices(cfg, T0, budget_text_len, frame_cap)                                        # a1
-    T = len(idx)
-    keys, dkeys = cache.frame_keys(e, px_siglip, px_dino, idx, image_size)
-    before = cache.stats()
-    segmented = T > cfg.get("max_num_segments", 24) + 1
-    early = {}
-
-    def after_dino(new, dino):
-        # a5 of the pairs whose frames are both new, from the fresh DINOv2 rows, enqueued BEFORE the SigLIP tower: the host
-        # reads them while the tower runs (as encode_video_with does); pairs with a cached frame come from the slab later
-        pos = {k: j for j, k in enumerate(new)}
-        todo = [i for i in range(T - 1) if keys[i] in pos and keys[i + 1] in pos and
-                cache.pair_get((dkeys[i], dkeys[i + 1])) is None]
-        if segmented and todo:
-            slab = dino.view(len(new), dino.shape[0] // len(new), dino.shape[1])
-            early["pairs"] = todo
-            early["read"] = e.slot_sims(slab, [(pos[keys[i]], pos[keys[i + 1]]) for i in todo], defer=True)
-
-    # a3/a4, a6-a10 for the frames the cache lacks; a call whose frames exceed the budget (known once the first frames fixed
-    # the row geometry) runs uncached
-    new = encode_missing(e, cache, keys, px_siglip, px_dino, idx, image_size, after_dino) if cache.fits(keys) else None
-    if new is None:
-        if info is not None:
-            info["cache"] = dict(bypassed=True, frames=T, frames_hit=0, frames_encoded=T, pairs_computed=0)
-        return None
-    if not segmented:                                                                               # a5
-        seg_idx = list(range(T))
-    else:
-        sims = cache.adjacent_sims(e, keys, dkeys, early)
-
-        def precise(pairs):
-            frames = seg.band_frames(pairs)
-            feats = precise_features(e, px_dino, [idx[f] for f in frames])
-            return e.pair_sims(feats, [(idx[i], idx[i + 1]) for i in pairs]).tolist()
-        seg_idx = select_segments_with(e, sims, lambda band: cache.precise_sims(band, dkeys, precise), info)
-    X = cache.assemble(e, keys)
-    N = cache.rows_per_frame
-    final_size = cache.final_sizes(keys)
-    if audio is not None:                                                                           # a20
-        audio = cached_audio(e, cache, audio, sample_indicator(T0, idx, video_index), T)
-
-    def cache_info():
-        after = cache.stats()
-        fresh = set(new)
-        return dict(bypassed=False, frames=T, frames_hit=sum(1 for k in keys if k not in fresh),
-                    frames_encoded=after["frames_encoded"] - before["frames_encoded"],
-                    pairs_computed=after["pairs_computed"] - before["pairs_computed"],
-                    evictions=after["evictions"] - before["evictions"], bytes=after["bytes"],
-                    windows_encoded=after["windows_encoded"] - before["windows_encoded"])
-    return dict(X=X, T=T, N=N, seg_idx=seg_idx, audio=audio, idx=idx, final_size=final_size, cache_info=cache_info)
-
-
-def encode_video_cached(e, cache, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio=None,
-                        frame_cap=224, splice=None, video_index=None, info=None):
-    """encode_video_with through a FrameCache (cache.py), bit for bit the same result: a1 as there; the a1-selected frames are
-    fingerprinted where they lie; only the frames the cache lacks run through the towers and the connector (frames are
-    independent through a3-a10) and are stored; the a5 similarities come from the cache or from the cached DINOv2 rows
-    (tdc_pair_cossim), the refinement's precise values from the cache or from the pixels passed; the connector rows of the kept
-    frames are gathered out of the slab; a20 and the prompt-dependent a11-a19 run as in encode_video_with.  A call whose
-    distinct frames exceed the budget runs encode_video_with and stores nothing.  info["cache"]: what this call reused and
-    encoded.  The tower batches see the HBM the cache holds as taken (auto_tower_batch): the rate may change, not the bits."""
-    cfg = e.cfg
-    f = video_front_cached(e, cache, px_siglip, px_dino, image_size, budget_text_len, audio, frame_cap, video_index, info)
-    if f is None:
-        return encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio,
-                                 frame_cap, None, splice, video_index, info)
-    X, T, N, seg_idx, idx, final_size = f["X"], f["T"], f["N"], f["seg_idx"], f["idx"], f["final_size"]
-    max_visual_len = visual_budget(cfg, n_text_tokens)
-    pid = text_prompt(cfg, prompt_ids)
-    vis = compress_with(e, X, T, N, seg_idx, pid, max_visual_len, f["audio"], None, splice, info)   # a11-a19 (+a21)
-    if info is not None:
-        info.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, final_size=final_size)
-        info["cache"] = f["cache_info"]()
-    return vis
