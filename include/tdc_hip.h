@@ -157,7 +157,9 @@ typedef struct {
     long long q_bs, k_bs, v_bs, o_bs;
     int q_rs, k_rs, v_rs, o_rs;
     int batch, heads, head_dim, sq, sk;
-    float scale; int dtype;
+    float scale; int dtype;       /* scale: finite and >= 0 (TDC_E_BADARG otherwise, nothing is written): the kernels take the
+                                     exponent offset of a row as max(q.k) * scale, which is its largest score only then.
+                                     scale == 0 is valid: every key weighs the same and o is the mean of V (-0.0 counts as 0) */
     /* optional additive score bias, fp32 (NULL = none): score(b,h,q,k) = scale*q.k + gate[(b*sq+q)*gate_rs + h] *
      * bias[h*bias_hs + q*bias_rs + k].  BEATs gated relative position bias
      * (tdc/audio_models/beats/backbone.py:650-661); needs sk % 4 == 0, head_dim <= 64. */
@@ -428,7 +430,7 @@ typedef struct {
     const void* vt; long long ldvt; const float* bv;
     int Nenc;
     const float *ln_g, *ln_b; float eps;
-    int dim, heads; float scale; int dtype;
+    int dim, heads; float scale; int dtype;     /* scale: finite and >= 0, as in tdc_attn_desc; the ctx form does not read it */
     /* ctx != NULL: the OUTPUT-PROJECTION-ONLY form - ctx [F*K, ldctx] 16-bit is the attention output of the flat query rows
      * (row f*K + k), produced by separate launches (q GEMM, tdc_attention); the kernel then computes
      * h[:, :K] = LayerNorm(ctx Wo^T + bo + h[:, :K]) alone: wq / bq / k / vt / bv / Nenc / scale are not read. */

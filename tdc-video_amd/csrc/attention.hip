@@ -377,12 +377,22 @@ extern "C" int tdc_attention(const tdc_attn_desc* d, void* stream) {
         return TDC_E_BADARG;
     }
     if (d->heads > 65535 || d->batch > 65535) return TDC_E_BADARG;
+    // the non-biased kernels take the running maximum as max(raw score) * scale: the row maximum for scale >= 0 only (with a
+    // negative scale it would be the row minimum and P would overflow).  Tested on the bits - all-ones exponent = inf / NaN, sign
+    // bit with anything behind it = negative (-0.0 passes) -: this file is built without NaN semantics
+    const unsigned scale_bits = __builtin_bit_cast(unsigned, d->scale);
+    if ((scale_bits & 0x7f800000u) == 0x7f800000u || scale_bits > 0x80000000u) {
+        fprintf(stderr, "[tdc_hip] tdc_attention: scale must be finite and >= 0\n");
+        return TDC_E_BADARG;
+    }
     AttnArgs a;
     a.q = d->q; a.k = d->k; a.v = d->v; a.o = d->o;
     a.q_bs = d->q_bs; a.k_bs = d->k_bs; a.v_bs = d->v_bs; a.o_bs = d->o_bs;
     a.q_rs = d->q_rs; a.k_rs = d->k_rs; a.v_rs = d->v_rs; a.o_rs = d->o_rs;
     a.heads = d->heads; a.d = d->head_dim; a.sq = d->sq; a.sk = d->sk;
-    a.scale_log2 = d->scale * 1.4426950408889634f;
+    // scale == 0 (every key weighs the same): the smallest normal float instead of 0, so that the -inf of a masked key stays
+    // -inf through fma(s, c, -m) (0 * -inf is NaN) while every real key's exponent argument still rounds to 0, P = 1 exactly
+    a.scale_log2 = d->scale == 0.f ? 1.17549435e-38f : d->scale * 1.4426950408889634f;
     auto al = [](const void* p, int bytes) { return ((uintptr_t)p % bytes) == 0; };
     a.vec_ok = (d->head_dim % 8 == 0) && (d->head_dim >= 8) && (d->q_rs % 8 == 0) && (d->k_rs % 8 == 0) && (d->v_rs % 8 == 0) &&
                (d->o_rs % 4 == 0) && (d->q_bs % 8 == 0) && (d->k_bs % 8 == 0) && (d->v_bs % 8 == 0) &&

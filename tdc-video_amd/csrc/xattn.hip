@@ -573,6 +573,13 @@ extern "C" int tdc_qformer_xattn(const tdc_xattn_desc* d, void* stream) {
     if (!d || !d->h16 || (!d->h32 && !(out_only && d->res16)) || !d->wo || !d->bo || !d->ln_g || !d->ln_b) return TDC_E_BADARG;
     if (d->res16 && !out_only) return TDC_E_BADARG;
     if (!out_only && (!d->wq || !d->bq || !d->k || !d->vt)) return TDC_E_BADARG;
+    // the exponent offset is max(raw score) * scale: the row maximum for scale >= 0 only (tdc_xattn_desc.scale)
+    // tested on the bits, as in tdc_attention: all-ones exponent = inf / NaN, sign bit with anything behind it = negative
+    const unsigned scale_bits = __builtin_bit_cast(unsigned, d->scale);
+    if (!out_only && ((scale_bits & 0x7f800000u) == 0x7f800000u || scale_bits > 0x80000000u)) {
+        fprintf(stderr, "[tdc_hip] tdc_qformer_xattn: scale must be finite and >= 0\n");
+        return TDC_E_BADARG;
+    }
     if (!tdc_qformer_xattn_supported(d->dim, d->heads, d->K, out_only ? 8 : d->Nenc) || d->F <= 0 || d->S < d->K) {
         fprintf(stderr, "[tdc_hip] tdc_qformer_xattn: unsupported shape (dim=%d heads=%d K=%d Nenc=%d)\n", d->dim, d->heads, d->K,
                 d->Nenc);
@@ -596,7 +603,9 @@ extern "C" int tdc_qformer_xattn(const tdc_xattn_desc* d, void* stream) {
     a.wq = d->wq; a.wo = d->wo; a.bq = d->bq; a.bo = d->bo;
     a.k = d->k; a.ldk = d->ldk; a.vt = d->vt; a.ldvt = d->ldvt; a.bv = d->bv; a.Nenc = d->Nenc;
     a.ln_g = d->ln_g; a.ln_b = d->ln_b; a.eps = d->eps;
-    a.scale_log2 = d->scale * 1.4426950408889634f;
+    // scale == 0 (every key weighs the same): the smallest normal float instead of 0, so that the -inf of a masked key stays
+    // -inf through fma(s, c, -m) (0 * -inf is NaN) while every real key's exponent argument still rounds to 0, P = 1 exactly
+    a.scale_log2 = d->scale == 0.f ? 1.17549435e-38f : d->scale * 1.4426950408889634f;
     a.nblocks = (a.rows + XROWS - 1) / XROWS;
     const int nkt = (d->Nenc + 15) / 16;
     hipStream_t st = (hipStream_t)stream;
