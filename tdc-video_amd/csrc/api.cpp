@@ -50,87 +50,67 @@ VitWs vit_layout(const tdc_vit_model* m, int B, int H, int W) {
 
 #define RET_IF(x) do { int _rc = (x); if (_rc) { fprintf(stderr, "[tdc_hip] %s -> %d (%s:%d)\n", #x, _rc, __FILE__, __LINE__); return _rc; } } while (0)
 
-int gemm(const void* A, int lda, const tdc_lin& L, void* C, int ldc, int M, int dtype, int act, int out_f32,
-         const void* res, int ldres, int res_f32, tdc_rowmap cmap, tdc_rowmap rmap, void* st) {
+// The one builder of tdc_gemm_desc: C[M, L.n] = A[M, L.k] L.w^T + L.b on 16-bit operands and a 16-bit C of type `dtype`, identity
+// row maps.  Whatever else a launch does is named at its call site: Gemm(...).act(a).run(stream).
+struct Gemm {
     tdc_gemm_desc d;
-    memset(&d, 0, sizeof(d));
-    d.A = A; d.lda = lda; d.W = L.w; d.ldw = L.k; d.C = C; d.ldc = ldc; d.bias = L.b; d.res = res; d.ldres = ldres;
-    d.M = M; d.N = L.n; d.K = L.k; d.dtype = dtype; d.out_f32 = out_f32; d.res_f32 = res_f32; d.act = act;
-    d.c_map = cmap; d.r_map = rmap;
-    return tdc_gemm(&d, st);
-}
+    Gemm(const void* A, int lda, const tdc_lin& L, void* C, int ldc, int M, int dtype) {
+        memset(&d, 0, sizeof(d));
+        d.A = A; d.lda = lda; d.W = L.w; d.ldw = L.k; d.C = C; d.ldc = ldc; d.bias = L.b;
+        d.M = M; d.N = L.n; d.K = L.k; d.dtype = dtype;
+    }
+    Gemm& act(int a) { d.act = a; return *this; }
+    Gemm& out_f32() { d.out_f32 = 1; return *this; }
+    Gemm& ldw(int ld) { d.ldw = ld; return *this; }                               // a "weight" whose row stride is not its K
+    Gemm& res(const void* r, int ld, int f32) { d.res = r; d.ldres = ld; d.res_f32 = f32; return *this; }
+    Gemm& a_map(tdc_rowmap m) { d.a_map = m; return *this; }
+    Gemm& c_map(tdc_rowmap m) { d.c_map = m; return *this; }
+    Gemm& r_map(tdc_rowmap m) { d.r_map = m; return *this; }
+    // LayerNorm fusion, consumer side: (mean, rstd) per row and the row sums of the gamma-folded weight; with in_fp8 the same two
+    // operands carry the dequantisation scales (tdc_hip.h)
+    Gemm& fold(const float* stats, const float* c1) { d.ln_stats = stats; d.ln_c1 = c1; return *this; }
+    // ... producer side: the 16-bit copy of the updated rows (NULL over a 16-bit stream) and the per-slot (mean, M2) partials
+    Gemm& emit(void* x16, int ldx16, float* part) { d.x16 = x16; d.ldx16 = ldx16; d.ln_part = part; return *this; }
+    Gemm& in_fp8() { d.in_fp8 = 1; return *this; }
+    // e4m3 output + out_stats for the fp8-operand GEMM (weight scale next_wscale) behind it
+    Gemm& out_fp8(float* out_stats, float w2max, float bmax, float next_wscale) {
+        d.out_fp8 = 1; d.out_stats = out_stats; d.out_w2max = w2max; d.out_bmax = bmax; d.out_wscale = next_wscale;
+        return *this;
+    }
+    Gemm& c16(int type) { d.c16_dtype_p1 = type + 1; return *this; }              // 16-bit C / res of another type than `dtype`
+    Gemm& c_pad8() { d.c_pad8 = 1; return *this; }
+    int run(void* st) const { return tdc_gemm(&d, st); }
+};
 
-// LayerNorm -> e4m3 rows + per-row scales (stats) for an fp8-operand GEMM with per-tensor weight scale `wscale`
-int layernorm_fp8(const float* x, int ldx, void* y8, int ldy8, float* stats, float wscale, const float* g, const float* b,
-                  float eps, int rows, int cols, int dtype, void* st) {
+// The one builder of tdc_ln_desc: LayerNorm over `cols` columns of x [rows, ldx]; the outputs (y16 / y32 / y8) and the rest by name
+struct Ln {
     tdc_ln_desc d;
-    memset(&d, 0, sizeof(d));
-    d.x = x; d.ldx = ldx; d.x_f32 = 1; d.gamma = g; d.beta = b; d.eps = eps;
-    d.rows = rows; d.cols = cols; d.dtype = dtype;
-    d.y8 = y8; d.ldy8 = ldy8; d.y8_stats = stats; d.y8_wscale = wscale;
-    return tdc_layernorm(&d, st);
-}
+    Ln(const void* x, int ldx, int x_f32, const float* g, const float* b, float eps, int rows, int cols, int dtype) {
+        memset(&d, 0, sizeof(d));
+        d.x = x; d.ldx = ldx; d.x_f32 = x_f32; d.gamma = g; d.beta = b; d.eps = eps; d.rows = rows; d.cols = cols; d.dtype = dtype;
+    }
+    Ln& y16(void* y, int ld) { d.y16 = y; d.ldy16 = ld; return *this; }
+    Ln& y32(float* y, int ld) { d.y32 = y; d.ldy32 = ld; return *this; }
+    // e4m3 rows + per-row scales (stats) for an fp8-operand GEMM with per-tensor weight scale `wscale`
+    Ln& y8(void* y, int ld, float* stats, float wscale) { d.y8 = y; d.ldy8 = ld; d.y8_stats = stats; d.y8_wscale = wscale; return *this; }
+    Ln& y_map(tdc_rowmap m) { d.y_map = m; return *this; }
+    Ln& add(const float* table, int ld, int period, int mode) { d.add = table; d.ldadd = ld; d.add_period = period; d.add_mode = mode; return *this; }
+    Ln& x_type(int type) { d.x_dtype_p1 = type + 1; return *this; }               // 16-bit x of another type than `dtype`
+    int run(void* st) const { return tdc_layernorm(&d, st); }
+};
 
-// fp32 residual-stream update x32 += s_a s_w (A8 W8^T) + b on fp8 operands
-int gemm_fp8_rmw(const void* A8, int lda, const tdc_lin& L, float* x32, int ld, int M, int dtype, const float* stats,
-                 const float* zeros, void* st) {
-    tdc_gemm_desc d;
-    memset(&d, 0, sizeof(d));
-    d.A = A8; d.lda = lda; d.W = L.w; d.ldw = L.k; d.C = x32; d.ldc = ld; d.bias = L.b; d.res = x32; d.ldres = ld;
-    d.M = M; d.N = L.n; d.K = L.k; d.dtype = dtype; d.out_f32 = 1; d.res_f32 = 1; d.in_fp8 = 1;
-    d.ln_stats = stats; d.ln_c1 = zeros;
-    return tdc_gemm(&d, st);
-}
-
-// ... over a 16-bit residual stream of type `rt` (tdc_vit_model.res_dtype_p1): x <- T16(s_a s_w acc + bias + float(x))
-int gemm_fp8_rmw16(const void* A8, int lda, const tdc_lin& L, void* x16, int ld, int M, int rt, const float* stats,
-                   const float* zeros, void* st) {
-    tdc_gemm_desc d;
-    memset(&d, 0, sizeof(d));
-    d.A = A8; d.lda = lda; d.W = L.w; d.ldw = L.k; d.C = x16; d.ldc = ld; d.bias = L.b; d.res = x16; d.ldres = ld;
-    d.M = M; d.N = L.n; d.K = L.k; d.dtype = rt; d.in_fp8 = 1;
-    d.ln_stats = stats; d.ln_c1 = zeros;
-    return tdc_gemm(&d, st);
-}
-
-int gemm_fp8(const void* A8, int lda, const tdc_lin& L, void* C, int ldc, int M, int dtype, int act, const float* stats,
-             const float* zeros, void* st) {
-    tdc_gemm_desc d;
-    memset(&d, 0, sizeof(d));
-    d.A = A8; d.lda = lda; d.W = L.w; d.ldw = L.k; d.C = C; d.ldc = ldc; d.bias = L.b;
-    d.M = M; d.N = L.n; d.K = L.k; d.dtype = dtype; d.act = act; d.in_fp8 = 1; d.ln_stats = stats; d.ln_c1 = zeros;
-    return tdc_gemm(&d, st);
-}
-
-// ... with e4m3 output C8 (row stride ldc bytes) + out_stats for the fp8-operand GEMM (weight scale next_wscale) after it
-int gemm_fp8_out8(const void* A8, int lda, const tdc_lin& L, void* C8, int ldc, int M, int dtype, int act, const float* stats,
-                  const float* zeros, float* out_stats, float w2max, float bmax, float next_wscale, void* st) {
-    tdc_gemm_desc d;
-    memset(&d, 0, sizeof(d));
-    d.A = A8; d.lda = lda; d.W = L.w; d.ldw = L.k; d.C = C8; d.ldc = ldc; d.bias = L.b;
-    d.M = M; d.N = L.n; d.K = L.k; d.dtype = dtype; d.act = act; d.in_fp8 = 1; d.ln_stats = stats; d.ln_c1 = zeros;
-    d.out_fp8 = 1; d.out_stats = out_stats; d.out_w2max = w2max; d.out_bmax = bmax; d.out_wscale = next_wscale;
-    return tdc_gemm(&d, st);
-}
-
-// tdc_gemm with the LayerNorm-fusion operands (identity row maps): producer side x16 / part, consumer side stats / c1
-int gemm_ln(const void* A, int lda, const tdc_lin& L, void* C, int ldc, int M, int dtype, int act, int out_f32,
-            const void* res, int ldres, void* x16, int ldx16, float* part, const float* stats, const float* c1, void* st) {
-    tdc_gemm_desc d;
-    memset(&d, 0, sizeof(d));
-    d.A = A; d.lda = lda; d.W = L.w; d.ldw = L.k; d.C = C; d.ldc = ldc; d.bias = L.b; d.res = res; d.ldres = ldres;
-    d.M = M; d.N = L.n; d.K = L.k; d.dtype = dtype; d.out_f32 = out_f32; d.res_f32 = res ? 1 : 0; d.act = act;
-    d.x16 = x16; d.ldx16 = ldx16; d.ln_part = part; d.ln_stats = stats; d.ln_c1 = c1;
-    return tdc_gemm(&d, st);
-}
-
-int layernorm(const float* x, int ldx, void* y16, int ldy, const float* g, const float* b, float eps, int rows,
-              int cols, int dtype, void* st) {
-    tdc_ln_desc d;
-    memset(&d, 0, sizeof(d));
-    d.x = x; d.ldx = ldx; d.x_f32 = 1; d.y16 = y16; d.ldy16 = ldy; d.gamma = g; d.beta = b; d.eps = eps;
-    d.rows = rows; d.cols = cols; d.dtype = dtype;
-    return tdc_layernorm(&d, st);
+// self-attention over a packed qkv buffer [batch * S, ldqkv] (q | k | v at columns 0, D, 2 D) -> o [batch * S, ldo]; k_len: optional
+// per-item key count (tdc_attn_desc.k_len)
+int self_attention(const char* qkv, int ldqkv, void* o, int ldo, int batch, int S, int heads, int head_dim, int D, float scale,
+                   int dtype, void* st, const int* k_len = nullptr) {
+    tdc_attn_desc a;
+    memset(&a, 0, sizeof(a));
+    a.q = qkv; a.k = qkv + (size_t)D * 2; a.v = qkv + (size_t)2 * D * 2; a.o = o;
+    a.q_bs = a.k_bs = a.v_bs = (long long)S * ldqkv; a.o_bs = (long long)S * ldo;
+    a.q_rs = a.k_rs = a.v_rs = ldqkv; a.o_rs = ldo;
+    a.batch = batch; a.heads = heads; a.head_dim = head_dim; a.sq = S; a.sk = S; a.scale = scale; a.dtype = dtype;
+    a.k_len = k_len;
+    return tdc_attention(&a, st);
 }
 
 struct QfWs {
@@ -183,25 +163,6 @@ QfWs qf_layout(const tdc_qformer_model* m, int F, int K, int Lt, int Nenc) {
     return w;
 }
 
-int ln_map(const void* x, int ldx, void* y16, float* y32, int ld, const float* g, const float* b, float eps, int rows,
-           int cols, int dtype, tdc_rowmap ymap, void* st, int x_f32 = 1) {
-    tdc_ln_desc d;
-    memset(&d, 0, sizeof(d));
-    d.x = x; d.ldx = ldx; d.x_f32 = x_f32; d.y16 = y16; d.ldy16 = ld; d.y32 = y32; d.ldy32 = ld; d.gamma = g; d.beta = b;
-    d.eps = eps; d.rows = rows; d.cols = cols; d.dtype = dtype; d.y_map = ymap;
-    return tdc_layernorm(&d, st);
-}
-
-int gemm_full(const void* A, int lda, const tdc_lin& L, void* C, int ldc, int M, int dtype, int act, int out_f32,
-              const void* res, int ldres, int res_f32, tdc_rowmap amap, tdc_rowmap cmap, tdc_rowmap rmap, void* st) {
-    tdc_gemm_desc d;
-    memset(&d, 0, sizeof(d));
-    d.A = A; d.lda = lda; d.W = L.w; d.ldw = L.k; d.C = C; d.ldc = ldc; d.bias = L.b; d.res = res; d.ldres = ldres;
-    d.M = M; d.N = L.n; d.K = L.k; d.dtype = dtype; d.out_f32 = out_f32; d.res_f32 = res_f32; d.act = act;
-    d.a_map = amap; d.c_map = cmap; d.r_map = rmap;
-    return tdc_gemm(&d, st);
-}
-
 }  // namespace
 
 extern "C" size_t tdc_qformer_workspace_bytes(const tdc_qformer_model* m, int F, int K, int Lt, int Nenc) {
@@ -235,7 +196,6 @@ extern "C" int tdc_qformer_fwd(const tdc_qformer_model* m, const void* enc, int 
     float* t32b = (float*)(ws + w.t32b);
     void* mq = ws + w.mq;
     void* mt = ws + w.mt;
-    const tdc_rowmap ident = {0, 0, 0, 0};
     const tdc_rowmap qmap = {K, S, 0, 1};
     const tdc_rowmap tmap = {Lt > 0 ? Lt : 1, S, K, 1};
     hipStream_t st = (hipStream_t)stream;
@@ -264,35 +224,22 @@ extern "C" int tdc_qformer_fwd(const tdc_qformer_model* m, const void* enc, int 
     if (fused) {
         // keys of all cross layers: one GEMM; values of all cross layers TRANSPOSED: one GEMM with the operands swapped
         // (A = Wv [n_cross*dim, H], "weight" = enc [F*Nenc, H]) - vt[c][f*Nenc + key], the A operand of the PV product
-        RET_IF(gemm_full(enc, ldenc, m->cross_k, kv, m->cross_k.n, F * Nenc, dt, TDC_ACT_NONE, 0, nullptr, 0, 0, ident,
-                         ident, ident, stream));
-        tdc_gemm_desc d;
-        memset(&d, 0, sizeof(d));
-        d.A = m->cross_v.w; d.lda = m->cross_v.k; d.W = enc; d.ldw = ldenc; d.C = ws + w.vt; d.ldc = (int)w.ldvt;
-        d.M = m->cross_v.n; d.N = F * Nenc; d.K = m->cross_v.k; d.dtype = dt; d.c_pad8 = 1;
-        RET_IF(tdc_gemm(&d, stream));
+        RET_IF(Gemm(enc, ldenc, m->cross_k, kv, m->cross_k.n, F * Nenc, dt).run(stream));
+        const tdc_lin enc_t = {enc, nullptr, F * Nenc, m->cross_v.k};
+        RET_IF(Gemm(m->cross_v.w, m->cross_v.k, enc_t, ws + w.vt, (int)w.ldvt, m->cross_v.n, dt).ldw(ldenc).c_pad8().run(stream));
     } else {
-        RET_IF(gemm_full(enc, ldenc, m->cross_kv, kv, m->cross_kv.n, U * Nenc, dt, TDC_ACT_NONE, 0, nullptr, 0, 0, ident,
-                         ident, ident, stream));
+        RET_IF(Gemm(enc, ldenc, m->cross_kv, kv, m->cross_kv.n, U * Nenc, dt).run(stream));
     }
     }
     const float scale = (float)(1.0 / sqrt((double)hd));          // float(hd ** -0.5), correctly rounded (1.0f / sqrtf is 1 ulp off at 72, 96)
     for (int l = 0; l < m->n_layers; ++l) {
         const tdc_qformer_layer& L = m->layers_host[l];
         bool q16 = false;   // this layer's query rows between the cross-attention output and the FFN LayerNorm: 16-bit only (t32 holds 16-bit rows)
-        RET_IF(gemm_full(h16, Dp, L.qkv, qkv, L.qkv.n, rows, dt, TDC_ACT_NONE, 0, nullptr, 0, 0, ident, ident, ident,
-                         stream));
-        tdc_attn_desc a;
-        memset(&a, 0, sizeof(a));
-        a.q = qkv; a.k = qkv + (size_t)D * 2; a.v = qkv + (size_t)2 * D * 2; a.o = ctx;
-        a.q_bs = a.k_bs = a.v_bs = (long long)S * L.qkv.n; a.o_bs = (long long)S * Dp;
-        a.q_rs = a.k_rs = a.v_rs = L.qkv.n; a.o_rs = Dp;
-        a.batch = F; a.heads = m->heads; a.head_dim = hd; a.sq = S; a.sk = S; a.scale = scale; a.dtype = dt;
-        if (mp) a.k_len = mp->self_len;     // a frame's text rows end at K + its own prompt's length
-        RET_IF(tdc_attention(&a, stream));
-        RET_IF(gemm_full(ctx, Dp, L.attn_out, t32, Dp, rows, dt, TDC_ACT_NONE, 1, h32, Dp, 1, ident, ident, ident,
-                         stream));
-        RET_IF(ln_map(t32, Dp, h16, h32, Dp, L.attn_ln_g, L.attn_ln_b, m->eps, rows, D, dt, ident, stream));
+        RET_IF(Gemm(h16, Dp, L.qkv, qkv, L.qkv.n, rows, dt).run(stream));
+        // multi-prompt: a frame's text rows end at K + its own prompt's length
+        RET_IF(self_attention(qkv, L.qkv.n, ctx, Dp, F, S, m->heads, hd, D, scale, dt, stream, mp ? mp->self_len : nullptr));
+        RET_IF(Gemm(ctx, Dp, L.attn_out, t32, Dp, rows, dt).out_f32().res(h32, Dp, 1).run(stream));
+        RET_IF(Ln(t32, Dp, 1, L.attn_ln_g, L.attn_ln_b, m->eps, rows, D, dt).y16(h16, Dp).y32(h32, Dp).run(stream));
         {
         TdcProfTagGuard tag_x(L.has_cross ? TDC_PROF_TAG_XATTN_BLOCK : -1);
         if (L.has_cross && fused) {
@@ -307,8 +254,7 @@ extern "C" int tdc_qformer_fwd(const tdc_qformer_model* m, const void* enc, int 
             x.dim = D; x.heads = m->heads; x.scale = scale; x.dtype = dt;
             RET_IF(tdc_qformer_xattn(&x, stream));
         } else if (L.has_cross) {
-            RET_IF(gemm_full(h16, Dp, L.cross_q, cq, Dp, F * K, dt, TDC_ACT_NONE, 0, nullptr, 0, 0, qmap, ident, ident,
-                             stream));
+            RET_IF(Gemm(h16, Dp, L.cross_q, cq, Dp, F * K, dt).a_map(qmap).run(stream));
             tdc_attn_desc c;
             memset(&c, 0, sizeof(c));
             const size_t koff = (size_t)L.cross_idx * 2 * D * 2;
@@ -330,33 +276,95 @@ extern "C" int tdc_qformer_fwd(const tdc_qformer_model* m, const void* enc, int 
                 q16 = true;
                 RET_IF(tdc_qformer_xattn(&x, stream));
             } else {
-                RET_IF(gemm_full(ctxq, Dp, L.cross_out, t32, Dp, F * K, dt, TDC_ACT_NONE, 1, h32, Dp, 1, ident, ident, qmap,
-                                 stream));
-                RET_IF(ln_map(t32, Dp, h16, h32, Dp, L.cross_ln_g, L.cross_ln_b, m->eps, F * K, D, dt, qmap, stream));
+                RET_IF(Gemm(ctxq, Dp, L.cross_out, t32, Dp, F * K, dt).out_f32().res(h32, Dp, 1).r_map(qmap).run(stream));
+                RET_IF(Ln(t32, Dp, 1, L.cross_ln_g, L.cross_ln_b, m->eps, F * K, D, dt).y16(h16, Dp).y32(h32, Dp).y_map(qmap).run(stream));
             }
         }
         }
-        RET_IF(gemm_full(h16, Dp, L.fq1, mq, L.fq2.k, F * K, dt, TDC_ACT_GELU_ERF, 0, nullptr, 0, 0, qmap, ident, ident,
-                         stream));
+        RET_IF(Gemm(h16, Dp, L.fq1, mq, L.fq2.k, F * K, dt).act(TDC_ACT_GELU_ERF).a_map(qmap).run(stream));
         if (q16)
-            RET_IF(gemm_full(mq, L.fq2.k, L.fq2, t32, Dp, F * K, dt, TDC_ACT_NONE, 0, h16, Dp, 0, ident, ident, qmap, stream));
+            RET_IF(Gemm(mq, L.fq2.k, L.fq2, t32, Dp, F * K, dt).res(h16, Dp, 0).r_map(qmap).run(stream));
         else
-            RET_IF(gemm_full(mq, L.fq2.k, L.fq2, t32, Dp, F * K, dt, TDC_ACT_NONE, 1, h32, Dp, 1, ident, ident, qmap,
-                             stream));
+            RET_IF(Gemm(mq, L.fq2.k, L.fq2, t32, Dp, F * K, dt).out_f32().res(h32, Dp, 1).r_map(qmap).run(stream));
         if (Lt > 0) {
-            RET_IF(gemm_full(h16, Dp, L.ft1, mt, L.ft2.k, F * Lt, dt, TDC_ACT_GELU_ERF, 0, nullptr, 0, 0, tmap, ident,
-                             ident, stream));
-            RET_IF(gemm_full(mt, L.ft2.k, L.ft2, t32b, Dp, F * Lt, dt, TDC_ACT_NONE, 1, h32, Dp, 1, ident, ident, tmap,
-                             stream));
+            RET_IF(Gemm(h16, Dp, L.ft1, mt, L.ft2.k, F * Lt, dt).act(TDC_ACT_GELU_ERF).a_map(tmap).run(stream));
+            RET_IF(Gemm(mt, L.ft2.k, L.ft2, t32b, Dp, F * Lt, dt).out_f32().res(h32, Dp, 1).r_map(tmap).run(stream));
         }
-        RET_IF(ln_map(t32, Dp, h16, h32, Dp, L.fq_ln_g, L.fq_ln_b, m->eps, F * K, D, dt, qmap, stream, q16 ? 0 : 1));
+        RET_IF(Ln(t32, Dp, q16 ? 0 : 1, L.fq_ln_g, L.fq_ln_b, m->eps, F * K, D, dt).y16(h16, Dp).y32(h32, Dp).y_map(qmap).run(stream));
         if (Lt > 0)
-            RET_IF(ln_map(t32b, Dp, h16, h32, Dp, L.ft_ln_g, L.ft_ln_b, m->eps, F * Lt, D, dt, tmap, stream));
+            RET_IF(Ln(t32b, Dp, 1, L.ft_ln_g, L.ft_ln_b, m->eps, F * Lt, D, dt).y16(h16, Dp).y32(h32, Dp).y_map(tmap).run(stream));
     }
-    RET_IF(gemm_full(h16, Dp, m->vision_proj, out, ldo, F * K, dt, TDC_ACT_NONE, 0, nullptr, 0, 0, qmap, ident, ident,
-                     stream));
+    RET_IF(Gemm(h16, Dp, m->vision_proj, out, ldo, F * K, dt).a_map(qmap).run(stream));
     return tdc_l2_normalize(out, ldo, F * K, m->H, dt, stream);
 }
+
+// ---- ViT tower (a2-a4) ---------------------------------------------------------------------------------------------------
+namespace {
+// The residual stream x [rows, Dp] of a tower (the x32 region of the workspace): fp32 rows, or 16-bit rows of type `rt`
+// (tdc_vit_model.res_dtype_p1) under GEMM operands of type `dt`.  Its operations are the ones VideoEncoder._tower_batch
+// (pipeline.py) names - ln, update, the patch embedding, the final LayerNorm + resample - and everything in which the two streams
+// differ is said here, once.
+struct ResStream {
+    void* x; bool f32; int rt;
+    int rows, D, Dp, dt; float eps;      // shared by every launch: `rows` rows of D real columns (stride Dp), operands of type dt
+    void* h16;                           // 16-bit operand rows: a LayerNorm's output (e4m3 bytes for ln8), the fp32 stream's row copy
+    float* part;                         // the fold's per-slot (mean, M2) partials
+    void* st;
+
+    // a GEMM that writes rows of the stream: fp32 C, or 16-bit C of the stream's own type under operands of type dt
+    Gemm into(const void* a, int lda, const tdc_lin& lin, int M) const {
+        Gemm g(a, lda, lin, x, Dp, M, dt);
+        if (f32) g.out_f32(); else g.c16(rt);
+        return g;
+    }
+    // LayerNorm of the stream -> 16-bit operand rows in h16 (a 16-bit stream says its own type: it may differ from dt)
+    int ln(const float* g, const float* b) const {
+        Ln l(x, Dp, f32, g, b, eps, rows, D, dt);
+        if (!f32) l.x_type(rt);
+        return l.y16(h16, Dp).run(st);
+    }
+    // ... -> e4m3 rows in h16 (row stride ldy8 bytes) + per-row scales in `stats`, for an fp8-operand GEMM of weight scale `wscale`.
+    // tdc_ln_desc.x_dtype_p1 excludes the e4m3 output; this form writes no 16-bit value, so `dtype` itself names the type of a
+    // 16-bit stream's rows
+    int ln8(const float* g, const float* b, int ldy8, float* stats, float wscale) const {
+        return Ln(x, Dp, f32, g, b, eps, rows, D, f32 ? dt : rt).y8(h16, ldy8, stats, wscale).run(st);
+    }
+    // x <- x + a lin^T + b in place: the fp32 stream is read-modify-written (8 B per element), the 16-bit one rounds
+    // acc + bias + float(x) once.  emit (LayerNorm fold): the epilogue also leaves the per-slot partials of the updated rows and - fp32
+    // stream only - their 16-bit copy in h16 for the folded consumers; over a 16-bit stream those read the stream itself (fold_src)
+    int update(const void* a, int lda, const tdc_lin& lin, bool emit = false) const {
+        Gemm g = into(a, lda, lin, rows);
+        g.res(x, Dp, f32);
+        if (emit) g.emit(f32 ? h16 : nullptr, f32 ? Dp : 0, part);
+        return g.run(st);
+    }
+    // ... on e4m3 operands a8 / lin.w with the dequantisation scales in `stats`.  tdc_gemm_desc.c16_dtype_p1 excludes fp8 operands;
+    // with in_fp8 `dtype` types C / res only, so it names the type of a 16-bit stream
+    int update8(const void* a8, int lda, const tdc_lin& lin, const float* stats, const float* zeros) const {
+        Gemm g(a8, lda, lin, x, Dp, rows, f32 ? dt : rt);
+        if (f32) g.out_f32();
+        return g.res(x, Dp, f32).in_fp8().fold(stats, zeros).run(st);
+    }
+    // A operand of the folded consumers (qkv of the layers with qkv_c1, every fc1): the RAW rows - the fp32 stream's 16-bit copy, the
+    // 16-bit stream itself (of the operands' type then, whole 64-column slots)
+    const void* fold_src() const { return f32 ? h16 : x; }
+    // patch embedding: GEMM over the im2col rows, position rows added in the epilogue, output rows skip the cls slot; then the cls row
+    int embed(const tdc_vit_model* m, const void* patches, int B, int P, int S) const {
+        const tdc_rowmap cmap = {P, S, m->has_cls, 1}, rmap = {P, 0, m->has_cls, 1};
+        RET_IF(into(patches, m->patch_lin.k, m->patch_lin, B * P).res(m->pos, m->ldpos, 1).c_map(cmap).r_map(rmap).run(st));
+        if (!m->has_cls) return 0;
+        return f32 ? tdc_set_rows((float*)x, Dp, B, S, 0, m->cls_row, st) : tdc_set_rows16(x, Dp, B, S, 0, m->cls_row, rt, st);
+    }
+    // optional final LayerNorm, then the bilinear resample of the g x g token grid (cls dropped) into `out`
+    int finish(const tdc_vit_model* m, int B, int g, void* out, int ldo, int out_grid, const int* idx0, const int* idx1,
+               const float* frac, int out_dt) const {
+        if (!m->lnf_g)
+            return tdc_resample_tokens(x, f32, Dp, m->has_cls, g, out, ldo, out_grid, idx0, idx1, frac, B, D, f32 ? dt : rt, out_dt, st);
+        RET_IF(ln(m->lnf_g, m->lnf_b));
+        return tdc_resample_tokens(h16, 0, Dp, m->has_cls, g, out, ldo, out_grid, idx0, idx1, frac, B, D, dt, out_dt, st);
+    }
+};
+}  // namespace
 
 extern "C" size_t tdc_vit_workspace_bytes(const tdc_vit_model* m, int B, int H, int W) {
     if (!m || B <= 0 || !m->layers_host) return 0;
@@ -372,237 +380,85 @@ extern "C" int tdc_vit_fwd(const tdc_vit_model* m, const void* px, int px_f32, i
     char* ws = (char*)workspace;
     const int g = H / m->patch, P = g * g, S = P + m->has_cls, rows = B * S;
     const int D = m->dim, Dp = pad64i(D), dt = m->dtype;
+    const int out_dt = m->out_dtype_p1 ? m->out_dtype_p1 - 1 : dt;
     void* patches = ws + w.patches;
-    float* x32 = (float*)(ws + w.x32);
     void* h16 = ws + w.h16;
     char* qkv = ws + w.qkv;
     void* attn = ws + w.attn;
     void* mlp = ws + w.mlp;
-    const tdc_rowmap ident = {0, 0, 0, 0};
-    // patch embedding: im2col + GEMM, position rows added in the epilogue, output rows skip the cls slot
-    RET_IF(tdc_im2col(px, px_f32, patches, m->patch_lin.k, B, H, W, m->patch, dt, stream));
-    if (!m->res_dtype_p1) {
-        tdc_rowmap cmap = {P, S, m->has_cls, 1}, rmap = {P, 0, m->has_cls, 1};
-        RET_IF(gemm(patches, m->patch_lin.k, m->patch_lin, x32, Dp, B * P, dt, TDC_ACT_NONE, 1, m->pos, m->ldpos, 1,
-                    cmap, rmap, stream));
-        if (m->has_cls) RET_IF(tdc_set_rows(x32, Dp, B, S, 0, m->cls_row, stream));
-    }
-    // attention output pad columns must be zero (K padding of the out-projection)
-    if (Dp != D) {
-        // one-time clear through the LayerNorm kernel is not possible; the pad columns of `attn` are zeroed by writing
-        // the whole buffer once with a gather-free memset on the stream
-        hipError_t e = hipMemsetAsync(attn, 0, (size_t)rows * Dp * 2, (hipStream_t)stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    const float scale = (float)(1.0 / sqrt((double)m->head_dim));  // float(head_dim ** -0.5), correctly rounded (1.0f / sqrtf is 1 ulp off at 72)
-    const int out_dt = m->out_dtype_p1 ? m->out_dtype_p1 - 1 : dt;
-    if (m->res_dtype_p1) {
-        // 16-bit residual stream (tdc_vit_model.res_dtype_p1): x lives in the x32 region as rows of type `rt`; the out-projection
-        // and fc2 GEMMs read-modify-write it in 16 bits (one rounding of acc + bias + float(x)), the LayerNorms read 16-bit rows
-        const int rt = m->res_dtype_p1 - 1;
-        if ((rt != TDC_F16 && rt != TDC_BF16) || (out_dt != TDC_F16 && out_dt != TDC_BF16)) return TDC_E_BADARG;
-        if (m->fp8 && (m->fused || D % 128 != 0)) return TDC_E_BADARG;
-        // fused over the 16-bit stream: the folded consumers (qkv of layers >= 1, every fc1) read the stream ITSELF as their A
-        // operand - operands of the stream's type, whole 64-column slots - and the out-projection / fc2 epilogues emit only the
-        // per-slot (mean, M2) partials: no LayerNorm kernel and no 16-bit row copy inside the layer loop
-        const bool fused16 = m->fused != 0;
-        if (fused16 && (rt != dt || D % 64 != 0)) return TDC_E_BADARG;
-        void* x16 = x32;
-        float* part16 = (float*)(ws + w.part);
-        float* stats16 = (float*)(ws + w.stats);
-        auto gemm_c16 = [&](const void* A, int lda, const tdc_lin& L, int M, const void* res, int ldres, int res_f32,
-                            tdc_rowmap cmap, tdc_rowmap rmap, float* part = nullptr) {
-            tdc_gemm_desc d;
-            memset(&d, 0, sizeof(d));
-            d.A = A; d.lda = lda; d.W = L.w; d.ldw = L.k; d.C = x16; d.ldc = Dp; d.bias = L.b; d.res = res; d.ldres = ldres;
-            d.M = M; d.N = L.n; d.K = L.k; d.dtype = dt; d.res_f32 = res_f32; d.c_map = cmap; d.r_map = rmap;
-            d.c16_dtype_p1 = rt + 1;
-            d.ln_part = part;
-            return tdc_gemm(&d, stream);
-        };
-        auto ln16 = [&](const float* g, const float* b) {
-            tdc_ln_desc d;
-            memset(&d, 0, sizeof(d));
-            d.x = x16; d.ldx = Dp; d.x_f32 = 0; d.x_dtype_p1 = rt + 1; d.y16 = h16; d.ldy16 = Dp; d.gamma = g; d.beta = b;
-            d.eps = m->eps; d.rows = rows; d.cols = D; d.dtype = dt;
-            return tdc_layernorm(&d, stream);
-        };
-        {
-            tdc_rowmap cmap = {P, S, m->has_cls, 1}, rmap = {P, 0, m->has_cls, 1};
-            RET_IF(gemm_c16(patches, m->patch_lin.k, m->patch_lin, B * P, m->pos, m->ldpos, 1, cmap, rmap));
-        }
-        if (m->has_cls) RET_IF(tdc_set_rows16(x16, Dp, B, S, 0, m->cls_row, rt, stream));
-        for (int l = 0; l < m->n_layers; ++l) {
-            const tdc_vit_layer& L = m->layers_host[l];
-            if (m->fp8) {
-                // e4m3 operands over the 16-bit stream (BASELINE config 5 at the final code): the LayerNorm kernel reads the 16-bit
-                // rows and writes e4m3 rows + scales; out-projection / fc2 read-modify-write the stream in 16 bits - on 16-bit
-                // operands (level 1) or on e4m3 operands with the scales in the fold operands (levels 2, 3)
-                auto ln8 = [&](const float* g_, const float* b_, int ldy8, float wscale) {
-                    tdc_ln_desc d;
-                    memset(&d, 0, sizeof(d));
-                    d.x = x16; d.ldx = Dp; d.x_f32 = 0; d.dtype = rt; d.gamma = g_; d.beta = b_; d.eps = m->eps;
-                    d.rows = rows; d.cols = D; d.y8 = h16; d.ldy8 = ldy8; d.y8_stats = stats16; d.y8_wscale = wscale;
-                    return tdc_layernorm(&d, stream);
-                };
-                RET_IF(ln8(L.ln1_g, L.ln1_b, L.qkv.k, L.qkv_wscale));
-                RET_IF(gemm_fp8(h16, L.qkv.k, L.qkv, qkv, L.qkv.n, rows, dt, TDC_ACT_NONE, stats16, L.zeros, stream));
-                tdc_attn_desc a;
-                memset(&a, 0, sizeof(a));
-                const long long bs = (long long)S * L.qkv.n;
-                a.q = qkv; a.k = qkv + (size_t)D * 2; a.v = qkv + (size_t)2 * D * 2; a.o = attn;
-                a.q_bs = a.k_bs = a.v_bs = bs; a.o_bs = (long long)S * Dp;
-                a.q_rs = a.k_rs = a.v_rs = L.qkv.n; a.o_rs = Dp;
-                a.batch = B; a.heads = m->heads; a.head_dim = m->head_dim; a.sq = S; a.sk = S; a.scale = scale; a.dtype = dt;
-                RET_IF(tdc_attention(&a, stream));
-                if (m->fp8 >= 2) {
-                    RET_IF(tdc_quantize_rows_fp8(attn, Dp, rows, Dp, dt, h16, L.out.k, stats16, L.out_wscale, stream));
-                    RET_IF(gemm_fp8_rmw16(h16, L.out.k, L.out, x16, Dp, rows, rt, stats16, L.zeros, stream));
-                } else {
-                    RET_IF(gemm_c16(attn, Dp, L.out, rows, x16, Dp, 0, ident, ident));
-                }
-                RET_IF(ln8(L.ln2_g, L.ln2_b, L.fc1.k, L.fc1_wscale));
-                const int mlp_ld8 = vit_mlp_ld(m);
-                const int mlp_n = m->act == TDC_ACT_SWIGLU ? L.fc1.n / 2 : L.fc1.n;
-                if (m->fp8 >= 3) {
-                    float* stats2 = stats16 + al256((size_t)rows * 8) / 4;
-                    if (mlp_n != L.fc2.k) return TDC_E_BADARG;
-                    RET_IF(gemm_fp8_out8(h16, L.fc1.k, L.fc1, qkv, L.fc2.k, rows, dt, m->act, stats16, L.zeros, stats2, L.fc1_w2max,
-                                         L.fc1_bmax, L.fc2_wscale, stream));
-                    RET_IF(gemm_fp8_rmw16(qkv, L.fc2.k, L.fc2, x16, Dp, rows, rt, stats2, L.zeros, stream));
-                } else {
-                    RET_IF(gemm_fp8(h16, L.fc1.k, L.fc1, mlp, mlp_ld8, rows, dt, m->act, stats16, L.zeros, stream));
-                    if (m->fp8 == 2) {
-                        RET_IF(tdc_quantize_rows_fp8(mlp, mlp_ld8, rows, mlp_n, dt, qkv, L.fc2.k, stats16, L.fc2_wscale, stream));
-                        RET_IF(gemm_fp8_rmw16(qkv, L.fc2.k, L.fc2, x16, Dp, rows, rt, stats16, L.zeros, stream));
-                    } else {
-                        RET_IF(gemm_c16(mlp, L.fc2.k, L.fc2, rows, x16, Dp, 0, ident, ident));
-                    }
-                }
-                continue;
-            }
-            if (fused16 && L.qkv_c1) {
-                RET_IF(gemm_ln(x16, Dp, L.qkv, qkv, L.qkv.n, rows, dt, TDC_ACT_NONE, 0, nullptr, 0, nullptr, 0, nullptr, stats16,
-                               L.qkv_c1, stream));
-            } else {
-                RET_IF(ln16(L.ln1_g, L.ln1_b));
-                RET_IF(gemm(h16, Dp, L.qkv, qkv, L.qkv.n, rows, dt, TDC_ACT_NONE, 0, nullptr, 0, 0, ident, ident, stream));
-            }
-            tdc_attn_desc a;
-            memset(&a, 0, sizeof(a));
-            const long long bs = (long long)S * L.qkv.n;
-            a.q = qkv; a.k = qkv + (size_t)D * 2; a.v = qkv + (size_t)2 * D * 2; a.o = attn;
-            a.q_bs = a.k_bs = a.v_bs = bs; a.o_bs = (long long)S * Dp;
-            a.q_rs = a.k_rs = a.v_rs = L.qkv.n; a.o_rs = Dp;
-            a.batch = B; a.heads = m->heads; a.head_dim = m->head_dim; a.sq = S; a.sk = S; a.scale = scale; a.dtype = dt;
-            RET_IF(tdc_attention(&a, stream));
-            if (fused16) {
-                RET_IF(gemm_c16(attn, Dp, L.out, rows, x16, Dp, 0, ident, ident, part16));
-                RET_IF(tdc_ln_finalize(part16, D / 64, rows, m->eps, stats16, stream));
-                RET_IF(gemm_ln(x16, Dp, L.fc1, mlp, L.fc2.k, rows, dt, m->act, 0, nullptr, 0, nullptr, 0, nullptr, stats16,
-                               L.fc1_c1, stream));
-                if (l + 1 < m->n_layers) {
-                    RET_IF(gemm_c16(mlp, L.fc2.k, L.fc2, rows, x16, Dp, 0, ident, ident, part16));
-                    RET_IF(tdc_ln_finalize(part16, D / 64, rows, m->eps, stats16, stream));
-                } else {
-                    RET_IF(gemm_c16(mlp, L.fc2.k, L.fc2, rows, x16, Dp, 0, ident, ident));
-                }
-                continue;
-            }
-            RET_IF(gemm_c16(attn, Dp, L.out, rows, x16, Dp, 0, ident, ident));
-            RET_IF(ln16(L.ln2_g, L.ln2_b));
-            RET_IF(gemm(h16, Dp, L.fc1, mlp, L.fc2.k, rows, dt, m->act, 0, nullptr, 0, 0, ident, ident, stream));
-            RET_IF(gemm_c16(mlp, L.fc2.k, L.fc2, rows, x16, Dp, 0, ident, ident));
-        }
-        const void* src16 = x16;
-        int src_dt = rt;
-        if (m->lnf_g) {
-            RET_IF(ln16(m->lnf_g, m->lnf_b));
-            src16 = h16;
-            src_dt = dt;
-        }
-        return tdc_resample_tokens(src16, 0, Dp, m->has_cls, g, out, ldo, out_grid, idx0, idx1, frac, B, D, src_dt, out_dt, stream);
-    }
-    // fused: the block's LayerNorms are folded into the GEMMs around them (tdc_gemm_desc: x16 / ln_part / ln_stats / ln_c1);
-    // h16 then holds the 16-bit copy of the residual stream instead of the LayerNorm output
+    float* stats = (float*)(ws + w.stats);                      // (mean, rstd) of the fold / the e4m3 rows' scales
+    float* stats2 = stats + al256((size_t)rows * 8) / 4;        // fp8 level 3: fc1's out_stats
+    const ResStream x = {ws + w.x32, !m->res_dtype_p1, m->res_dtype_p1 - 1, rows, D, Dp, dt, m->eps, h16, (float*)(ws + w.part), stream};
+    // fused: the block's LayerNorms are folded into the GEMMs around them (tdc_gemm_desc: x16 / ln_part / ln_stats / ln_c1): no
+    // LayerNorm kernel behind layer 0's first.  fp8: the LayerNorms emit e4m3 rows + scales, qkv / fc1 (level 2: out / fc2 too) run on them
     const bool fused = m->fused != 0;
-    if ((fused && (D % 64 != 0)) || (m->fp8 && (fused || D % 128 != 0))) return TDC_E_BADARG;
-    float* part = (float*)(ws + w.part);
-    float* stats = (float*)(ws + w.stats);
+    const int fp8 = m->fp8;
+    // every refusal comes before the first launch
+    if (!x.f32 && x.rt != TDC_F16 && x.rt != TDC_BF16) return TDC_E_BADARG;
+    if (out_dt != TDC_F16 && out_dt != TDC_BF16) return TDC_E_BADARG;
+    if (fp8 && (fused || D % 128 != 0)) return TDC_E_BADARG;
+    if (fused && (D % 64 != 0 || (!x.f32 && x.rt != dt))) return TDC_E_BADARG;     // see ResStream::fold_src
+    RET_IF(tdc_im2col(px, px_f32, patches, m->patch_lin.k, B, H, W, m->patch, dt, stream));
+    // the attention writes the real columns only: its output's pad columns (K padding of the out-projection) are cleared once.  The
+    // clear and the patch embedding touch different buffers; each stream keeps the order it has always enqueued them in
+    const auto clear_attn_pad = [&]() { return Dp != D ? (int)hipMemsetAsync(attn, 0, (size_t)rows * Dp * 2, (hipStream_t)stream) : 0; };
+    if (!x.f32) RET_IF(clear_attn_pad());
+    RET_IF(x.embed(m, patches, B, P, S));
+    if (x.f32) RET_IF(clear_attn_pad());
+    const float scale = (float)(1.0 / sqrt((double)m->head_dim));  // float(head_dim ** -0.5), correctly rounded (1.0f / sqrtf is 1 ulp off at 72)
     const int slots = D / 64;
-    const int mlp_ld = vit_mlp_ld(m);            // row stride of the MLP hidden buffer (16-bit values)
+    // the loop body reads side by side with VideoEncoder._tower_batch (pipeline.py)
     for (int l = 0; l < m->n_layers; ++l) {
         const tdc_vit_layer& L = m->layers_host[l];
-        if (m->fp8) {
-            RET_IF(layernorm_fp8(x32, Dp, h16, L.qkv.k, stats, L.qkv_wscale, L.ln1_g, L.ln1_b, m->eps, rows, D, dt, stream));
-            RET_IF(gemm_fp8(h16, L.qkv.k, L.qkv, qkv, L.qkv.n, rows, dt, TDC_ACT_NONE, stats, L.zeros, stream));
-        } else if (!fused || !L.qkv_c1) {
-            RET_IF(layernorm(x32, Dp, h16, Dp, L.ln1_g, L.ln1_b, m->eps, rows, D, dt, stream));
-            RET_IF(gemm(h16, Dp, L.qkv, qkv, L.qkv.n, rows, dt, TDC_ACT_NONE, 0, nullptr, 0, 0, ident, ident, stream));
+        if (fp8) {
+            RET_IF(x.ln8(L.ln1_g, L.ln1_b, L.qkv.k, stats, L.qkv_wscale));
+            RET_IF(Gemm(h16, L.qkv.k, L.qkv, qkv, L.qkv.n, rows, dt).in_fp8().fold(stats, L.zeros).run(stream));
+        } else if (!fused || !L.qkv_c1) {       // layer 0 of a fused tower: its input comes from the patch embedding, no statistics yet
+            RET_IF(x.ln(L.ln1_g, L.ln1_b));
+            RET_IF(Gemm(h16, Dp, L.qkv, qkv, L.qkv.n, rows, dt).run(stream));
         } else {
-            RET_IF(gemm_ln(h16, Dp, L.qkv, qkv, L.qkv.n, rows, dt, TDC_ACT_NONE, 0, nullptr, 0, nullptr, 0, nullptr, stats,
-                           L.qkv_c1, stream));
+            RET_IF(Gemm(x.fold_src(), Dp, L.qkv, qkv, L.qkv.n, rows, dt).fold(stats, L.qkv_c1).run(stream));
         }
-        tdc_attn_desc a;
-        memset(&a, 0, sizeof(a));
-        const long long bs = (long long)S * L.qkv.n;
-        a.q = qkv; a.k = qkv + (size_t)D * 2; a.v = qkv + (size_t)2 * D * 2; a.o = attn;
-        a.q_bs = a.k_bs = a.v_bs = bs; a.o_bs = (long long)S * Dp;
-        a.q_rs = a.k_rs = a.v_rs = L.qkv.n; a.o_rs = Dp;
-        a.batch = B; a.heads = m->heads; a.head_dim = m->head_dim; a.sq = S; a.sk = S; a.scale = scale; a.dtype = dt;
-        RET_IF(tdc_attention(&a, stream));
+        RET_IF(self_attention(qkv, L.qkv.n, attn, Dp, B, S, m->heads, m->head_dim, D, scale, dt, stream));
+        if (fp8 >= 2) {     // attention output -> e4m3 rows (in h16: the LayerNorm rows are consumed) -> out-projection on fp8
+            RET_IF(tdc_quantize_rows_fp8(attn, Dp, rows, Dp, dt, h16, L.out.k, stats, L.out_wscale, stream));
+            RET_IF(x.update8(h16, L.out.k, L.out, stats, L.zeros));
+        } else {
+            RET_IF(x.update(attn, Dp, L.out, fused));
+        }
+        // fc1's output: the fp8 forms write it at the row stride the workspace was laid out with (fc1's width when that exceeds
+        // fc2.k), the others - and every 16-bit-operand fc2, level 1's included - at fc2.k; one number for every real model
+        const int mlp_ld = fp8 ? vit_mlp_ld(m) : L.fc2.k;
+        const int mlp_n = m->act == TDC_ACT_SWIGLU ? L.fc1.n / 2 : L.fc1.n;     // columns fc1 writes (pad columns: 0)
         if (fused) {
-            RET_IF(gemm_ln(attn, Dp, L.out, x32, Dp, rows, dt, TDC_ACT_NONE, 1, x32, Dp, h16, Dp, part, nullptr, nullptr,
-                           stream));
-            RET_IF(tdc_ln_finalize(part, slots, rows, m->eps, stats, stream));
-            RET_IF(gemm_ln(h16, Dp, L.fc1, mlp, L.fc2.k, rows, dt, m->act, 0, nullptr, 0, nullptr, 0, nullptr, stats,
-                           L.fc1_c1, stream));
-            if (l + 1 < m->n_layers) {
-                RET_IF(gemm_ln(mlp, L.fc2.k, L.fc2, x32, Dp, rows, dt, TDC_ACT_NONE, 1, x32, Dp, h16, Dp, part, nullptr,
-                               nullptr, stream));
-                RET_IF(tdc_ln_finalize(part, slots, rows, m->eps, stats, stream));
-            } else {
-                RET_IF(gemm(mlp, L.fc2.k, L.fc2, x32, Dp, rows, dt, TDC_ACT_NONE, 1, x32, Dp, 1, ident, ident, stream));
-            }
-        } else if (m->fp8) {
-            if (m->fp8 >= 2) {   // attention output -> e4m3 rows (in h16: the LayerNorm rows are consumed) -> out-proj on fp8
-                RET_IF(tdc_quantize_rows_fp8(attn, Dp, rows, Dp, dt, h16, L.out.k, stats, L.out_wscale, stream));
-                RET_IF(gemm_fp8_rmw(h16, L.out.k, L.out, x32, Dp, rows, dt, stats, L.zeros, stream));
-            } else {
-                RET_IF(gemm(attn, Dp, L.out, x32, Dp, rows, dt, TDC_ACT_NONE, 1, x32, Dp, 1, ident, ident, stream));
-            }
-            RET_IF(layernorm_fp8(x32, Dp, h16, L.fc1.k, stats, L.fc1_wscale, L.ln2_g, L.ln2_b, m->eps, rows, D, dt, stream));
-            const int mlp_n = m->act == TDC_ACT_SWIGLU ? L.fc1.n / 2 : L.fc1.n;   // columns fc1 writes (pad columns: 0)
-            if (m->fp8 >= 3) {   // fc1 writes the e4m3 MLP hidden + its row scales itself (qkv buffer, second stats array)
-                float* stats2 = stats + al256((size_t)rows * 8) / 4;
+            RET_IF(tdc_ln_finalize(x.part, slots, rows, m->eps, stats, stream));
+            RET_IF(Gemm(x.fold_src(), Dp, L.fc1, mlp, mlp_ld, rows, dt).act(m->act).fold(stats, L.fc1_c1).run(stream));
+        } else if (fp8) {
+            RET_IF(x.ln8(L.ln2_g, L.ln2_b, L.fc1.k, stats, L.fc1_wscale));
+            if (fp8 >= 3) {     // fc1 writes the e4m3 MLP hidden + its row scales itself (qkv buffer, second stats array)
                 if (mlp_n != L.fc2.k) return TDC_E_BADARG;
-                RET_IF(gemm_fp8_out8(h16, L.fc1.k, L.fc1, qkv, L.fc2.k, rows, dt, m->act, stats, L.zeros, stats2, L.fc1_w2max,
-                                     L.fc1_bmax, L.fc2_wscale, stream));
-                RET_IF(gemm_fp8_rmw(qkv, L.fc2.k, L.fc2, x32, Dp, rows, dt, stats2, L.zeros, stream));
+                RET_IF(Gemm(h16, L.fc1.k, L.fc1, qkv, L.fc2.k, rows, dt).act(m->act).in_fp8().fold(stats, L.zeros)
+                           .out_fp8(stats2, L.fc1_w2max, L.fc1_bmax, L.fc2_wscale).run(stream));
             } else {
-                RET_IF(gemm_fp8(h16, L.fc1.k, L.fc1, mlp, mlp_ld, rows, dt, m->act, stats, L.zeros, stream));
-                if (m->fp8 == 2) {   // MLP hidden -> e4m3 rows (in the qkv buffer, free after the attention) -> fc2 on fp8
-                    RET_IF(tdc_quantize_rows_fp8(mlp, mlp_ld, rows, mlp_n, dt, qkv, L.fc2.k, stats, L.fc2_wscale, stream));
-                    RET_IF(gemm_fp8_rmw(qkv, L.fc2.k, L.fc2, x32, Dp, rows, dt, stats, L.zeros, stream));
-                } else {
-                    RET_IF(gemm(mlp, L.fc2.k, L.fc2, x32, Dp, rows, dt, TDC_ACT_NONE, 1, x32, Dp, 1, ident, ident, stream));
-                }
+                RET_IF(Gemm(h16, L.fc1.k, L.fc1, mlp, mlp_ld, rows, dt).act(m->act).in_fp8().fold(stats, L.zeros).run(stream));
             }
         } else {
-            RET_IF(gemm(attn, Dp, L.out, x32, Dp, rows, dt, TDC_ACT_NONE, 1, x32, Dp, 1, ident, ident, stream));
-            RET_IF(layernorm(x32, Dp, h16, Dp, L.ln2_g, L.ln2_b, m->eps, rows, D, dt, stream));
-            RET_IF(gemm(h16, Dp, L.fc1, mlp, L.fc2.k, rows, dt, m->act, 0, nullptr, 0, 0, ident, ident, stream));
-            RET_IF(gemm(mlp, L.fc2.k, L.fc2, x32, Dp, rows, dt, TDC_ACT_NONE, 1, x32, Dp, 1, ident, ident, stream));
+            RET_IF(x.ln(L.ln2_g, L.ln2_b));
+            RET_IF(Gemm(h16, Dp, L.fc1, mlp, mlp_ld, rows, dt).act(m->act).run(stream));
+        }
+        if (fp8 >= 3) {
+            RET_IF(x.update8(qkv, L.fc2.k, L.fc2, stats2, L.zeros));
+        } else if (fp8 == 2) {      // MLP hidden -> e4m3 rows (in the qkv buffer, free after the attention) -> fc2 on fp8
+            RET_IF(tdc_quantize_rows_fp8(mlp, mlp_ld, rows, mlp_n, dt, qkv, L.fc2.k, stats, L.fc2_wscale, stream));
+            RET_IF(x.update8(qkv, L.fc2.k, L.fc2, stats, L.zeros));
+        } else if (fused && l + 1 < m->n_layers) {
+            RET_IF(x.update(mlp, L.fc2.k, L.fc2, true));
+            RET_IF(tdc_ln_finalize(x.part, slots, rows, m->eps, stats, stream));
+        } else {                    // the last layer's statistics would have no consumer
+            RET_IF(x.update(mlp, L.fc2.k, L.fc2));
         }
     }
-    const void* src = x32;
-    int src_f32 = 1;
-    if (m->lnf_g) {
-        RET_IF(layernorm(x32, Dp, h16, Dp, m->lnf_g, m->lnf_b, m->eps, rows, D, dt, stream));
-        src = h16;
-        src_f32 = 0;
-    }
-    return tdc_resample_tokens(src, src_f32, Dp, m->has_cls, g, out, ldo, out_grid, idx0, idx1, frac, B, D, dt, out_dt, stream);
+    return x.finish(m, B, g, out, ldo, out_grid, idx0, idx1, frac, out_dt);
 }
 
 // ---- connector (a6-a9) -------------------------------------------------------------------------------------------------
@@ -635,10 +491,6 @@ ConnWs conn_layout(const tdc_connector_model* m, int T) {
     return w;
 }
 
-int ln16(const float* x, int ldx, void* y16, int ldy, const float* g, const float* b, float eps, int rows, int cols,
-         int dtype, void* st) {
-    return layernorm(x, ldx, y16, ldy, g, b, eps, rows, cols, dtype, st);
-}
 }  // namespace
 
 extern "C" size_t tdc_connector_workspace_bytes(const tdc_connector_model* m, int T) {
@@ -655,16 +507,16 @@ extern "C" int tdc_connector_fwd(const tdc_connector_model* m, const void* sig, 
     char* ws = (char*)workspace;
     const int C = m->C, Cp = pad64i(C), dt = m->dtype, side = m->side, r = m->r;
     const int P = side * r * side * r, nq = side * side, rows = T * P, qrows = T * nq;
-    const tdc_rowmap ident = {0, 0, 0, 0};
+    const float eps = 1e-5f;
     hipStream_t st = (hipStream_t)stream;
     // a6: mm_projector_aux_i = Linear + GELU(erf), Linear, LayerNorm(1e-5); global context = mean over the tokens of aux_0
     const void* feats[2] = {sig, dino};
     const int lds[2] = {ld_s, ld_d};
     for (int i = 0; i < 2; ++i) {
         const tdc_aux_proj& a = m->aux[i];
-        RET_IF(gemm(feats[i], lds[i], a.fc1, ws + w.h, Cp, rows, dt, TDC_ACT_GELU_ERF, 0, nullptr, 0, 0, ident, ident, stream));
-        RET_IF(gemm(ws + w.h, Cp, a.fc2, ws + w.y32, Cp, rows, dt, TDC_ACT_NONE, 1, nullptr, 0, 0, ident, ident, stream));
-        RET_IF(ln16((const float*)(ws + w.y32), Cp, ws + w.aux[i], Cp, a.ln_g, a.ln_b, 1e-5f, rows, C, dt, stream));
+        RET_IF(Gemm(feats[i], lds[i], a.fc1, ws + w.h, Cp, rows, dt).act(TDC_ACT_GELU_ERF).run(stream));
+        RET_IF(Gemm(ws + w.h, Cp, a.fc2, ws + w.y32, Cp, rows, dt).out_f32().run(stream));
+        RET_IF(Ln(ws + w.y32, Cp, 1, a.ln_g, a.ln_b, eps, rows, C, dt).y16(ws + w.aux[i], Cp).run(stream));
     }
     RET_IF(tdc_token_mean(ws + w.aux[0], P, Cp, ws + w.ctx, T, dt, stream));
     // queries start as vision_query broadcast to every window of every frame (cambrian_arch.py:1018-1023)
@@ -674,24 +526,19 @@ extern "C" int tdc_connector_fwd(const tdc_connector_model* m, const void* sig, 
         const tdc_sva_layer& L = m->layers_host[l];
         char* q16 = ws + w.q16[cur];
         char* q16n = ws + w.q16[cur ^ 1];
-        RET_IF(gemm(ws + w.ctx, Cp, L.proj_context, ws + w.cproj, Cp, T, dt, TDC_ACT_NONE, 0, nullptr, 0, 0, ident, ident, stream));
-        RET_IF(gemm(ws + w.cproj, Cp, L.proj_in_c, ws + w.cin, Cp, T, dt, TDC_ACT_NONE, 1, nullptr, 0, 0, ident, ident, stream));
+        RET_IF(Gemm(ws + w.ctx, Cp, L.proj_context, ws + w.cproj, Cp, T, dt).run(stream));
+        RET_IF(Gemm(ws + w.cproj, Cp, L.proj_in_c, ws + w.cin, Cp, T, dt).out_f32().run(stream));
         {   // proj_in(cat[q, ctx]) = proj_in_q(q) + (per-frame) proj_in_c(ctx)
             const tdc_rowmap rmap = {nq, 1, 0, 0};
-            RET_IF(gemm(q16, Cp, L.proj_in_q, ws + w.qin, Cp, qrows, dt, TDC_ACT_NONE, 1, ws + w.cin, Cp, 1, ident, rmap, stream));
+            RET_IF(Gemm(q16, Cp, L.proj_in_q, ws + w.qin, Cp, qrows, dt).out_f32().res(ws + w.cin, Cp, 1).r_map(rmap).run(stream));
         }
-        for (int tw = 0; tw < 2; ++tw) {
-            tdc_ln_desc d;
-            memset(&d, 0, sizeof(d));
-            d.x = ws + w.aux[tw]; d.ldx = Cp; d.x_f32 = 0; d.y16 = ws + w.xn; d.ldy16 = Cp;
-            d.gamma = m->ones_C; d.beta = m->zeros_C; d.eps = 1e-5f;
-            d.add = L.pos[tw]; d.ldadd = L.ldpos; d.add_period = P; d.add_mode = 1;
-            d.rows = rows; d.cols = C; d.dtype = dt;
-            RET_IF(tdc_layernorm(&d, stream));
-            RET_IF(gemm(ws + w.xn, Cp, L.kv[tw], ws + w.kv[tw], L.kv[tw].n, rows, dt, TDC_ACT_NONE, 0, nullptr, 0, 0, ident, ident, stream));
+        for (int tw = 0; tw < 2; ++tw) {    // un-affine LayerNorm of the tower's tokens + window position (the affines live in kv[tw])
+            RET_IF(Ln(ws + w.aux[tw], Cp, 0, m->ones_C, m->zeros_C, eps, rows, C, dt).y16(ws + w.xn, Cp)
+                       .add(L.pos[tw], L.ldpos, P, 1).run(stream));
+            RET_IF(Gemm(ws + w.xn, Cp, L.kv[tw], ws + w.kv[tw], L.kv[tw].n, rows, dt).run(stream));
         }
-        RET_IF(ln16((const float*)(ws + w.qin), Cp, ws + w.qn, Cp, L.q_ln_g, L.q_ln_b, 1e-5f, qrows, C, dt, stream));
-        RET_IF(gemm(ws + w.qn, Cp, L.q_proj, ws + w.qs, Cp, qrows, dt, TDC_ACT_NONE, 0, nullptr, 0, 0, ident, ident, stream));
+        RET_IF(Ln(ws + w.qin, Cp, 1, L.q_ln_g, L.q_ln_b, eps, qrows, C, dt).y16(ws + w.qn, Cp).run(stream));
+        RET_IF(Gemm(ws + w.qn, Cp, L.q_proj, ws + w.qs, Cp, qrows, dt).run(stream));
         {
             tdc_sva_attn_desc a;
             memset(&a, 0, sizeof(a));
@@ -701,13 +548,13 @@ extern "C" int tdc_connector_fwd(const tdc_connector_model* m, const void* sig, 
             if (Cp != C && hipMemsetAsync(ws + w.att, 0, (size_t)qrows * Cp * 2, st) != hipSuccess) return TDC_E_BADARG;
             RET_IF(tdc_sva_attention(&a, stream));
         }
-        RET_IF(gemm(ws + w.att, Cp, L.o_proj, ws + w.q2, Cp, qrows, dt, TDC_ACT_NONE, 1, ws + w.qin, Cp, 1, ident, ident, stream));
-        RET_IF(ln16((const float*)(ws + w.q2), Cp, ws + w.qn, Cp, L.norm_g, L.norm_b, 1e-5f, qrows, C, dt, stream));
-        RET_IF(gemm(ws + w.qn, Cp, L.out1, ws + w.mh, Cp, qrows, dt, TDC_ACT_GELU_ERF, 0, nullptr, 0, 0, ident, ident, stream));
-        RET_IF(gemm(ws + w.mh, Cp, L.out2, q16n, Cp, qrows, dt, TDC_ACT_NONE, 0, q16, Cp, 0, ident, ident, stream));
+        RET_IF(Gemm(ws + w.att, Cp, L.o_proj, ws + w.q2, Cp, qrows, dt).out_f32().res(ws + w.qin, Cp, 1).run(stream));
+        RET_IF(Ln(ws + w.q2, Cp, 1, L.norm_g, L.norm_b, eps, qrows, C, dt).y16(ws + w.qn, Cp).run(stream));
+        RET_IF(Gemm(ws + w.qn, Cp, L.out1, ws + w.mh, Cp, qrows, dt).act(TDC_ACT_GELU_ERF).run(stream));
+        RET_IF(Gemm(ws + w.mh, Cp, L.out2, q16n, Cp, qrows, dt).res(q16, Cp, 0).run(stream));
         cur ^= 1;
     }
     // a9: mm_projector
-    RET_IF(gemm(ws + w.q16[cur], Cp, m->mm1, ws + w.mh, m->mm1.n, qrows, dt, TDC_ACT_GELU_ERF, 0, nullptr, 0, 0, ident, ident, stream));
-    return gemm(ws + w.mh, m->mm1.n, m->mm2, out, ldo, qrows, dt, TDC_ACT_NONE, 0, nullptr, 0, 0, ident, ident, stream);
+    RET_IF(Gemm(ws + w.q16[cur], Cp, m->mm1, ws + w.mh, m->mm1.n, qrows, dt).act(TDC_ACT_GELU_ERF).run(stream));
+    return Gemm(ws + w.mh, m->mm1.n, m->mm2, out, ldo, qrows, dt).run(stream);
 }
