@@ -9,6 +9,8 @@ The engine is pipeline.VideoEncoder on GPUs; the CPU tests plug in doubles.  The
              audio_tokens (raw-waveform audio)
   probed     mark / fetch / after (the host read beside the compute stream), two_streams / tower_stream (SigLIP on a side
              stream), emit_into, multi_prompt_ok, dev, side - absent on the doubles
+  features   towers (what features.tower_signature fingerprints); probed: tower_width(name), feature_rows(x) (the tower
+             rows' padding columns), feature_signature() (the signature, cached)
 """
 import torch
 
@@ -159,8 +161,15 @@ def encode_video_prompts_with(e, px_siglip, px_dino, image_size, prompts, audio=
     through compress_many_with.  prompts: dicts of budget_text_len, n_text_tokens, prompt_ids, optional splice.  infos: one dict
     per prompt, filled as encode_video's info= plus info["prompts"] (the selection's front facts - info["cache"] among them -
     are those of the ONE front pass the selection's prompts share)."""
+    def front(btl, finfo):
+        return video_front(e, cache, px_siglip, px_dino, image_size, btl, audio, frame_cap, None, video_index, finfo)
+    return prompts_over_fronts(e, px_siglip.shape[0], prompts, front, frame_cap, infos, max_prompts, pad_fraction)
+
+
+def prompts_over_fronts(e, T0, prompts, front, frame_cap=224, infos=None, max_prompts=8, pad_fraction=0.25):
+    """encode_video_prompts_with behind its input: the prompts of one T0-frame video grouped by their a1 selection,
+    front(budget_text_len, info) -> the front of a selection (run once per distinct selection), compress_many_with over each"""
     cfg = e.cfg
-    T0 = px_siglip.shape[0]
     sels, order = {}, []
     for p, pr in enumerate(prompts):
         key = tuple(frame_indices(cfg, T0, pr["budget_text_len"], frame_cap))                       # a1
@@ -174,7 +183,7 @@ def encode_video_prompts_with(e, px_siglip, px_dino, image_size, prompts, audio=
         members = sels[key]
         btl = prompts[members[0]]["budget_text_len"]
         finfo = {} if infos is not None else None
-        f = video_front(e, cache, px_siglip, px_dino, image_size, btl, audio, frame_cap, None, video_index, finfo)
+        f = front(btl, finfo)
         sub = [infos[p] for p in members] if infos is not None else None
         res = compress_many_with(e, f["X"], f["T"], f["N"], f["seg_idx"], [prompts[p] for p in members], f["audio"], sub,
                                  max_prompts, pad_fraction)
@@ -268,13 +277,19 @@ def join_side_tower(e, started, px_siglip):
 def select_segments_with(e, sims, refine, info=None):
     """a5 (tdc/cambrian_arch.py:832-849) on the T - 1 host similarities.  With engine.selection_eps, the pairs whose order that
     error leaves open (segment.selection_band) are re-ranked on refine(band) -> their fp16-tower similarities in band order,
-    unless the band is a plateau (segment.band_allowed).  info receives refined_pairs and refine_skipped_pairs."""
+    unless the band is a plateau (segment.band_allowed).  info receives refined_pairs and refine_skipped_pairs.  refine=None
+    (stored tower features: no pixels to re-encode): the similarities are ranked as they are and info receives
+    refine_unavailable_pairs = the size of the band that would have been refined."""
     mns = e.cfg.get("max_num_segments", 24)
     eps = getattr(e, "selection_eps", None)
     band = seg.selection_band(sims, mns, eps) if eps else []
     if band and not seg.band_allowed(band, len(sims) + 1, getattr(e, "selection_max_fraction", 0.125)):
         if info is not None:
             info["refine_skipped_pairs"] = len(band)
+        band = []
+    if band and refine is None:
+        if info is not None:
+            info["refine_unavailable_pairs"] = len(band)
         band = []
     if info is not None:
         info["refined_pairs"] = list(band)
@@ -332,6 +347,14 @@ def video_front_with(e, px_siglip, px_dino, image_size, budget_text_len, audio=N
     T = len(idx)
     sig, dino, (seg_idx,) = towers_and_selection(e, px_siglip, px_dino, [(0, T, T > cfg.get("max_num_segments", 24) + 1)],
                                                  None if info is None else [info])                  # a3-a5
+    return front_after_towers(e, sig, dino, seg_idx, T0, idx, image_size, audio, keep, video_index)
+
+
+def front_after_towers(e, sig, dino, seg_idx, T0, idx, image_size, audio=None, keep=None, video_index=None):
+    """what a front does once the tower rows of the a1-kept frames idx (of T0) and their a5 selection are known - the
+    connector (a6-a10) and the frames' audio (a20) -> the front's dict.  Shared by the pixel front (video_front_with) and the
+    front from stored features (video_front_from_features)."""
+    T = len(idx)
     sizes = [tuple(image_size)] * T
     X, final_size = e.connector(sig, dino, T, sizes, keep)                                          # a6-a10
     N = X.shape[0] // T
@@ -355,8 +378,13 @@ def encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text
     """One video: pixels -> emitted visual tokens [n, H] (VideoEncoder.encode_video documents the arguments).  cache: a
     FrameCache - the front runs through it (video_front), the result is bit for bit that of cache=None, and info["cache"]
     says what the call reused and encoded."""
-    cfg = e.cfg
     f = video_front(e, cache, px_siglip, px_dino, image_size, budget_text_len, audio, frame_cap, keep, video_index, info)
+    return encode_front(e, f, n_text_tokens, prompt_ids, keep, splice, info)
+
+
+def encode_front(e, f, n_text_tokens, prompt_ids, keep=None, splice=None, info=None):
+    """one prompt over the front f (video_front / video_front_from_features): a11-a19 (+a21) -> emitted visual tokens [n, H]"""
+    cfg = e.cfg
     X, T, N, seg_idx, idx, final_size = f["X"], f["T"], f["N"], f["seg_idx"], f["idx"], f["final_size"]
     max_visual_len = visual_budget(cfg, n_text_tokens)
     pid = text_prompt(cfg, prompt_ids)
@@ -589,3 +617,113 @@ def encode_video_cached(e, cache, px_siglip, px_dino, image_size, budget_text_le
     """encode_video_with(..., cache=cache): one video through a FrameCache (cache.py), bit for bit the uncached result"""
     return encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio, frame_cap,
                              None, splice, video_index, info, cache)
+
+
+# ---- encode from stored tower features (features.FeatureSet; DESIGN.md section 13) ------------------------------------------
+def stored_rows(e, name, rows, T0):
+    """tower rows [T0 * P, >= D] as FeatureSet stores them: [T0, P, D], the padding columns dropped (D: engine.tower_width)"""
+    D = e.tower_width(name) if hasattr(e, "tower_width") else rows.shape[1]
+    return rows[:, :D].reshape(T0, rows.shape[0] // T0, D)
+
+
+def export_features_with(e, px_siglip, px_dino, image_size):
+    """a3 / a4 of EVERY input frame (no a1: it reads the prompt length and the cap) -> features.FeatureSet.  The towers run as
+    in towers_and_selection: SigLIP on the side stream under `two_streams`, after the DINOv2 tower otherwise."""
+    from .features import FeatureSet, tower_signature
+    T0 = px_siglip.shape[0]
+    if px_dino.shape[0] != T0 or T0 < 1:
+        raise ValueError("export_features: %d SigLIP and %d DINOv2 frames" % (T0, px_dino.shape[0]))
+    side_sig = start_side_tower(e, px_siglip)
+    dino = e.tower("dino", px_dino)                                                                 # a4
+    sig = join_side_tower(e, side_sig, px_siglip)                                                   # a3
+    return FeatureSet(stored_rows(e, "siglip", sig, T0), stored_rows(e, "dino", dino, T0), image_size, tower_signature(e))
+
+
+def check_features(e, fs):
+    """refuse a FeatureSet whose towers are not this engine's: ValueError naming both signatures"""
+    from .features import tower_signature
+    mine = tower_signature(e)
+    if fs.signature != mine:
+        raise ValueError("the feature set was exported by towers %r, this engine's towers are %r (check_signature=False "
+                         "skips the comparison)" % (fs.signature, mine))
+
+
+def feature_rows(e, fs, idx=None):
+    """the stored rows of the frames idx (None: all) as the towers hand them on: ([T * P, width] SigLIP, DINOv2) on the
+    engine's device.  The gather is plain indexing on the device, as the pixel path's px[sel]; engine.feature_rows restores
+    the zero padding columns the towers write, so every launch behind it sees the pixel path's operands."""
+    dev = getattr(e, "dev", fs.siglip.device)
+    out = []
+    for name, x in (("siglip", fs.siglip), ("dino", fs.dino)):
+        if hasattr(e, "tower_width") and x.shape[2] != e.tower_width(name):
+            raise ValueError("%s features are %d wide, the engine's tower is %d wide" % (name, x.shape[2], e.tower_width(name)))
+        x = x.to(dev)
+        if idx is not None and len(idx) != x.shape[0]:              # every frame kept: the rows stay where they lie
+            x = x[torch.tensor(idx, device=x.device)]
+        out.append(e.feature_rows(x) if hasattr(e, "feature_rows") else x.reshape(-1, x.shape[2]))
+    return out
+
+
+def video_front_from_features(e, fs, budget_text_len, audio=None, frame_cap=224, video_index=None, info=None,
+                              check_signature=True):
+    """video_front_with from the stored tower rows of a video (features.FeatureSet) instead of its pixels: a1, the kept
+    frames' rows gathered, a5 by the pixel path's launch on the gathered DINOv2 rows, then front_after_towers -> the same dict,
+    the same bits.  The selection refinement needs pixels: under engine.selection_eps a non-empty band is ranked on the stored
+    similarities and reported as info["refine_unavailable_pairs"] (select_segments_with, refine=None)."""
+    if check_signature:
+        check_features(e, fs)
+    cfg = e.cfg
+    T0 = fs.frames
+    idx = frame_indices(cfg, T0, budget_text_len, frame_cap)                                        # a1
+    T = len(idx)
+    sig, dino = feature_rows(e, fs, idx)
+    if T > cfg.get("max_num_segments", 24) + 1:                                                     # a5
+        sims_dev = e.sims_tensor(dino, T)
+        ev = e.mark() if hasattr(e, "mark") and sims_dev.is_cuda else None
+        sims = e.fetch(sims_dev, ev) if ev is not None else sims_dev.tolist()
+        seg_idx = select_segments_with(e, sims, None, info)
+    else:
+        seg_idx = list(range(T))
+    return front_after_towers(e, sig, dino, seg_idx, T0, idx, fs.image_size, audio, None, video_index)
+
+
+def encode_features_with(e, fs, budget_text_len, n_text_tokens, prompt_ids, audio=None, frame_cap=224, splice=None,
+                         video_index=None, info=None, check_signature=True, image=False):
+    """encode_video_with from a FeatureSet: bit for bit its result for the pixels the set was exported from, whenever that
+    call refines nothing.  image=True (a one-frame set): the connector rows [:, :H] of the image, as
+    prepare_inputs_labels_for_multimodal's image branch (info receives final_size)."""
+    if image:
+        if fs.frames != 1:
+            raise ValueError("image=True takes a one-frame feature set, got %d frames" % fs.frames)
+        if check_signature:
+            check_features(e, fs)
+        sig, dino = feature_rows(e, fs)
+        X, sizes = e.connector(sig, dino, 1, [tuple(fs.image_size)])
+        if info is not None:
+            info["final_size"] = sizes
+        return X[:, :e.H]
+    f = video_front_from_features(e, fs, budget_text_len, audio, frame_cap, video_index, info, check_signature)
+    return encode_front(e, f, n_text_tokens, prompt_ids, None, splice, info)
+
+
+def encode_features_prompts_with(e, fs, prompts, audio=None, frame_cap=224, video_index=None, infos=None, max_prompts=8,
+                                 pad_fraction=0.25, check_signature=True):
+    """encode_video_prompts_with from a FeatureSet: the front from features once per distinct a1 selection, the selection's
+    prompts through compress_many_with -> one result per prompt, bit for bit encode_features_with's"""
+    if check_signature:
+        check_features(e, fs)
+
+    def front(btl, finfo):
+        return video_front_from_features(e, fs, btl, audio, frame_cap, video_index, finfo, False)
+    return prompts_over_fronts(e, fs.frames, prompts, front, frame_cap, infos, max_prompts, pad_fraction)
+
+
+def same_features_key(e, fs, budget_text_len, frame_cap, audio=None, video_index=None):
+    """`config.tdc_batch_prompts` over feature inputs: what two samples must share to be questions about the SAME stored
+    video - the content of both feature tensors (content_key), image_size, the a1 selection, and their audio as
+    same_video_key compares it"""
+    idx = frame_indices(e.cfg, fs.frames, budget_text_len, frame_cap)
+    akey = None
+    if audio is not None:
+        akey = (content_key(e, audio), tuple(sample_indicator(fs.frames, idx, video_index)))
+    return (content_key(e, fs.siglip), content_key(e, fs.dino), tuple(fs.image_size), tuple(idx), akey)

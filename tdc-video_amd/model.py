@@ -23,7 +23,8 @@ import torch.nn as nn
 
 from . import lib as L
 from . import segment as seg
-from .encode import batch_groups, encode_image_cached, frame_indices, same_video_key
+from .encode import batch_groups, encode_image_cached, frame_indices, same_features_key, same_video_key
+from .features import FeatureSet, is_feature_set
 from .pipeline import VideoEncoder
 
 IGNORE_INDEX = -100        # tdc/constants.py
@@ -372,7 +373,7 @@ class CambrianMetaModel:
         `config.tdc_frame_cap` (default 224 = the reference's "in case of OOM" constant, tdc/cambrian_arch.py:907-916,813-822):
         the cap of both frame sub-samplings; `config.tdc_shard_frames`: see prepare_inputs_labels_for_multimodal;
         `config.tdc_video_cache_bytes`: see tdc_video_cache; `config.tdc_shard_cache_bytes`: see tdc_shard_cache;
-        `config.tdc_batch_frames`: see tdc_batch_frames.
+        `config.tdc_batch_frames`: see tdc_batch_frames; `config.tdc_feature_inputs`: see tdc_feature_inputs.
         bench.py's line is reproduced by dtype=float16, tdc_tower_dtype="bfloat16", tdc_tower_res_dtype="float16",
         tdc_frame_cap=T (its `product_setting` field says so; `bench.py --via-mixin` runs exactly that)."""
         if self._tdc_encoder is None or refresh:
@@ -507,6 +508,24 @@ class CambrianMetaModel:
                     raise ValueError("config.tdc_batch_prompts and config.%s cannot be set together" % other)
         return n
 
+    def tdc_feature_inputs(self):
+        """`config.tdc_feature_inputs`: True = `images` carries stored tower features instead of pixels (features.FeatureSet,
+        VideoEncoder.export_features): images[0][i] / images[1][i] are the SigLIP / DINOv2 rows of sample i, [T, tokens,
+        hidden_size of that tower], or images[0][i] is a FeatureSet and images[1][i] None; every sample runs through
+        VideoEncoder.encode_features (images: its connector-only form).  Absent / False: pixels.  Set together with
+        `config.tdc_shard_frames`, `tdc_batch_frames`, `tdc_video_cache_bytes` or `tdc_shard_cache_bytes` it raises: those need
+        pixels, or key on them.  `config.tdc_batch_prompts` composes with it."""
+        v = getattr(self.config, "tdc_feature_inputs", None)
+        if v is None:
+            return False
+        if not isinstance(v, bool):
+            raise ValueError("config.tdc_feature_inputs must be True / False (absent = off), got %r" % (v,))
+        if v:
+            for other in ("tdc_shard_frames", "tdc_batch_frames", "tdc_video_cache_bytes", "tdc_shard_cache_bytes"):
+                if getattr(self.config, other, None):
+                    raise ValueError("config.tdc_feature_inputs and config.%s cannot be set together" % other)
+        return v
+
     def tdc_prompt_pad_fraction(self):
         """`config.tdc_prompt_pad_fraction`: the share of a prompt group's rows that may be padding (encode.prompt_groups);
         absent: 1/4."""
@@ -624,6 +643,34 @@ class CambrianMetaForCausalLM(ABC):
             seg_all.append(torch.tensor(segi))
         return torch.cat(out_f, 0), new_sizes, [torch.cat(out_0, 0), torch.cat(out_1, 0)], sel_all, seg_all
 
+    # ---- config.tdc_feature_inputs ----------------------------------------------------------------------------------
+    def _feature_sets(self, images, image_sizes, bsz):
+        """`images` under config.tdc_feature_inputs -> one features.FeatureSet per sample.  Videos: images[0] / images[1] are
+        lists, entry i the [T, tokens, width] rows of sample i (or a FeatureSet in images[0][i], images[1][i] None); single
+        images: two [bsz, tokens, width] tensors.  A width that is not the tower's raises ValueError here, before any launch."""
+        towers = self.get_model().get_vision_tower_aux_list()
+        widths = (towers[0].hidden_size, towers[-1].hidden_size)
+        out = []
+        for i in range(bsz):
+            s = images[0][i]
+            d = images[1][i] if len(images) > 1 and images[1] is not None else None
+            if is_feature_set(s):
+                if d is not None:
+                    raise ValueError("config.tdc_feature_inputs: images[0][%d] is a FeatureSet, images[1][%d] must be None" % (i, i))
+                fs = s
+            else:
+                if not (torch.is_tensor(s) and torch.is_tensor(d)):
+                    raise ValueError("config.tdc_feature_inputs: sample %d needs a FeatureSet or the two towers' feature tensors" % i)
+                if s.dim() == 2:
+                    s, d = s.unsqueeze(0), d.unsqueeze(0)
+                fs = FeatureSet(s, d, image_sizes[i])
+            for name, x, w in (("SigLIP", fs.siglip, widths[0]), ("DINOv2", fs.dino, widths[1])):
+                if x.shape[-1] != w:
+                    raise ValueError("config.tdc_feature_inputs: the %s features of sample %d are %d wide, the tower's "
+                                     "hidden_size is %d" % (name, i, x.shape[-1], w))
+            out.append(fs)
+        return out
+
     # ---- the hot path ---------------------------------------------------------------------------------------------
     def prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, attention_mask, past_key_values, labels,
                                              images, image_aux_attention_masks_list=None, image_sizes=None,
@@ -633,6 +680,9 @@ class CambrianMetaForCausalLM(ABC):
         towers = model.get_vision_tower_aux_list()
         if towers is None or images is None or input_ids.shape[1] == 1:
             return (input_ids, position_ids, attention_mask, past_key_values, None, labels, None, None, None, None)
+        feature_inputs = model.tdc_feature_inputs()  # config.tdc_feature_inputs: `images` holds stored tower features
+        if feature_inputs:
+            feature_sets = self._feature_sets(images, image_sizes, input_ids.shape[0])      # validated before any engine call
         eng = model.tdc_engine()
         vcache = model.tdc_video_cache()             # config.tdc_video_cache_bytes (validated even when no video comes)
         batch_frames = model.tdc_batch_frames()      # config.tdc_batch_frames (0: every sample on its own)
@@ -641,7 +691,7 @@ class CambrianMetaForCausalLM(ABC):
         cfgd = self._cfg()
         K = cfgd.get("context_token_num", 16)
         H = model.config.hidden_size
-        is_video = type(images[0]) is list or images[0].ndim == 5
+        is_video = isinstance(images[0], (list, tuple)) if feature_inputs else type(images[0]) is list or images[0].ndim == 5
         bsz = input_ids.shape[0]
         # every integer decision below (text lengths, <image> positions, which rows survive the mask) is taken on ONE host copy of
         # the ids / mask: a device-side torch.where(...).tolist() waits for everything queued on the stream - the previous
@@ -654,7 +704,9 @@ class CambrianMetaForCausalLM(ABC):
 
         def facts(i):
             """the host-side facts of sample i: pixels, text lengths, prompt ids, audio, a21 hand-off, frame cap"""
-            if is_video:
+            if feature_inputs:
+                vid_s, vid_d = feature_sets[i], None
+            elif is_video:
                 vid_s, vid_d = images[0][i], images[1][i]
                 if vid_s.ndim == 3:
                     vid_s, vid_d = vid_s.unsqueeze(0), vid_d.unsqueeze(0)
@@ -709,7 +761,16 @@ class CambrianMetaForCausalLM(ABC):
             i, vid_s, vid_d, n_text, prompt_ids, audio, splice = (f[k] for k in ("i", "vid_s", "vid_d", "n_text", "prompt_ids",
                                                                                   "audio", "splice"))
             keep = {}
-            if is_video:
+            if feature_inputs:
+                # config.tdc_feature_inputs: the towers ran when the set was exported (a set made of bare tensors carries no
+                # signature to compare)
+                kw = dict(info=keep, check_signature=vid_s.signature is not None)
+                if is_video:
+                    vis = eng.encode_features(vid_s, f["btl"], n_text, prompt_ids, audio=audio, frame_cap=f["cap"], splice=splice,
+                                              video_index=f["vindex"], **kw)
+                else:
+                    vis = eng.encode_features(vid_s, None, n_text, None, image=True, **kw)
+            elif is_video:
                 vindex, cap, btl, sharded = f["vindex"], f["cap"], f["btl"], f["sharded"]
                 if sharded is not None:
                     # config.tdc_shard_frames under an initialised torch.distributed (one process per GPU, every rank called
@@ -765,6 +826,11 @@ class CambrianMetaForCausalLM(ABC):
             infos = [{} for _ in fs]
             qs = [dict(budget_text_len=f["btl"], n_text_tokens=f["n_text"], prompt_ids=f["prompt_ids"], splice=f["splice"])
                   for f in fs]
+            if feature_inputs:
+                vis = eng.encode_features_prompts(f0["vid_s"], qs, audio=f0["audio"], frame_cap=f0["cap"],
+                                                  video_index=f0["vindex"], infos=infos, max_prompts=batch_prompts,
+                                                  pad_fraction=pad_fraction, check_signature=f0["vid_s"].signature is not None)
+                return [(v, f["splice"] is not None, info["final_size"]) for v, f, info in zip(vis, fs, infos)]
             eng.two_streams = model.tdc_side_stream(min(f0["vid_s"].shape[0], f0["cap"]))
             vis = eng.encode_video_prompts(f0["vid_s"].to(eng.dev), f0["vid_d"].to(eng.dev), tuple(image_sizes[f0["i"]]), qs,
                                            audio=f0["audio"], frame_cap=f0["cap"], video_index=f0["vindex"], infos=infos,
@@ -777,8 +843,11 @@ class CambrianMetaForCausalLM(ABC):
             fs = [facts(i) for i in range(bsz)]
             same = {}
             for f in fs:
-                key = same_video_key(eng, f["vid_s"], f["vid_d"], tuple(image_sizes[f["i"]]), f["btl"], f["cap"], f["audio"],
-                                     f["vindex"])
+                if feature_inputs:
+                    key = same_features_key(eng, f["vid_s"], f["btl"], f["cap"], f["audio"], f["vindex"])
+                else:
+                    key = same_video_key(eng, f["vid_s"], f["vid_d"], tuple(image_sizes[f["i"]]), f["btl"], f["cap"], f["audio"],
+                                         f["vindex"])
                 same.setdefault(key, []).append(f)
             results = [None] * bsz
             for members in same.values():

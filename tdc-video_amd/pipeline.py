@@ -17,8 +17,8 @@ from . import segment as seg
 from . import weights as Wt
 # the orchestration over an engine (encode.py): what the methods below call, and the names this module has always offered
 from .encode import (batch_groups, cached_audio, compress_many_with, compress_with, emission_plan,  # noqa: F401
-                     encode_batch_with, encode_image_cached, encode_missing, encode_video_cached, encode_video_prompts_with,
-                     encode_video_with, frame_indices, gather_frames, join_side_tower, precise_features, prompt_groups,
+                     encode_batch_with, encode_features_prompts_with, encode_features_with, encode_image_cached, encode_missing,
+                     encode_video_cached, encode_video_prompts_with, encode_video_with, export_features_with, frame_indices, gather_frames, join_side_tower, precise_features, prompt_groups,
                      prompt_maps, same_video_key, sample_indicator, select_segments_with, start_side_tower, text_prompt,
                      visual_budget)
 from .weights import pad64
@@ -72,7 +72,7 @@ class VideoEncoder:
     beats = None                  # beats.BeatsEncoder for raw-waveform audio input
     selection_eps = None
     selection_max_fraction = 0.125
-    _tower_dtype = _conn_struct = _qf_struct = _tower_stream = _side_stream = None
+    _tower_dtype = _conn_struct = _qf_struct = _tower_stream = _side_stream = _feature_sig = None
 
     def __init__(self, sd, cfg, dtype=torch.float16, device="cuda", siglip_heads=16, dino_heads=24,
                  qformer_heads=12, tower_batch=None, fp8_towers=False, tower_dtype=None, ln_fuse=False,
@@ -426,6 +426,31 @@ class VideoEncoder:
         """a FrameCache of max_bytes for encode_video(cache=...) of this engine (cache.py)"""
         from .cache import FrameCache, engine_signature
         return FrameCache(max_bytes, engine_signature(self))
+
+    # ---- stored tower features (features.py, DESIGN.md section 13) --------------------------------------------------------
+    def tower_width(self, name):
+        """un-padded width of tower `name`'s rows: the input width of its aux projector (known without tower weights too)"""
+        return self.c.aux[0 if name == "siglip" else 1].fc1.k
+
+    def feature_rows(self, x):
+        """stored rows [T, P, D] -> the [T * P, pad64(D)] rows `tower` returns: the padding columns are the zeros its last
+        kernel writes (tdc_resample_tokens), so a5 and the connector launch on the pixel path's operands"""
+        T, P, D = x.shape
+        if x.dtype != self.dtype:
+            raise ValueError("features are %s, this engine's towers emit %s" % (x.dtype, self.dtype))
+        x = x.to(self.dev)
+        if D == pad64(D):
+            return x.reshape(T * P, D).contiguous()
+        rows = torch.zeros(T * P, pad64(D), device=self.dev, dtype=self.dtype)
+        rows[:, :D] = x.reshape(T * P, D)
+        return rows
+
+    def feature_signature(self):
+        """features.tower_signature of this engine, computed once (it fingerprints every tower weight on the device)"""
+        if self._feature_sig is None:
+            from .features import compute_tower_signature
+            self._feature_sig = compute_tower_signature(self)
+        return self._feature_sig
 
     def frame_sims(self, dino_feat, T):
         """same as a python list (one D2H copy: the segmentation is host logic)."""
@@ -995,3 +1020,29 @@ class VideoEncoder:
         `image`; -> one result per sample, bit for bit what encode_video (an image: the mixin's image branch) returns for it.
         infos: one info dict per sample (encode_batch_with).  All samples share the pixel geometry and type."""
         return encode_batch_with(self, samples, frame_cap, infos)
+
+    def export_features(self, px_siglip, px_dino, image_size):
+        """The frozen towers once per video: ALL frames of px_siglip / px_dino ([T0, 3, H, W]; one frame is an image) through
+        both towers -> features.FeatureSet (the rows `tower` returns without their padding columns, image_size, the towers'
+        signature) for encode_features / encode_features_prompts, .save(path) and FeatureSet.load.  No a1 sub-sampling: it
+        reads the prompt length and the frame cap.  The set serves any connector / Q-Former checkpoint, `context_token_num`,
+        cap and prompt; it is refused (ValueError) by an engine whose towers differ in any output bit.
+        The selection refinement needs pixels and cannot run from a set: an engine built with `tdc_dino_dtype = "float16"`
+        (dino_dtype=torch.float16) stores DINOv2 rows of the reference's own precision, and no refinement is then wanted."""
+        return export_features_with(self, px_siglip.to(self.dev), px_dino.to(self.dev), image_size)
+
+    def encode_features(self, fs, budget_text_len, n_text_tokens, prompt_ids, audio=None, frame_cap=224, splice=None,
+                        video_index=None, info=None, check_signature=True, image=False):
+        """encode_video from a FeatureSet instead of pixels: bit for bit what encode_video returns for the pixels the set was
+        exported from, whenever that call refines nothing (a band the refinement would re-encode is ranked as stored and
+        reported in info["refine_unavailable_pairs"]).  check_signature=False: no comparison of the set's signature with this
+        engine's towers (an engine that holds none).  image=True: a one-frame set as a single image - the connector only."""
+        return encode_features_with(self, fs, budget_text_len, n_text_tokens, prompt_ids, audio, frame_cap, splice, video_index,
+                                    info, check_signature, image)
+
+    def encode_features_prompts(self, fs, prompts, audio=None, frame_cap=224, video_index=None, infos=None, max_prompts=8,
+                                pad_fraction=0.25, check_signature=True):
+        """encode_video_prompts from a FeatureSet: the front from features once, then one compressor pass per group of
+        prompts -> one result per prompt, bit for bit what encode_features returns for it."""
+        return encode_features_prompts_with(self, fs, prompts, audio, frame_cap, video_index, infos, max_prompts, pad_fraction,
+                                            check_signature)
