@@ -251,8 +251,18 @@ int tdc_adaptive_pool_tokens(const void* x, int N, int frame_rows, int ld, void*
                              const int* src_row, int dtype, void* stream);
 /* out[i, :cols] = table_k[row] where (k,row) = src[2i], src[2i+1]; tables: up to 4 16-bit matrices with their ld.
  * Used for unpad+newline (cambrian_arch.py:1195-1293) and token emission (:1668-1709).
- * writes: out[i, 0 .. cols) for i < n (pad columns: caller).  reads: the `cols` columns of the table rows `src` names, src[0 .. 2n). */
-typedef struct { const void* base[4]; int ld[4]; } tdc_gather_tables;
+ * writes: out[i, 0 .. cols) for i < n (pad columns: caller).  reads: the `cols` columns of the table rows `src` names, src[0 .. 2n).
+ * scale[k] != NULL (all four NULL, as a zero-initialised struct has them: the form above, unchanged): table k holds OCP e4m3
+ * bytes [rows, ld[k]] (ld[k] in BYTES) and scale[k] one fp32 scale per table row (the compact feature store, features.py):
+ *   out[i, c] = T16(float(e4m3 table_k[row, c]) * scale_k[row]),  c < cols
+ * - one fp32 multiply, one round-to-nearest-even conversion to the call's 16-bit `dtype`; the e4m3 NaN codes give NaN.  One
+ * call may mix 16-bit and e4m3 tables.  The e4m3 form
+ * writes: out[i, 0 .. cols) only (pad columns: caller), as the 16-bit form.
+ * reads: the `cols` BYTES of the table rows `src` names and the scale_k[row] of those rows, src[0 .. 2n) - nothing else: not the
+ * bytes cols .. ld[k] behind a row, not the rows or scales `src` does not name.
+ * 16-byte stores with 16- or 8-byte loads when cols, ldo, ld[k] and the bases allow it (cols % 8 == 0, ldo % 8 == 0, out 16-byte
+ * aligned; ld[k] and base[k] multiples of 16 with cols % 16 == 0, or of 8), element-wise otherwise. */
+typedef struct { const void* base[4]; int ld[4]; const float* scale[4]; } tdc_gather_tables;
 int tdc_gather_rows(const tdc_gather_tables* t, const int* src, void* out, int ldo, int n, int cols, int dtype,
                     void* stream);
 /* every row of out [rows, ld] (16-bit, ld % 8 == 0) := row[0 .. ld) (the SVA queries start as `vision_query` on every

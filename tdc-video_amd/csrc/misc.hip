@@ -286,6 +286,63 @@ __global__ __launch_bounds__(256) void gather_kernel(tdc_gather_tables t, const 
     }
 }
 
+// ... with e4m3 tables (tdc_gather_tables.scale[k] != NULL: the compact feature store).  One wave per output row, four rows
+// per workgroup: the table, the row and its scale are wave-uniform (SGPRs, the scale read once per row), a lane decodes 16 or
+// 8 bytes per step - v_cvt_pk_f32_fp8, one fp32 multiply, packed conversion to the 16-bit type - into 16-byte stores.  A row of
+// a 16-bit table in the same call is copied as gather_kernel copies it.
+template <class T>
+__device__ __forceinline__ typename VecOf<T>::v8 decode8(unsigned w0, unsigned w1, float s) {
+    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w0, false) * s, b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w0, true) * s;
+    const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)w1, false) * s, d = __builtin_amdgcn_cvt_pk_f32_fp8((int)w1, true) * s;
+    const u32x4 r = {__builtin_bit_cast(unsigned, cvt2<T>(a[0], a[1])), __builtin_bit_cast(unsigned, cvt2<T>(b[0], b[1])),
+                     __builtin_bit_cast(unsigned, cvt2<T>(c[0], c[1])), __builtin_bit_cast(unsigned, cvt2<T>(d[0], d[1]))};
+    return __builtin_bit_cast(typename VecOf<T>::v8, r);
+}
+template <class T>
+__global__ __launch_bounds__(256) void gather_decode_kernel(tdc_gather_tables t, const int* src, T* out, int ldo, int n,
+                                                            int cols) {
+    const int lane = threadIdx.x & 63;
+    const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const int k = __builtin_amdgcn_readfirstlane(src[2 * i]), r = __builtin_amdgcn_readfirstlane(src[2 * i + 1]);
+    const int ld = t.ld[k];
+    const float* sc = t.scale[k];
+    T* o = out + i * ldo;
+    typedef typename VecOf<T>::v8 v8;
+    const bool ovec = ((cols & 7) == 0) && ((ldo & 7) == 0) && (((uintptr_t)out & 15) == 0);
+    if (!sc) {
+        const T* row = (const T*)t.base[k] + (long long)r * ld;
+        if (ovec && ((ld & 7) == 0) && (((uintptr_t)t.base[k] & 15) == 0)) {
+            for (int c = lane * 8; c < cols; c += 64 * 8) *(v8*)(o + c) = *(const v8*)(row + c);
+        } else {
+            for (int c = lane; c < cols; c += 64) o[c] = row[c];
+        }
+        return;
+    }
+    const unsigned char* row = (const unsigned char*)t.base[k] + (long long)r * ld;
+    const float s = sc[r];
+    if (ovec && ((cols & 15) == 0) && ((ld & 15) == 0) && (((uintptr_t)t.base[k] & 15) == 0)) {
+        for (int c = lane * 16; c < cols; c += 64 * 16) {
+            const u32x4 w = *(const u32x4*)(row + c);
+            *(v8*)(o + c) = decode8<T>(w[0], w[1], s);
+            *(v8*)(o + c + 8) = decode8<T>(w[2], w[3], s);
+        }
+    } else if (ovec && ((ld & 7) == 0) && (((uintptr_t)t.base[k] & 7) == 0)) {
+        for (int c = lane * 8; c < cols; c += 64 * 8) {
+            const u32x2 w = *(const u32x2*)(row + c);
+            *(v8*)(o + c) = decode8<T>(w[0], w[1], s);
+        }
+    } else {
+        for (int c = lane; c < cols; c += 64) {
+            // the product as an fp32 VALUE before it is converted: left to itself the compiler fuses multiply and conversion
+            // into one v_fma_mixlo_f16, which rounds once - not what the packed paths above (and the header) compute
+            float p = __builtin_amdgcn_cvt_f32_fp8((int)row[c], 0) * s;
+            asm volatile("" : "+v"(p));
+            o[c] = (T)p;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ SVA core
 // one wave per (query, head-group): q_len = 1, kv = n_towers * r * r <= 8 keys.  Each lane owns dim/64 channels;
 // head h covers channels [h*hd, (h+1)*hd): per-head dot products are reduced inside the lanes that share a head.
@@ -565,6 +622,11 @@ extern "C" int tdc_gather_rows(const tdc_gather_tables* t, const int* src, void*
                                int dtype, void* stream) {
     if (!t || !src || !out || n <= 0) return TDC_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
+    if (t->scale[0] || t->scale[1] || t->scale[2] || t->scale[3]) {            // e4m3 tables: decoded in the gather
+        DISPATCH(dtype, hipLaunchKernelGGL(gather_decode_kernel<TT>, dim3((unsigned)(((long long)n + 3) / 4)), dim3(256), 0, st, *t,
+                                           src, (TT*)out, ldo, n, cols));
+        return (int)hipGetLastError();
+    }
     DISPATCH(dtype, hipLaunchKernelGGL(gather_kernel<TT>, dim3(n), dim3(256), 0, st, *t, src, (TT*)out, ldo, n, cols));
     return (int)hipGetLastError();
 }

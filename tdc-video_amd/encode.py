@@ -10,7 +10,9 @@ The engine is pipeline.VideoEncoder on GPUs; the CPU tests plug in doubles.  The
   probed     mark / fetch / after (the host read beside the compute stream), two_streams / tower_stream (SigLIP on a side
              stream), emit_into, multi_prompt_ok, dev, side - absent on the doubles
   features   towers (what features.tower_signature fingerprints); probed: tower_width(name), feature_rows(x) (the tower
-             rows' padding columns), feature_signature() (the signature, cached)
+             rows' padding columns), feature_signature() (the signature, cached); compact sets (section 14):
+             quantize_feature_rows(rows, D) -> (e4m3 bytes [n, D], fp32 scales [n]), decode_feature_rows(bytes [T0, P, D],
+             scales [T0, P], idx or None, dtype) -> the rows [T * P, width] of the frames idx as `tower` returns them
 """
 import torch
 
@@ -626,17 +628,49 @@ def stored_rows(e, name, rows, T0):
     return rows[:, :D].reshape(T0, rows.shape[0] // T0, D)
 
 
-def export_features_with(e, px_siglip, px_dino, image_size):
+def export_features_with(e, px_siglip, px_dino, image_size, store="f16"):
     """a3 / a4 of EVERY input frame (no a1: it reads the prompt length and the cap) -> features.FeatureSet.  The towers run as
-    in towers_and_selection: SigLIP on the side stream under `two_streams`, after the DINOv2 tower otherwise."""
+    in towers_and_selection: SigLIP on the side stream under `two_streams`, after the DINOv2 tower otherwise.
+    store="e4m3": the compact set (compact_rows) - the bytes compact_features_with makes of the lossless set."""
     from .features import FeatureSet, tower_signature
+    if store not in ("f16", "e4m3"):
+        raise ValueError("export_features: store is \"f16\" (lossless) or \"e4m3\" (compact), got %r" % (store,))
     T0 = px_siglip.shape[0]
     if px_dino.shape[0] != T0 or T0 < 1:
         raise ValueError("export_features: %d SigLIP and %d DINOv2 frames" % (T0, px_dino.shape[0]))
     side_sig = start_side_tower(e, px_siglip)
     dino = e.tower("dino", px_dino)                                                                 # a4
     sig = join_side_tower(e, side_sig, px_siglip)                                                   # a3
+    if store == "e4m3":
+        return compact_rows(e, sig, dino, T0, image_size, tower_signature(e))
     return FeatureSet(stored_rows(e, "siglip", sig, T0), stored_rows(e, "dino", dino, T0), image_size, tower_signature(e))
+
+
+def compact_rows(e, sig, dino, T0, image_size, signature):
+    """the tower rows of ALL T0 frames ([T0 * P, >= D] each, as `tower` returns them) -> the compact FeatureSet (DESIGN.md
+    section 14): per tower the e4m3 bytes and one fp32 scale per token row (engine.quantize_feature_rows: scale = max|row| / 448,
+    1 for a zero row), and the a5 similarities of these 16-bit DINOv2 rows - taken before they are dropped, by the launch the
+    lossless path takes them with, so a selection over all T0 frames is the lossless path's bit for bit."""
+    from .features import FeatureSet
+    sims = e.sims_tensor(dino, T0) if T0 > 1 else None
+    if sims is not None and not torch.is_tensor(sims):
+        sims = torch.tensor(sims, dtype=torch.float32)
+    parts = []
+    for name, rows in (("siglip", sig), ("dino", dino)):
+        D = e.tower_width(name) if hasattr(e, "tower_width") else rows.shape[1]
+        b, sc = e.quantize_feature_rows(rows, D)
+        parts += [b.reshape(T0, rows.shape[0] // T0, D), sc.reshape(T0, rows.shape[0] // T0)]
+    return FeatureSet(parts[0], parts[2], image_size, signature, parts[1], parts[3],
+                      None if sims is None else sims.float().reshape(T0 - 1), sig.dtype)
+
+
+def compact_features_with(e, fs):
+    """a lossless FeatureSet -> its compact form, the bytes export_features_with(store="e4m3") gives for the same pixels"""
+    from .features import is_compact
+    if is_compact(fs):
+        return fs
+    sig, dino = feature_rows(e, fs)
+    return compact_rows(e, sig, dino, fs.frames, fs.image_size, fs.signature)
 
 
 def check_features(e, fs):
@@ -651,13 +685,20 @@ def check_features(e, fs):
 def feature_rows(e, fs, idx=None):
     """the stored rows of the frames idx (None: all) as the towers hand them on: ([T * P, width] SigLIP, DINOv2) on the
     engine's device.  The gather is plain indexing on the device, as the pixel path's px[sel]; engine.feature_rows restores
-    the zero padding columns the towers write, so every launch behind it sees the pixel path's operands."""
+    the zero padding columns the towers write, so every launch behind it sees the pixel path's operands.
+    A compact set: its bytes and scales go to the device and engine.decode_feature_rows does the a1 gather, the decode and the
+    padded layout in one launch per tower - the 16-bit rows of a dropped frame never exist."""
+    from .features import is_compact
     dev = getattr(e, "dev", fs.siglip.device)
     out = []
     for name, x in (("siglip", fs.siglip), ("dino", fs.dino)):
         if hasattr(e, "tower_width") and x.shape[2] != e.tower_width(name):
             raise ValueError("%s features are %d wide, the engine's tower is %d wide" % (name, x.shape[2], e.tower_width(name)))
         x = x.to(dev)
+        if is_compact(fs):
+            sc = (fs.siglip_scale if name == "siglip" else fs.dino_scale).to(dev)
+            out.append(e.decode_feature_rows(x, sc, None if idx is None or len(idx) == x.shape[0] else idx, fs.rows_dtype))
+            continue
         if idx is not None and len(idx) != x.shape[0]:              # every frame kept: the rows stay where they lie
             x = x[torch.tensor(idx, device=x.device)]
         out.append(e.feature_rows(x) if hasattr(e, "feature_rows") else x.reshape(-1, x.shape[2]))
@@ -670,6 +711,7 @@ def video_front_from_features(e, fs, budget_text_len, audio=None, frame_cap=224,
     frames' rows gathered, a5 by the pixel path's launch on the gathered DINOv2 rows, then front_after_towers -> the same dict,
     the same bits.  The selection refinement needs pixels: under engine.selection_eps a non-empty band is ranked on the stored
     similarities and reported as info["refine_unavailable_pairs"] (select_segments_with, refine=None)."""
+    from .features import is_compact
     if check_signature:
         check_features(e, fs)
     cfg = e.cfg
@@ -677,10 +719,18 @@ def video_front_from_features(e, fs, budget_text_len, audio=None, frame_cap=224,
     idx = frame_indices(cfg, T0, budget_text_len, frame_cap)                                        # a1
     T = len(idx)
     sig, dino = feature_rows(e, fs, idx)
+    compact = is_compact(fs)
     if T > cfg.get("max_num_segments", 24) + 1:                                                     # a5
-        sims_dev = e.sims_tensor(dino, T)
-        ev = e.mark() if hasattr(e, "mark") and sims_dev.is_cuda else None
-        sims = e.fetch(sims_dev, ev) if ev is not None else sims_dev.tolist()
+        if compact and fs.sims is not None and T == T0:
+            # every frame kept: the similarities of the ORIGINAL 16-bit rows, stored with the set - no launch, and the
+            # lossless path's selection bit for bit
+            sims = fs.sims.tolist()
+        else:
+            sims_dev = e.sims_tensor(dino, T)
+            ev = e.mark() if hasattr(e, "mark") and sims_dev.is_cuda else None
+            sims = e.fetch(sims_dev, ev) if ev is not None else sims_dev.tolist()
+        if compact and info is not None:
+            info["selection_sims"] = "stored" if fs.sims is not None and T == T0 else "decoded"
         seg_idx = select_segments_with(e, sims, None, info)
     else:
         seg_idx = list(range(T))
@@ -721,9 +771,13 @@ def encode_features_prompts_with(e, fs, prompts, audio=None, frame_cap=224, vide
 def same_features_key(e, fs, budget_text_len, frame_cap, audio=None, video_index=None):
     """`config.tdc_batch_prompts` over feature inputs: what two samples must share to be questions about the SAME stored
     video - the content of both feature tensors (content_key), image_size, the a1 selection, and their audio as
-    same_video_key compares it"""
+    same_video_key compares it; a compact set: its scales too"""
+    from .features import is_compact
     idx = frame_indices(e.cfg, fs.frames, budget_text_len, frame_cap)
     akey = None
     if audio is not None:
         akey = (content_key(e, audio), tuple(sample_indicator(fs.frames, idx, video_index)))
-    return (content_key(e, fs.siglip), content_key(e, fs.dino), tuple(fs.image_size), tuple(idx), akey)
+    key = (content_key(e, fs.siglip), content_key(e, fs.dino), tuple(fs.image_size), tuple(idx), akey)
+    if is_compact(fs):                      # the same bytes under other scales are other rows
+        key += (content_key(e, fs.siglip_scale), content_key(e, fs.dino_scale), str(fs.rows_dtype))
+    return key

@@ -11,23 +11,56 @@ import torch
 
 from .cache import fingerprint_rows_host
 
-FORMAT = 1
+FORMAT = 1                  # lossless sets: the 16-bit rows
+FORMAT_COMPACT = 2          # compact sets: e4m3 bytes, one fp32 scale per token row, the exact a5 similarities (section 14)
+ROWS_DTYPES = {"float16": torch.float16, "bfloat16": torch.bfloat16, "float32": torch.float32}
 
 
 class FeatureSet:
     """siglip [T0, P, Ds], dino [T0, P, Dd] (16-bit, the type the towers emit; P = 576 at full size), image_size (the source
-    image size the connector un-pads by), signature (tower_signature of the exporting engine; None: unknown)."""
+    image size the connector un-pads by), signature (tower_signature of the exporting engine; None: unknown).  store = "f16".
 
-    def __init__(self, siglip, dino, image_size, signature=None):
+    The compact form (store = "e4m3"; VideoEncoder.export_features(store="e4m3") / compact_features):
+    siglip / dino are uint8 [T0, P, D] - OCP e4m3 bytes, plain uint8 so that loading depends on no torch float8 type -,
+    siglip_scale / dino_scale fp32 [T0, P] (row = float(byte) * scale), sims fp32 [T0 - 1] - the a5 similarities of the ORIGINAL
+    16-bit DINOv2 rows of all T0 frames (None for one frame), so that a lossy store never moves the frame selection - and
+    rows_dtype, the 16-bit type the rows decode to.  The signature stays the towers': the store form is a property of the set."""
+
+    def __init__(self, siglip, dino, image_size, signature=None, siglip_scale=None, dino_scale=None, sims=None, rows_dtype=None):
         if not (torch.is_tensor(siglip) and torch.is_tensor(dino) and siglip.dim() == 3 and dino.dim() == 3):
             raise ValueError("a FeatureSet holds two [frames, tokens, width] tensors")
         if siglip.shape[:2] != dino.shape[:2] or siglip.shape[0] < 1:
             raise ValueError("SigLIP features %s and DINOv2 features %s do not describe the same frames"
                              % (tuple(siglip.shape), tuple(dino.shape)))
-        # fp32: the CPU engine doubles of the tests; VideoEncoder.feature_rows takes the engine's own 16-bit type only
-        if siglip.dtype != dino.dtype or siglip.dtype not in (torch.float16, torch.bfloat16, torch.float32):
-            raise ValueError("feature types %s / %s: both towers emit one type, fp16 or bf16" % (siglip.dtype, dino.dtype))
+        compact = siglip_scale is not None or dino_scale is not None or siglip.dtype == torch.uint8 or dino.dtype == torch.uint8
+        if compact:
+            if siglip.dtype != torch.uint8 or dino.dtype != torch.uint8:
+                raise ValueError("feature types %s / %s: a compact set holds e4m3 bytes as uint8 in both towers"
+                                 % (siglip.dtype, dino.dtype))
+            for name, sc in (("siglip_scale", siglip_scale), ("dino_scale", dino_scale)):
+                if not (torch.is_tensor(sc) and sc.dtype == torch.float32 and tuple(sc.shape) == tuple(siglip.shape[:2])):
+                    raise ValueError("%s: a compact set holds one fp32 scale per token row, %s; got %s"
+                                     % (name, tuple(siglip.shape[:2]), "%s %s" % (sc.dtype, tuple(sc.shape))
+                                        if torch.is_tensor(sc) else type(sc).__name__))
+            if sims is not None and not (torch.is_tensor(sims) and sims.dtype == torch.float32
+                                         and tuple(sims.shape) == (siglip.shape[0] - 1,)):
+                raise ValueError("sims: the %d fp32 adjacent-frame similarities of %d frames" % (siglip.shape[0] - 1, siglip.shape[0]))
+            if sims is not None and sims.numel() == 0:
+                sims = None
+            if isinstance(rows_dtype, str):
+                rows_dtype = ROWS_DTYPES.get(rows_dtype)
+            if rows_dtype not in ROWS_DTYPES.values():
+                raise ValueError("rows_dtype %r: the type the rows of a compact set decode to, fp16 or bf16" % (rows_dtype,))
+        else:
+            # fp32: the CPU engine doubles of the tests; VideoEncoder.feature_rows takes the engine's own 16-bit type only
+            if siglip.dtype != dino.dtype or siglip.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+                raise ValueError("feature types %s / %s: both towers emit one type, fp16 or bf16" % (siglip.dtype, dino.dtype))
+            if sims is not None or rows_dtype not in (None, siglip.dtype):
+                raise ValueError("a lossless set holds neither similarities nor a rows_dtype of its own")
+            rows_dtype = siglip.dtype
         self.siglip, self.dino = siglip, dino
+        self.siglip_scale, self.dino_scale, self.sims, self.rows_dtype = siglip_scale, dino_scale, sims, rows_dtype
+        self.store = "e4m3" if compact else "f16"
         self.image_size = tuple(int(v) for v in image_size)
         self.signature = None if signature is None else str(signature)
 
@@ -35,16 +68,28 @@ class FeatureSet:
     def frames(self):
         return int(self.siglip.shape[0])
 
+    def tensors(self):
+        """every tensor the set holds, by attribute name"""
+        names = ("siglip", "dino", "siglip_scale", "dino_scale", "sims")
+        return {k: getattr(self, k) for k in names if getattr(self, k) is not None}
+
+    def _with(self, f):
+        t = {k: f(v) for k, v in self.tensors().items()}
+        if self.store == "f16":
+            return FeatureSet(t["siglip"], t["dino"], self.image_size, self.signature)
+        return FeatureSet(t["siglip"], t["dino"], self.image_size, self.signature, t["siglip_scale"], t["dino_scale"],
+                          t.get("sims"), self.rows_dtype)
+
     @property
     def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in (self.siglip, self.dino))
+        return sum(t.numel() * t.element_size() for t in self.tensors().values())
 
     def to(self, device):
-        """the set with both tensors on `device` (itself when they already are)"""
+        """the set with its tensors on `device` (itself when they already are)"""
         device = torch.device(device)
-        if self.siglip.device == device and self.dino.device == device:
+        if all(t.device == device for t in self.tensors().values()):
             return self
-        return FeatureSet(self.siglip.to(device), self.dino.to(device), self.image_size, self.signature)
+        return self._with(lambda t: t.to(device))
 
     def cpu(self):
         """the set in host memory - pinned when CUDA is available, so .to(device) is one DMA per tensor"""
@@ -53,26 +98,39 @@ class FeatureSet:
                 return t
             out = torch.empty(t.shape, dtype=t.dtype, pin_memory=torch.cuda.is_available())
             return out.copy_(t)
-        return FeatureSet(host(self.siglip), host(self.dino), self.image_size, self.signature)
+        return self._with(host)
 
     def save(self, path):
-        """a plain dict of tensors, ints and strings through torch.save: no pickled class, loads with weights_only=True"""
+        """a plain dict of tensors, ints and strings through torch.save: no pickled class, loads with weights_only=True.
+        Lossless sets are format 1, as they always were; compact sets are format 2."""
         def compact(t):                         # a copy that owns exactly its bytes (a view would drag its whole storage along)
             return t.detach().to("cpu").clone(memory_format=torch.contiguous_format)
-        torch.save(dict(format=FORMAT, siglip=compact(self.siglip), dino=compact(self.dino),
-                        image_size=[int(v) for v in self.image_size], signature=self.signature or ""), path)
+        d = dict(format=FORMAT, siglip=compact(self.siglip), dino=compact(self.dino),
+                 image_size=[int(v) for v in self.image_size], signature=self.signature or "")
+        if self.store == "e4m3":
+            d.update(format=FORMAT_COMPACT, store="e4m3", siglip_scale=compact(self.siglip_scale),
+                     dino_scale=compact(self.dino_scale), rows_dtype=str(self.rows_dtype).replace("torch.", ""),
+                     sims=compact(self.sims) if self.sims is not None else torch.empty(0, dtype=torch.float32))
+        torch.save(d, path)
 
     @classmethod
     def load(cls, path, map_location="cpu"):
         d = torch.load(path, map_location=map_location, weights_only=True)
+        if isinstance(d, dict) and d.get("format") == FORMAT_COMPACT and d.get("store") == "e4m3":
+            return cls(d["siglip"], d["dino"], d["image_size"], d["signature"] or None, d["siglip_scale"], d["dino_scale"],
+                       d["sims"] if d["sims"].numel() else None, d["rows_dtype"])
         if not isinstance(d, dict) or d.get("format") != FORMAT:
-            raise ValueError("%s is not a FeatureSet file of format %d" % (path, FORMAT))
+            raise ValueError("%s is not a FeatureSet file of format %d or %d" % (path, FORMAT, FORMAT_COMPACT))
         return cls(d["siglip"], d["dino"], d["image_size"], d["signature"] or None)
 
 
 def is_feature_set(x):
-    """a FeatureSet by what it holds (the package is importable under two names, so its class is not compared)"""
+    """a FeatureSet by what it holds (the package is importable under two names, so its class is not compared); both stores"""
     return all(hasattr(x, k) for k in ("siglip", "dino", "image_size", "signature", "frames")) and not torch.is_tensor(x)
+
+
+def is_compact(fs):
+    return getattr(fs, "store", "f16") == "e4m3"
 
 
 def _walk(e, v, out):

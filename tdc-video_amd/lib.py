@@ -50,7 +50,7 @@ class AttnDesc(C.Structure):
 
 
 class GatherTables(C.Structure):
-    _fields_ = [("base", C.c_void_p * 4), ("ld", C.c_int * 4)]
+    _fields_ = [("base", C.c_void_p * 4), ("ld", C.c_int * 4), ("scale", C.c_void_p * 4)]
 
 
 class SvaAttnDesc(C.Structure):

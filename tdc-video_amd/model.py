@@ -511,7 +511,8 @@ class CambrianMetaModel:
     def tdc_feature_inputs(self):
         """`config.tdc_feature_inputs`: True = `images` carries stored tower features instead of pixels (features.FeatureSet,
         VideoEncoder.export_features): images[0][i] / images[1][i] are the SigLIP / DINOv2 rows of sample i, [T, tokens,
-        hidden_size of that tower], or images[0][i] is a FeatureSet and images[1][i] None; every sample runs through
+        hidden_size of that tower], or images[0][i] is a FeatureSet - lossless or compact (store="e4m3"; raw tensors are
+        always lossless) - and images[1][i] None; every sample runs through
         VideoEncoder.encode_features (images: its connector-only form).  Absent / False: pixels.  Set together with
         `config.tdc_shard_frames`, `tdc_batch_frames`, `tdc_video_cache_bytes` or `tdc_shard_cache_bytes` it raises: those need
         pixels, or key on them.  `config.tdc_batch_prompts` composes with it."""

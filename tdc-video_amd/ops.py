@@ -488,16 +488,30 @@ def check_pairs_host(pairs, table_rows):
     assert (p[:, 1] < lim).all(), "gather row out of range"
 
 
-def gather_rows(tables, src, n, cols, out=None, validated=False):
+def gather_rows(tables, src, n, cols, out=None, validated=False, scales=None, dtype=None):
     """tables: list of <= 4 2-D 16-bit tensors; src int32 [n, 2] (table, row) on the device.  validated=True: the caller
-    has range-checked the map on the host (check_pairs_host) - skips the device-side check and its synchronisations."""
+    has range-checked the map on the host (check_pairs_host) - skips the device-side check and its synchronisations.
+    scales: per table None or an fp32 tensor [rows] - that table then holds e4m3 bytes (uint8 [rows, >= cols]) decoded in the
+    gather, out = T16(float(byte) * scale[row]); dtype: the 16-bit output type (needed when every table is e4m3)."""
     gt = L.GatherTables()
-    dtype = tables[0].dtype
+    scales = list(scales) if scales is not None else [None] * len(tables)
+    assert 1 <= len(tables) <= 4 and len(scales) == len(tables)
+    if dtype is None:
+        plain = [t.dtype for t, s in zip(tables, scales) if s is None]
+        assert plain, "gather_rows over e4m3 tables alone needs the output dtype"
+        dtype = plain[0]
     rows_ok = []
-    for i, t in enumerate(tables):
+    for i, (t, s) in enumerate(zip(tables, scales)):
         if t.dim() == 1:
             t = t.view(1, -1)
-        assert t.is_cuda and t.stride(1) == 1 and t.dtype == dtype and t.shape[1] >= cols
+        assert t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and t.shape[1] >= cols
+        if s is None:
+            assert t.dtype == dtype
+        else:
+            assert t.dtype in FP8_DTYPES, "an e4m3 table is uint8 (or a torch float8_e4m3fn) tensor"
+            assert s.is_cuda and s.dtype == torch.float32 and s.dim() == 1 and s.is_contiguous() and s.shape[0] == t.shape[0], \
+                "one contiguous fp32 scale per table row"
+            gt.scale[i] = s.data_ptr()
         gt.base[i] = t.data_ptr()
         gt.ld[i] = t.stride(0)
         rows_ok.append(t.shape[0])
@@ -511,7 +525,7 @@ def gather_rows(tables, src, n, cols, out=None, validated=False):
                 assert int(sel.max()) < r and int(sel.min()) >= 0, "gather row out of range"
     if out is None:
         out = torch.empty(n, cols, device=src.device, dtype=dtype)
-    assert out.shape[0] >= n and out.shape[1] >= cols and out.stride(1) == 1
+    assert out.dtype == dtype and out.shape[0] >= n and out.shape[1] >= cols and out.stride(1) == 1
     L.check(L.load().tdc_gather_rows(C.byref(gt), _ptr(src), _ptr(out), out.stride(0), n, cols, _dtcode(dtype),
                                      _stream()), "tdc_gather_rows")
     return out

@@ -16,7 +16,7 @@ from . import ops
 from . import segment as seg
 from . import weights as Wt
 # the orchestration over an engine (encode.py): what the methods below call, and the names this module has always offered
-from .encode import (batch_groups, cached_audio, compress_many_with, compress_with, emission_plan,  # noqa: F401
+from .encode import (batch_groups, cached_audio, compact_features_with, compress_many_with, compress_with, emission_plan,  # noqa: F401
                      encode_batch_with, encode_features_prompts_with, encode_features_with, encode_image_cached, encode_missing,
                      encode_video_cached, encode_video_prompts_with, encode_video_with, export_features_with, frame_indices, gather_frames, join_side_tower, precise_features, prompt_groups,
                      prompt_maps, same_video_key, sample_indicator, select_segments_with, start_side_tower, text_prompt,
@@ -444,6 +444,42 @@ class VideoEncoder:
         rows = torch.zeros(T * P, pad64(D), device=self.dev, dtype=self.dtype)
         rows[:, :D] = x.reshape(T * P, D)
         return rows
+
+    def quantize_feature_rows(self, rows, D):
+        """tower rows [n, >= D] (16-bit) -> (e4m3 bytes uint8 [n, D], fp32 scales [n]) of the compact feature store (DESIGN.md
+        section 14): tdc_quantize_rows_fp8 with wscale = 1 and ldy8 = D - scale = max|row| / 448 (1 for a zero row), bytes =
+        e4m3(row / scale)"""
+        if rows.dtype != self.dtype:
+            raise ValueError("features are %s, this engine's towers emit %s" % (rows.dtype, self.dtype))
+        if D % 8 or D > 4608:
+            raise ValueError("the compact feature store takes tower widths that are multiples of 8, at most 4608; got %d" % D)
+        if rows.stride(0) % 8 or rows.data_ptr() % 16:          # stored [n, D] rows of a view: the kernel reads 16-byte pieces
+            rows = rows.contiguous()
+        y8 = torch.empty(rows.shape[0], D, device=self.dev, dtype=torch.uint8)
+        _, stats = ops.quantize_rows_fp8(rows, D, 1.0, y8=y8)
+        return y8, stats[:, 1].contiguous()
+
+    def decode_feature_rows(self, x8, scale, idx, dtype):
+        """compact rows x8 [T0, P, D] (e4m3 bytes) with scale [T0, P], the frames idx (None: all) -> the [T * P, pad64(D)] rows
+        `tower` returns for them, up to the e4m3 rounding: ONE tdc_gather_rows launch gathers the kept frames, decodes them and
+        lays them out; the padding columns are the zeros of the allocation"""
+        T0, P, D = x8.shape
+        if dtype != self.dtype:
+            raise ValueError("the compact features decode to %s, this engine's towers emit %s" % (dtype, self.dtype))
+        x8, scale = x8.to(self.dev).contiguous(), scale.to(self.dev).contiguous()
+        if idx is None:
+            frames = torch.arange(T0, device=self.dev, dtype=torch.int32)
+        else:                                   # the kernel trusts its indices: range-checked here, on the host
+            assert len(idx) and min(idx) >= 0 and max(idx) < T0, "frame out of range"
+            frames = torch.tensor(list(idx), device=self.dev, dtype=torch.int32)
+        assert T0 * P < 2 ** 31
+        rows = (frames[:, None] * P + torch.arange(P, device=self.dev, dtype=torch.int32)[None]).reshape(-1)
+        src = torch.stack([torch.zeros_like(rows), rows], 1).contiguous()
+        n = rows.shape[0]
+        Dp = pad64(D)
+        out = (torch.empty if Dp == D else torch.zeros)(n, Dp, device=self.dev, dtype=self.dtype)
+        return ops.gather_rows([x8.view(T0 * P, D)], src, n, D, out=out, validated=True, scales=[scale.view(T0 * P)],
+                               dtype=self.dtype)
 
     def feature_signature(self):
         """features.tower_signature of this engine, computed once (it fingerprints every tower weight on the device)"""
@@ -1021,15 +1057,23 @@ class VideoEncoder:
         infos: one info dict per sample (encode_batch_with).  All samples share the pixel geometry and type."""
         return encode_batch_with(self, samples, frame_cap, infos)
 
-    def export_features(self, px_siglip, px_dino, image_size):
+    def export_features(self, px_siglip, px_dino, image_size, store="f16"):
         """The frozen towers once per video: ALL frames of px_siglip / px_dino ([T0, 3, H, W]; one frame is an image) through
         both towers -> features.FeatureSet (the rows `tower` returns without their padding columns, image_size, the towers'
         signature) for encode_features / encode_features_prompts, .save(path) and FeatureSet.load.  No a1 sub-sampling: it
         reads the prompt length and the frame cap.  The set serves any connector / Q-Former checkpoint, `context_token_num`,
         cap and prompt; it is refused (ValueError) by an engine whose towers differ in any output bit.
         The selection refinement needs pixels and cannot run from a set: an engine built with `tdc_dino_dtype = "float16"`
-        (dino_dtype=torch.float16) stores DINOv2 rows of the reference's own precision, and no refinement is then wanted."""
-        return export_features_with(self, px_siglip.to(self.dev), px_dino.to(self.dev), image_size)
+        (dino_dtype=torch.float16) stores DINOv2 rows of the reference's own precision, and no refinement is then wanted.
+        store="e4m3": the compact set - one e4m3 byte per value and one fp32 scale per token row, half
+        the bytes wherever the set lives or moves, decoded in the row gather of encode_features; it carries the exact a5
+        similarities of the 16-bit rows, so a call that keeps every frame selects the lossless path's key frames bit for bit.
+        The connector and Q-Former operands are lossy (measured contract: section 14)."""
+        return export_features_with(self, px_siglip.to(self.dev), px_dino.to(self.dev), image_size, store)
+
+    def compact_features(self, fs):
+        """a lossless FeatureSet -> the compact one, on the device: the bytes export_features(store="e4m3") gives"""
+        return compact_features_with(self, fs)
 
     def encode_features(self, fs, budget_text_len, n_text_tokens, prompt_ids, audio=None, frame_cap=224, splice=None,
                         video_index=None, info=None, check_signature=True, image=False):
