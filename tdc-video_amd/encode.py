@@ -13,6 +13,8 @@ The engine is pipeline.VideoEncoder on GPUs; the CPU tests plug in doubles.  The
              rows' padding columns), feature_signature() (the signature, cached); compact sets (section 14):
              quantize_feature_rows(rows, D) -> (e4m3 bytes [n, D], fp32 scales [n]), decode_feature_rows(bytes [T0, P, D],
              scales [T0, P], idx or None, dtype) -> the rows [T * P, width] of the frames idx as `tower` returns them
+  frames     pixels_from_frames(frames uint8 [T0, H, W, 3], idx or None) -> (px_siglip, px_dino) of the frames idx, as the
+             pixel entries take them
 """
 import torch
 
@@ -578,18 +580,26 @@ def video_front_cached(e, cache, px_siglip, px_dino, image_size, budget_text_len
     frames are gathered out of the slab.  -> video_front_with's dict plus `cache_info()` (the info["cache"] entry, read after
     the compressor ran), or None when the call's frames exceed the budget (info["cache"] says bypassed; nothing stored).  The
     tower batches see the HBM the cache holds as taken (auto_tower_batch): the rate may change, not the bits."""
+    T0 = px_siglip.shape[0]
+    idx = frame_indices(e.cfg, T0, budget_text_len, frame_cap)                                      # a1
+    return front_cached_selected(e, cache, px_siglip, px_dino, idx, idx, T0, image_size, audio, video_index, info)
+
+
+def front_cached_selected(e, cache, px_siglip, px_dino, rows, idx, T0, image_size, audio=None, video_index=None, info=None):
+    """video_front_cached behind a1: the kept frames are the rows `rows` of px_siglip / px_dino and the frames idx of the
+    T0-frame video.  The pixel entry passes rows = idx (the pixels of all T0 frames); the frames entry
+    (video_front_from_frames) has resized only the kept frames and passes rows = 0 .. T-1.  Audio and the returned idx refer
+    to the video's own frame numbers; the cache keys are the fingerprints of the pixels either way."""
     cfg = e.cfg
     cache.bind(e)
-    T0 = px_siglip.shape[0]
-    idx = frame_indices(cfg, T0, budget_text_len, frame_cap)                                        # a1
     T = len(idx)
-    keys, dkeys = cache.frame_keys(e, px_siglip, px_dino, idx, image_size)
+    keys, dkeys = cache.frame_keys(e, px_siglip, px_dino, rows, image_size)
     before = cache.stats()
     segmented = T > cfg.get("max_num_segments", 24) + 1
     early = {}
     # a3/a4, a6-a10 for the frames the cache lacks, a5 of the new frames' pairs enqueued BEFORE the SigLIP tower; a call whose
     # frames exceed the budget (known once the first frames fixed the row geometry) runs uncached
-    new = encode_missing(e, cache, keys, px_siglip, px_dino, idx, image_size, lambda new, dino: early.update(
+    new = encode_missing(e, cache, keys, px_siglip, px_dino, rows, image_size, lambda new, dino: early.update(
         cache.early_sims(e, keys, dkeys, new, dino, segmented))) if cache.fits(keys) else None
     if new is None:
         if info is not None:
@@ -602,8 +612,8 @@ def video_front_cached(e, cache, px_siglip, px_dino, image_size, budget_text_len
 
         def precise(pairs):
             frames = seg.band_frames(pairs)
-            feats = precise_features(e, px_dino, [idx[f] for f in frames])
-            return e.pair_sims(feats, [(idx[i], idx[i + 1]) for i in pairs]).tolist()
+            feats = precise_features(e, px_dino, [rows[f] for f in frames])
+            return e.pair_sims(feats, [(rows[i], rows[i + 1]) for i in pairs]).tolist()
         seg_idx = select_segments_with(e, sims, lambda band: cache.precise_sims(band, dkeys, precise), info)
     X = cache.assemble(e, keys)
     N = cache.rows_per_frame
@@ -781,3 +791,97 @@ def same_features_key(e, fs, budget_text_len, frame_cap, audio=None, video_index
     if is_compact(fs):                      # the same bytes under other scales are other rows
         key += (content_key(e, fs.siglip_scale), content_key(e, fs.dino_scale), str(fs.rows_dtype))
     return key
+
+
+# ---- encode from decoded uint8 frames: select, then resize what runs ----------------------------------
+EXPORT_FRAMES_SLAB = 256        # frames per tower pass of export_features_from_frames_with (tower rows do not depend on it)
+
+
+def frames_size(frames, image_size=None):
+    """(T0, image_size) of decoded frames [T0, H, W, 3]; image_size defaults to (H, W), what the reference's drivers pass"""
+    shape = tuple(frames.shape) if hasattr(frames, "shape") else (len(frames),) + tuple(frames[0].shape)
+    if len(shape) != 4 or shape[0] < 1:
+        raise ValueError("frames must be [T0, H, W, 3] with T0 >= 1, got %s" % (shape,))
+    return int(shape[0]), (tuple(image_size) if image_size is not None else (int(shape[1]), int(shape[2])))
+
+
+def video_front_from_frames(e, frames, image_size, budget_text_len, audio=None, frame_cap=224, video_index=None, info=None,
+                            cache=None):
+    """video_front from the decoded frames of a video (uint8 [T0, H, W, 3]) instead of its pixels: a1 FIRST, on the frame
+    count alone, then only the kept frames are resized and normalised (engine.pixels_from_frames), then the pixel front's
+    towers_and_selection and front_after_towers with T0 and idx handed over as video_front_with hands them - the same
+    launches on the same operands, so the same dict and the same bits as the pixel front on process_images of ALL frames.
+    Audio and info["frame_indices"] refer to the video's own frame numbers.  cache: the kept pixels go through
+    front_cached_selected (a1 is not run again on the selected set); the keys are the pixel fingerprints, so a video asked
+    first through pixels hits here.  info gains frames_in = T0 and frames_resized = len(idx)."""
+    cfg = e.cfg
+    T0, image_size = frames_size(frames, image_size)
+    idx = frame_indices(cfg, T0, budget_text_len, frame_cap)                                        # a1
+    T = len(idx)
+    px_siglip, px_dino = e.pixels_from_frames(frames, idx)
+    if info is not None:
+        info.update(frames_in=T0, frames_resized=T)
+    if cache is not None:
+        f = front_cached_selected(e, cache, px_siglip, px_dino, list(range(T)), idx, T0, image_size, audio, video_index, info)
+        if f is not None:
+            return f
+    sig, dino, (seg_idx,) = towers_and_selection(e, px_siglip, px_dino, [(0, T, T > cfg.get("max_num_segments", 24) + 1)],
+                                                 None if info is None else [info])                  # a3-a5
+    return front_after_towers(e, sig, dino, seg_idx, T0, idx, image_size, audio, None, video_index)
+
+
+def encode_frames_with(e, frames, budget_text_len, n_text_tokens, prompt_ids, audio=None, frame_cap=224, splice=None,
+                       video_index=None, info=None, cache=None, image_size=None, image=False):
+    """encode_video_with from decoded frames: bit for bit its result on process_images of the same frames.  image=True (one
+    frame): the connector rows [:, :H] of the image, as prepare_inputs_labels_for_multimodal's image branch (through the
+    cache when one is given; info receives final_size)."""
+    if image:
+        T0, image_size = frames_size(frames, image_size)
+        if T0 != 1:
+            raise ValueError("image=True takes one frame, got %d" % T0)
+        px_siglip, px_dino = e.pixels_from_frames(frames, None)
+        if cache is not None:
+            X, sizes = encode_image_cached(e, cache, px_siglip, px_dino, image_size)
+        else:
+            X, sizes = e.connector(e.tower("siglip", px_siglip), e.tower("dino", px_dino), 1, [tuple(image_size)])
+        if info is not None:
+            info.update(final_size=sizes, frames_in=1, frames_resized=1)
+        return X[:, :e.H]
+    f = video_front_from_frames(e, frames, image_size, budget_text_len, audio, frame_cap, video_index, info, cache)
+    return encode_front(e, f, n_text_tokens, prompt_ids, None, splice, info)
+
+
+def encode_frames_prompts_with(e, frames, prompts, audio=None, frame_cap=224, video_index=None, infos=None, cache=None,
+                               max_prompts=8, pad_fraction=0.25, image_size=None):
+    """encode_video_prompts_with from decoded frames: the front from frames once per distinct a1 selection (each resizes its
+    own kept frames), the selection's prompts through compress_many_with -> one result per prompt, bit for bit
+    encode_frames_with's"""
+    T0, image_size = frames_size(frames, image_size)
+
+    def front(btl, finfo):
+        return video_front_from_frames(e, frames, image_size, btl, audio, frame_cap, video_index, finfo, cache)
+    return prompts_over_fronts(e, T0, prompts, front, frame_cap, infos, max_prompts, pad_fraction)
+
+
+def export_features_from_frames_with(e, frames, store="f16", image_size=None, slab=None):
+    """export_features_with from decoded frames: EVERY frame (no a1), preprocessed and run through both towers `slab` frames
+    at a time (default EXPORT_FRAMES_SLAB), the rows concatenated.  Tower rows do not depend on the tower batch, so the set equals
+    export_features_with(*process_images(frames)) bit for bit - without the pixels of all T0 frames ever existing."""
+    from .features import FeatureSet, tower_signature
+    if store not in ("f16", "e4m3"):
+        raise ValueError("export_features: store is \"f16\" (lossless) or \"e4m3\" (compact), got %r" % (store,))
+    T0, image_size = frames_size(frames, image_size)
+    slab = EXPORT_FRAMES_SLAB if slab is None else int(slab)
+    if slab < 1:
+        raise ValueError("export_features: slab must be a positive frame count, got %r" % (slab,))
+    sigs, dinos = [], []
+    for s in range(0, T0, slab):
+        px_siglip, px_dino = e.pixels_from_frames(frames, list(range(s, min(s + slab, T0))))
+        side_sig = start_side_tower(e, px_siglip)
+        dinos.append(e.tower("dino", px_dino))                                                      # a4
+        sigs.append(join_side_tower(e, side_sig, px_siglip))                                        # a3
+    sig = sigs[0] if len(sigs) == 1 else torch.cat(sigs, 0)
+    dino = dinos[0] if len(dinos) == 1 else torch.cat(dinos, 0)
+    if store == "e4m3":
+        return compact_rows(e, sig, dino, T0, image_size, tower_signature(e))
+    return FeatureSet(stored_rows(e, "siglip", sig, T0), stored_rows(e, "dino", dino, T0), image_size, tower_signature(e))

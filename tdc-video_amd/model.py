@@ -373,7 +373,8 @@ class CambrianMetaModel:
         `config.tdc_frame_cap` (default 224 = the reference's "in case of OOM" constant, tdc/cambrian_arch.py:907-916,813-822):
         the cap of both frame sub-samplings; `config.tdc_shard_frames`: see prepare_inputs_labels_for_multimodal;
         `config.tdc_video_cache_bytes`: see tdc_video_cache; `config.tdc_shard_cache_bytes`: see tdc_shard_cache;
-        `config.tdc_batch_frames`: see tdc_batch_frames; `config.tdc_feature_inputs`: see tdc_feature_inputs.
+        `config.tdc_batch_frames`: see tdc_batch_frames; `config.tdc_feature_inputs`: see tdc_feature_inputs;
+        `config.tdc_frame_inputs`: see tdc_frame_inputs.
         bench.py's line is reproduced by dtype=float16, tdc_tower_dtype="bfloat16", tdc_tower_res_dtype="float16",
         tdc_frame_cap=T (its `product_setting` field says so; `bench.py --via-mixin` runs exactly that)."""
         if self._tdc_encoder is None or refresh:
@@ -525,6 +526,26 @@ class CambrianMetaModel:
             for other in ("tdc_shard_frames", "tdc_batch_frames", "tdc_video_cache_bytes", "tdc_shard_cache_bytes"):
                 if getattr(self.config, other, None):
                     raise ValueError("config.tdc_feature_inputs and config.%s cannot be set together" % other)
+        return v
+
+    def tdc_frame_inputs(self):
+        """`config.tdc_frame_inputs`: True = `images` carries decoded uint8 frames instead of pixels.  Videos: images[0][i] is the
+        uint8 [T, H, W, 3] tensor (or numpy array) of sample i, on the host or the device, and images[1] is ignored (None);
+        single images: images[0] is uint8 [bsz, H, W, 3].  Every sample runs through VideoEncoder.encode_frames: a1 first, then
+        only the kept frames are uploaded and resized - the 10-tuple is bit for bit the pixel call's on
+        preprocess.process_images of the same frames.  Absent / False: pixels.  Composes with `config.tdc_video_cache_bytes`;
+        set together with `config.tdc_feature_inputs`, `tdc_shard_frames`, `tdc_batch_frames`, `tdc_shard_cache_bytes` or
+        `tdc_batch_prompts` it raises: those paths take pixels or features."""
+        v = getattr(self.config, "tdc_frame_inputs", None)
+        if v is None:
+            return False
+        if not isinstance(v, bool):
+            raise ValueError("config.tdc_frame_inputs must be True / False (absent = off), got %r" % (v,))
+        if v:
+            for other in ("tdc_feature_inputs", "tdc_shard_frames", "tdc_batch_frames", "tdc_shard_cache_bytes",
+                          "tdc_batch_prompts"):
+                if getattr(self.config, other, None):
+                    raise ValueError("config.tdc_frame_inputs and config.%s cannot be set together" % other)
         return v
 
     def tdc_prompt_pad_fraction(self):
@@ -681,6 +702,7 @@ class CambrianMetaForCausalLM(ABC):
         towers = model.get_vision_tower_aux_list()
         if towers is None or images is None or input_ids.shape[1] == 1:
             return (input_ids, position_ids, attention_mask, past_key_values, None, labels, None, None, None, None)
+        frame_inputs = model.tdc_frame_inputs()      # config.tdc_frame_inputs: `images` holds decoded uint8 frames
         feature_inputs = model.tdc_feature_inputs()  # config.tdc_feature_inputs: `images` holds stored tower features
         if feature_inputs:
             feature_sets = self._feature_sets(images, image_sizes, input_ids.shape[0])      # validated before any engine call
@@ -692,7 +714,10 @@ class CambrianMetaForCausalLM(ABC):
         cfgd = self._cfg()
         K = cfgd.get("context_token_num", 16)
         H = model.config.hidden_size
-        is_video = isinstance(images[0], (list, tuple)) if feature_inputs else type(images[0]) is list or images[0].ndim == 5
+        if feature_inputs or frame_inputs:
+            is_video = isinstance(images[0], (list, tuple))
+        else:
+            is_video = type(images[0]) is list or images[0].ndim == 5
         bsz = input_ids.shape[0]
         # every integer decision below (text lengths, <image> positions, which rows survive the mask) is taken on ONE host copy of
         # the ids / mask: a device-side torch.where(...).tolist() waits for everything queued on the stream - the previous
@@ -707,6 +732,8 @@ class CambrianMetaForCausalLM(ABC):
             """the host-side facts of sample i: pixels, text lengths, prompt ids, audio, a21 hand-off, frame cap"""
             if feature_inputs:
                 vid_s, vid_d = feature_sets[i], None
+            elif frame_inputs:
+                vid_s, vid_d = (images[0][i] if is_video else images[0][i:i + 1]), None
             elif is_video:
                 vid_s, vid_d = images[0][i], images[1][i]
                 if vid_s.ndim == 3:
@@ -771,6 +798,15 @@ class CambrianMetaForCausalLM(ABC):
                                               video_index=f["vindex"], **kw)
                 else:
                     vis = eng.encode_features(vid_s, None, n_text, None, image=True, **kw)
+            elif frame_inputs:
+                # config.tdc_frame_inputs: a1 first, then only the kept frames are uploaded and resized
+                kw = dict(info=keep, cache=vcache, image_size=None if image_sizes is None else tuple(image_sizes[i]))
+                if is_video:
+                    eng.two_streams = model.tdc_side_stream(min(len(vid_s), f["cap"]))
+                    vis = eng.encode_frames(vid_s, f["btl"], n_text, prompt_ids, audio=audio, frame_cap=f["cap"], splice=splice,
+                                            video_index=f["vindex"], **kw)
+                else:
+                    vis = eng.encode_frames(vid_s, None, n_text, None, image=True, **kw)
             elif is_video:
                 vindex, cap, btl, sharded = f["vindex"], f["cap"], f["btl"], f["sharded"]
                 if sharded is not None:

@@ -13,14 +13,16 @@ import torch
 
 from . import lib as L
 from . import ops
+from . import preprocess
 from . import segment as seg
 from . import weights as Wt
 # the orchestration over an engine (encode.py): what the methods below call, and the names this module has always offered
 from .encode import (batch_groups, cached_audio, compact_features_with, compress_many_with, compress_with, emission_plan,  # noqa: F401
-                     encode_batch_with, encode_features_prompts_with, encode_features_with, encode_image_cached, encode_missing,
-                     encode_video_cached, encode_video_prompts_with, encode_video_with, export_features_with, frame_indices, gather_frames, join_side_tower, precise_features, prompt_groups,
-                     prompt_maps, same_video_key, sample_indicator, select_segments_with, start_side_tower, text_prompt,
-                     visual_budget)
+                     encode_batch_with, encode_features_prompts_with, encode_features_with, encode_frames_prompts_with,
+                     encode_frames_with, encode_image_cached, encode_missing, encode_video_cached, encode_video_prompts_with,
+                     encode_video_with, export_features_from_frames_with, export_features_with, frame_indices, gather_frames,
+                     join_side_tower, precise_features, prompt_groups, prompt_maps, same_video_key, sample_indicator,
+                     select_segments_with, start_side_tower, text_prompt, visual_budget)
 from .weights import pad64
 
 ACT_CODES = {"gelu_tanh": L.ACT_GELU_TANH, "gelu_erf": L.ACT_GELU_ERF, "swiglu": L.ACT_SWIGLU}
@@ -72,11 +74,14 @@ class VideoEncoder:
     beats = None                  # beats.BeatsEncoder for raw-waveform audio input
     selection_eps = None
     selection_max_fraction = 0.125
+    frame_towers = (preprocess.SIGLIP, preprocess.DINOV2)      # {R, mean, std} per tower for the frame entries (section 15)
+    frame_slab = 64               # frames per resize launch of pixels_from_frames (bounds its scratch; not the result)
     _tower_dtype = _conn_struct = _qf_struct = _tower_stream = _side_stream = _feature_sig = None
 
     def __init__(self, sd, cfg, dtype=torch.float16, device="cuda", siglip_heads=16, dino_heads=24,
                  qformer_heads=12, tower_batch=None, fp8_towers=False, tower_dtype=None, ln_fuse=False,
-                 tower_res_dtype=None, dino_dtype=None, selection_refine=None, selection_eps=1e-3, selection_max_fraction=0.125):
+                 tower_res_dtype=None, dino_dtype=None, selection_refine=None, selection_eps=1e-3, selection_max_fraction=0.125,
+                 frame_towers=None):
         """sd: reference-named state dict without the leading 'model.'; cfg: dict of reference config keys.
         dtype: 16-bit type of the connector, the Q-Former and every tensor handed to the caller; tower_dtype (default:
         dtype): 16-bit type of the two ViT towers - their last kernel (the token-grid resample) writes `dtype` rows.  bf16
@@ -104,8 +109,12 @@ class VideoEncoder:
         epilogues read-modify-write 8 B per element); torch.float16 (or bfloat16): that 16-bit type - 4 B per element, half
         the LayerNorm input bytes, sums formed in fp32 and rounded once per residual add.  fp16 is the reference's own
         arithmetic (its HF towers run under torch_dtype=float16, tdc/builder.py:69).  Composes with fp8_towers (round 6) and, when the
-        operands have the stream's type, with ln_fuse."""
+        operands have the stream's type, with ln_fuse.
+        frame_towers: what the frame entries (pixels_from_frames, encode_frames ...) resize decoded frames to - a pair of
+        dicts {R, mean, std}, SigLIP's then DINOv2's; default (preprocess.SIGLIP, preprocess.DINOV2): 384 / 378 px."""
         self.cfg = dict(cfg)
+        if frame_towers is not None:
+            self.frame_towers = tuple(frame_towers)
         self.tower_res_dtype = None if tower_res_dtype in (None, torch.float32) else tower_res_dtype
         assert self.tower_res_dtype in (None, torch.float16, torch.bfloat16)
         # the LayerNorm fold over a 16-bit stream: the consumer GEMMs read the stream itself as their A operand, so the
@@ -1090,3 +1099,37 @@ class VideoEncoder:
         prompts -> one result per prompt, bit for bit what encode_features returns for it."""
         return encode_features_prompts_with(self, fs, prompts, audio, frame_cap, video_index, infos, max_prompts, pad_fraction,
                                             check_signature)
+
+    # ---- decoded uint8 frames in (DESIGN.md section 15) ------------------------------------------------------------------
+    def pixels_from_frames(self, frames, idx=None, stats=None):
+        """decoded frames uint8 [T0, H, W, 3] (torch tensor - pageable, pinned or on the device - or numpy array) and the
+        ascending host list idx of the frames to keep (None: all) -> (px_siglip, px_dino) of the kept frames in the engine's
+        `dtype`, bit for bit preprocess.process_images(frames[idx], dtype, frame_towers): the reference's process_images on the
+        device.  Only the kept frames are uploaded and resized (preprocess.preprocess_selected)."""
+        if len(self.frame_towers) != 2:
+            raise ValueError("frame_towers is a pair of {R, mean, std} dicts (SigLIP, DINOv2), got %d" % len(self.frame_towers))
+        px_siglip, px_dino = preprocess.preprocess_selected(frames, idx, self.frame_towers, self.dtype, self.frame_slab,
+                                                            self.dev, stats=stats)
+        return px_siglip, px_dino
+
+    def encode_frames(self, frames, budget_text_len, n_text_tokens, prompt_ids, audio=None, frame_cap=224, splice=None,
+                      video_index=None, info=None, cache=None, image_size=None, image=False):
+        """encode_video from the decoded frames of a video, uint8 [T0, H, W, 3] as a decoder hands them over (host or device),
+        instead of pixels: a1 runs first, on the frame count, and only the frames it keeps are uploaded, resized and normalised
+        (pixels_from_frames) - bit for bit what encode_video returns for preprocess.process_images of all frames.  The other
+        arguments are encode_video's; image_size defaults to the frames' (H, W), what the reference's drivers pass.  info
+        gains frames_in and frames_resized.  image=True: one frame as a single image - the towers and the connector only."""
+        return encode_frames_with(self, frames, budget_text_len, n_text_tokens, prompt_ids, audio, frame_cap, splice,
+                                  video_index, info, cache, image_size, image)
+
+    def encode_frames_prompts(self, frames, prompts, audio=None, frame_cap=224, video_index=None, infos=None, cache=None,
+                              max_prompts=8, pad_fraction=0.25, image_size=None):
+        """encode_video_prompts from decoded frames: one result per prompt, bit for bit what encode_frames returns for it"""
+        return encode_frames_prompts_with(self, frames, prompts, audio, frame_cap, video_index, infos, cache, max_prompts,
+                                          pad_fraction, image_size)
+
+    def export_features_from_frames(self, frames, store="f16", image_size=None, slab=None):
+        """export_features from decoded frames: every frame, preprocessed and run through the towers `slab` frames at a time
+        (default encode.EXPORT_FRAMES_SLAB; the rows do not depend on it) - the set export_features gives for
+        preprocess.process_images of the frames, bit for bit, without the pixels of all frames ever being resident"""
+        return export_features_from_frames_with(self, frames, store, image_size, slab)
