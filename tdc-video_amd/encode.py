@@ -12,7 +12,9 @@ The engine is pipeline.VideoEncoder on GPUs; the CPU tests plug in doubles.  The
   features   towers (what features.tower_signature fingerprints); probed: tower_width(name), feature_rows(x) (the tower
              rows' padding columns), feature_signature() (the signature, cached); compact sets (section 14):
              quantize_feature_rows(rows, D) -> (e4m3 bytes [n, D], fp32 scales [n]), decode_feature_rows(bytes [T0, P, D],
-             scales [T0, P], idx or None, dtype) -> the rows [T * P, width] of the frames idx as `tower` returns them
+             scales [T0, P], idx or None, dtype) -> the rows [T * P, width] of the frames idx as `tower` returns them;
+             probed: gap_sims_tensor(dino rows, T0, G) -> fp32 [G, T0 - 1], the similarities across gaps 1 .. G (section 16;
+             gap_sims does it through sims_tensor on an engine without the method)
   frames     pixels_from_frames(frames uint8 [T0, H, W, 3], idx or None) -> (px_siglip, px_dino) of the frames idx, as the
              pixel entries take them
 """
@@ -638,13 +640,61 @@ def stored_rows(e, name, rows, T0):
     return rows[:, :D].reshape(T0, rows.shape[0] // T0, D)
 
 
-def export_features_with(e, px_siglip, px_dino, image_size, store="f16"):
-    """a3 / a4 of EVERY input frame (no a1: it reads the prompt length and the cap) -> features.FeatureSet.  The towers run as
-    in towers_and_selection: SigLIP on the side stream under `two_streams`, after the DINOv2 tower otherwise.
-    store="e4m3": the compact set (compact_rows) - the bytes compact_features_with makes of the lossless set."""
-    from .features import FeatureSet, tower_signature
+def check_store(store, gaps=None):
     if store not in ("f16", "e4m3"):
         raise ValueError("export_features: store is \"f16\" (lossless) or \"e4m3\" (compact), got %r" % (store,))
+    if gaps is not None and store != "e4m3":
+        raise ValueError("export_features: gaps=%r asks for the similarity table of a compact set (store=\"e4m3\"); a "
+                         "lossless set keeps its rows and needs none" % (gaps,))
+
+
+def auto_gaps(cfg, T0):
+    """the widest gap between two frames a5 can ever rank on a T0-frame video: a1 keeps uniform_indices(T0, m), whose
+    neighbours lie floor(T0 / m) or ceil(T0 / m) apart, and a5 runs only for m > max_num_segments + 1"""
+    return -(-T0 // (cfg.get("max_num_segments", 24) + 2))
+
+
+def resolve_gaps(cfg, T0, gaps):
+    """the `gaps` argument of the exports -> the number of table rows G (0: no table).  None: no table; "auto": auto_gaps;
+    an int >= 1: that many.  Clipped to T0 - 1, so one frame has no table."""
+    if gaps is None:
+        return 0
+    if isinstance(gaps, str) and gaps == "auto":
+        G = auto_gaps(cfg, T0)
+    elif isinstance(gaps, int) and not isinstance(gaps, bool) and gaps >= 1:
+        G = gaps
+    else:
+        raise ValueError("gaps is None (no table), \"auto\" or an int >= 1, got %r" % (gaps,))
+    return min(G, T0 - 1)
+
+
+def gap_sims(e, dino, T0, G, sims=None):
+    """fp32 [G, T0 - 1]: row g - 1, entry i = the a5 similarity of frames i and i + g of the DINOv2 tower rows `dino`
+    ([T0 * P, width], all T0 frames) for i + g < T0, every other entry 0.0.  engine.gap_sims_tensor where
+    the engine has it; otherwise per gap sims_tensor on the pairs' rows laid adjacent, every second value (as pair_sims), row 0
+    being sims - sims_tensor(dino, T0) - when the caller holds it."""
+    if hasattr(e, "gap_sims_tensor"):
+        return e.gap_sims_tensor(dino, T0, G)
+    fr = dino.reshape(T0, dino.shape[0] // T0, dino.shape[1])
+    out = torch.zeros(G, T0 - 1, dtype=torch.float32, device=dino.device)
+    for g in range(1, G + 1):
+        if g == 1:
+            row = sims if sims is not None else e.sims_tensor(dino, T0)
+        else:
+            n = T0 - g
+            row = e.sims_tensor(torch.stack([fr[:n], fr[g:]], 1).reshape(-1, dino.shape[1]), 2 * n)
+            row = torch.as_tensor(row, dtype=torch.float32)[0::2]
+        out[g - 1, :T0 - g] = torch.as_tensor(row, dtype=torch.float32).to(out.device)
+    return out
+
+
+def export_features_with(e, px_siglip, px_dino, image_size, store="f16", gaps=None):
+    """a3 / a4 of EVERY input frame (no a1: it reads the prompt length and the cap) -> features.FeatureSet.  The towers run as
+    in towers_and_selection: SigLIP on the side stream under `two_streams`, after the DINOv2 tower otherwise.
+    store="e4m3": the compact set (compact_rows) - the bytes compact_features_with makes of the lossless set.  gaps (compact
+    sets; resolve_gaps): the set also carries the similarities across that many frame gaps."""
+    from .features import FeatureSet, tower_signature
+    check_store(store, gaps)
     T0 = px_siglip.shape[0]
     if px_dino.shape[0] != T0 or T0 < 1:
         raise ValueError("export_features: %d SigLIP and %d DINOv2 frames" % (T0, px_dino.shape[0]))
@@ -652,35 +702,45 @@ def export_features_with(e, px_siglip, px_dino, image_size, store="f16"):
     dino = e.tower("dino", px_dino)                                                                 # a4
     sig = join_side_tower(e, side_sig, px_siglip)                                                   # a3
     if store == "e4m3":
-        return compact_rows(e, sig, dino, T0, image_size, tower_signature(e))
+        return compact_rows(e, sig, dino, T0, image_size, tower_signature(e), gaps)
     return FeatureSet(stored_rows(e, "siglip", sig, T0), stored_rows(e, "dino", dino, T0), image_size, tower_signature(e))
 
 
-def compact_rows(e, sig, dino, T0, image_size, signature):
+def compact_rows(e, sig, dino, T0, image_size, signature, gaps=None):
     """the tower rows of ALL T0 frames ([T0 * P, >= D] each, as `tower` returns them) -> the compact FeatureSet (DESIGN.md
     section 14): per tower the e4m3 bytes and one fp32 scale per token row (engine.quantize_feature_rows: scale = max|row| / 448,
     1 for a zero row), and the a5 similarities of these 16-bit DINOv2 rows - taken before they are dropped, by the launch the
-    lossless path takes them with, so a selection over all T0 frames is the lossless path's bit for bit."""
+    lossless path takes them with, so a selection over all T0 frames is the lossless path's bit for bit.  gaps (resolve_gaps):
+    the table of the same rows' similarities across gaps 1 .. G (gap_sims), which keeps that true under a1's sub-sampling."""
     from .features import FeatureSet
+    G = resolve_gaps(getattr(e, "cfg", {}), T0, gaps)
     sims = e.sims_tensor(dino, T0) if T0 > 1 else None
     if sims is not None and not torch.is_tensor(sims):
         sims = torch.tensor(sims, dtype=torch.float32)
+    if sims is not None:
+        sims = sims.float().reshape(T0 - 1)
+    table = gap_sims(e, dino, T0, G, sims) if G >= 1 else None
     parts = []
     for name, rows in (("siglip", sig), ("dino", dino)):
         D = e.tower_width(name) if hasattr(e, "tower_width") else rows.shape[1]
         b, sc = e.quantize_feature_rows(rows, D)
         parts += [b.reshape(T0, rows.shape[0] // T0, D), sc.reshape(T0, rows.shape[0] // T0)]
     return FeatureSet(parts[0], parts[2], image_size, signature, parts[1], parts[3],
-                      None if sims is None else sims.float().reshape(T0 - 1), sig.dtype)
+                      sims, sig.dtype, table)
 
 
-def compact_features_with(e, fs):
-    """a lossless FeatureSet -> its compact form, the bytes export_features_with(store="e4m3") gives for the same pixels"""
+def compact_features_with(e, fs, gaps=None):
+    """a lossless FeatureSet -> its compact form, the bytes export_features_with(store="e4m3", gaps=gaps) gives for the same
+    pixels.  A compact set comes back as it is; it cannot gain gaps (ValueError): its 16-bit rows are gone."""
     from .features import is_compact
     if is_compact(fs):
+        G = resolve_gaps(getattr(e, "cfg", {}), fs.frames, gaps)
+        if G > fs.gaps:
+            raise ValueError("compact_features: the set is compact already and holds the similarities of %d gap(s); %d are "
+                             "asked for, and only the 16-bit rows of a lossless set can give them" % (fs.gaps, G))
         return fs
     sig, dino = feature_rows(e, fs)
-    return compact_rows(e, sig, dino, fs.frames, fs.image_size, fs.signature)
+    return compact_rows(e, sig, dino, fs.frames, fs.image_size, fs.signature, gaps)
 
 
 def check_features(e, fs):
@@ -719,9 +779,11 @@ def video_front_from_features(e, fs, budget_text_len, audio=None, frame_cap=224,
                               check_signature=True):
     """video_front_with from the stored tower rows of a video (features.FeatureSet) instead of its pixels: a1, the kept
     frames' rows gathered, a5 by the pixel path's launch on the gathered DINOv2 rows, then front_after_towers -> the same dict,
-    the same bits.  The selection refinement needs pixels: under engine.selection_eps a non-empty band is ranked on the stored
+    the same bits.  A compact set: a5 ranks the stored similarities of the ORIGINAL rows wherever the set holds every gap between
+    neighbouring kept frames (features.stored_sims: every frame kept, or a gap table - section 16), else those of the decoded
+    rows; info["selection_sims"] says which.  The selection refinement needs pixels: under engine.selection_eps a non-empty band is ranked on the stored
     similarities and reported as info["refine_unavailable_pairs"] (select_segments_with, refine=None)."""
-    from .features import is_compact
+    from .features import is_compact, stored_sims
     if check_signature:
         check_features(e, fs)
     cfg = e.cfg
@@ -731,16 +793,15 @@ def video_front_from_features(e, fs, budget_text_len, audio=None, frame_cap=224,
     sig, dino = feature_rows(e, fs, idx)
     compact = is_compact(fs)
     if T > cfg.get("max_num_segments", 24) + 1:                                                     # a5
-        if compact and fs.sims is not None and T == T0:
-            # every frame kept: the similarities of the ORIGINAL 16-bit rows, stored with the set - no launch, and the
-            # lossless path's selection bit for bit
-            sims = fs.sims.tolist()
-        else:
+        # the similarities of the ORIGINAL 16-bit rows, stored with the set: every frame kept (gap 1), or sub-sampled within
+        # the set's gap table - no launch, and the lossless path's selection bit for bit
+        sims = stored = stored_sims(fs, idx) if compact else None
+        if sims is None:
             sims_dev = e.sims_tensor(dino, T)
             ev = e.mark() if hasattr(e, "mark") and sims_dev.is_cuda else None
             sims = e.fetch(sims_dev, ev) if ev is not None else sims_dev.tolist()
         if compact and info is not None:
-            info["selection_sims"] = "stored" if fs.sims is not None and T == T0 else "decoded"
+            info["selection_sims"] = "stored" if stored is not None else "decoded"
         seg_idx = select_segments_with(e, sims, None, info)
     else:
         seg_idx = list(range(T))
@@ -781,7 +842,8 @@ def encode_features_prompts_with(e, fs, prompts, audio=None, frame_cap=224, vide
 def same_features_key(e, fs, budget_text_len, frame_cap, audio=None, video_index=None):
     """`config.tdc_batch_prompts` over feature inputs: what two samples must share to be questions about the SAME stored
     video - the content of both feature tensors (content_key), image_size, the a1 selection, and their audio as
-    same_video_key compares it; a compact set: its scales too"""
+    same_video_key compares it; a compact set: its scales too, and its gap table (a set with one selects on other similarities
+    than a set without)"""
     from .features import is_compact
     idx = frame_indices(e.cfg, fs.frames, budget_text_len, frame_cap)
     akey = None
@@ -790,6 +852,8 @@ def same_features_key(e, fs, budget_text_len, frame_cap, audio=None, video_index
     key = (content_key(e, fs.siglip), content_key(e, fs.dino), tuple(fs.image_size), tuple(idx), akey)
     if is_compact(fs):                      # the same bytes under other scales are other rows
         key += (content_key(e, fs.siglip_scale), content_key(e, fs.dino_scale), str(fs.rows_dtype))
+        if getattr(fs, "gap_sims", None) is not None:
+            key += (content_key(e, fs.gap_sims),)
     return key
 
 
@@ -863,13 +927,12 @@ def encode_frames_prompts_with(e, frames, prompts, audio=None, frame_cap=224, vi
     return prompts_over_fronts(e, T0, prompts, front, frame_cap, infos, max_prompts, pad_fraction)
 
 
-def export_features_from_frames_with(e, frames, store="f16", image_size=None, slab=None):
+def export_features_from_frames_with(e, frames, store="f16", image_size=None, slab=None, gaps=None):
     """export_features_with from decoded frames: EVERY frame (no a1), preprocessed and run through both towers `slab` frames
     at a time (default EXPORT_FRAMES_SLAB), the rows concatenated.  Tower rows do not depend on the tower batch, so the set equals
     export_features_with(*process_images(frames)) bit for bit - without the pixels of all T0 frames ever existing."""
     from .features import FeatureSet, tower_signature
-    if store not in ("f16", "e4m3"):
-        raise ValueError("export_features: store is \"f16\" (lossless) or \"e4m3\" (compact), got %r" % (store,))
+    check_store(store, gaps)
     T0, image_size = frames_size(frames, image_size)
     slab = EXPORT_FRAMES_SLAB if slab is None else int(slab)
     if slab < 1:
@@ -883,5 +946,5 @@ def export_features_from_frames_with(e, frames, store="f16", image_size=None, sl
     sig = sigs[0] if len(sigs) == 1 else torch.cat(sigs, 0)
     dino = dinos[0] if len(dinos) == 1 else torch.cat(dinos, 0)
     if store == "e4m3":
-        return compact_rows(e, sig, dino, T0, image_size, tower_signature(e))
+        return compact_rows(e, sig, dino, T0, image_size, tower_signature(e), gaps)
     return FeatureSet(stored_rows(e, "siglip", sig, T0), stored_rows(e, "dino", dino, T0), image_size, tower_signature(e))

@@ -412,17 +412,29 @@ def frame_cossim(f, T, n):
     return sims
 
 
-def pair_cossim(slab, pairs, n):
+PAIR_COSSIM_MAX = 65535         # pairs per tdc_pair_cossim call (its grid's y extent)
+
+
+def pair_cossim_scratch(n_pairs, device):
+    """the scratch of pair_cossim calls of up to n_pairs pairs, for a caller that makes several (scratch=)"""
+    return torch.empty(L.load().tdc_pair_cossim_scratch_floats(n_pairs), device=device, dtype=torch.float32)
+
+
+def pair_cossim(slab, pairs, n, scratch=None):
     """slab: 16-bit [slots, ...] per-frame features, n elements per frame; pairs: host list of (slot_a, slot_b) -> fp32 [len(pairs)]
-    cos-sim values, bit for bit what frame_cossim gives for the same two frames adjacent in one buffer."""
+    cos-sim values, bit for bit what frame_cossim gives for the same two frames adjacent in one buffer.  scratch: a
+    pair_cossim_scratch of at least len(pairs) pairs, reused across calls on one stream (None: allocated here)."""
     assert slab.is_cuda and slab.is_contiguous() and slab.dim() >= 2 and n % 8 == 0
     stride = slab[0].numel()
-    assert stride >= n and stride % 8 == 0 and 0 < len(pairs) <= 65535
+    assert stride >= n and stride % 8 == 0 and 0 < len(pairs) <= PAIR_COSSIM_MAX
     flat = [int(v) for ab in pairs for v in ab]
     assert min(flat) >= 0 and max(flat) < slab.shape[0], "pair slot out of range"        # the kernel trusts its slots
     lib = L.load()
     p = torch.tensor(flat, dtype=torch.int32).to(slab.device, non_blocking=True)
-    scratch = torch.empty(lib.tdc_pair_cossim_scratch_floats(len(pairs)), device=slab.device, dtype=torch.float32)
+    if scratch is None:
+        scratch = torch.empty(lib.tdc_pair_cossim_scratch_floats(len(pairs)), device=slab.device, dtype=torch.float32)
+    assert scratch.is_cuda and scratch.dtype == torch.float32 and scratch.is_contiguous() \
+        and scratch.numel() >= lib.tdc_pair_cossim_scratch_floats(len(pairs)), "pair_cossim scratch too small"
     sims = torch.empty(len(pairs), device=slab.device, dtype=torch.float32)
     L.check(lib.tdc_pair_cossim(_ptr(slab), stride, n, _ptr(p), len(pairs), _ptr(sims), _ptr(scratch), _dt(slab), _stream()),
             "tdc_pair_cossim")

@@ -425,6 +425,28 @@ class VideoEncoder:
         ev = self.mark()
         return (lambda: self.fetch(sims, ev)) if defer else self.fetch(sims, ev)
 
+    def gap_sims_tensor(self, dino_feat, T0, G):
+        """the similarity table of a compact feature set: dino_feat [T0 * P, Dp], the DINOv2 rows of ALL
+        T0 frames -> fp32 device tensor [G, T0 - 1], row g - 1, entry i = cos(f_i, f_{i+g}) for i + g < T0, every other entry
+        0.0.  tdc_pair_cossim on the rows viewed as [T0, P, Dp] slots, at most 65535 pairs a call through one scratch: each
+        value is bit for bit what sims_tensor gives for the two frames laid adjacent (what the lossless path computes behind
+        its a1 gather), and row 0 is sims_tensor(dino_feat, T0).  Once per video, on export."""
+        if not 1 <= G <= T0 - 1:
+            raise ValueError("gap_sims_tensor: %d gaps of %d frames (1 .. frames - 1)" % (G, T0))
+        if dino_feat.shape[0] % T0:
+            raise ValueError("gap_sims_tensor: %d rows are not %d frames" % (dino_feat.shape[0], T0))
+        slab = dino_feat.contiguous().view(T0, dino_feat.shape[0] // T0, dino_feat.shape[1])
+        n = slab[0].numel()
+        pairs = [(i, i + g) for g in range(1, G + 1) for i in range(T0 - g)]
+        at = [(g - 1) * (T0 - 1) + i for g in range(1, G + 1) for i in range(T0 - g)]
+        out = torch.zeros(G * (T0 - 1), device=self.dev, dtype=torch.float32)
+        per = ops.PAIR_COSSIM_MAX
+        scratch = ops.pair_cossim_scratch(min(per, len(pairs)), self.dev)
+        for lo in range(0, len(pairs), per):
+            vals = ops.pair_cossim(slab, pairs[lo:lo + per], n, scratch=scratch)
+            out[torch.tensor(at[lo:lo + per], device=self.dev)] = vals
+        return out.view(G, T0 - 1)
+
     def fingerprint(self, px, rows, row_bytes=None, row_stride=None):
         """frame cache keys: the 128-bit content fingerprints of the frames px[rows] (read in place; row_bytes / row_stride:
         other rows of px's bytes, ops.fingerprint_rows) -> host list of (u64, u64)"""
@@ -1066,7 +1088,7 @@ class VideoEncoder:
         infos: one info dict per sample (encode_batch_with).  All samples share the pixel geometry and type."""
         return encode_batch_with(self, samples, frame_cap, infos)
 
-    def export_features(self, px_siglip, px_dino, image_size, store="f16"):
+    def export_features(self, px_siglip, px_dino, image_size, store="f16", gaps=None):
         """The frozen towers once per video: ALL frames of px_siglip / px_dino ([T0, 3, H, W]; one frame is an image) through
         both towers -> features.FeatureSet (the rows `tower` returns without their padding columns, image_size, the towers'
         signature) for encode_features / encode_features_prompts, .save(path) and FeatureSet.load.  No a1 sub-sampling: it
@@ -1077,12 +1099,17 @@ class VideoEncoder:
         store="e4m3": the compact set - one e4m3 byte per value and one fp32 scale per token row, half
         the bytes wherever the set lives or moves, decoded in the row gather of encode_features; it carries the exact a5
         similarities of the 16-bit rows, so a call that keeps every frame selects the lossless path's key frames bit for bit.
-        The connector and Q-Former operands are lossy (measured contract: section 14)."""
-        return export_features_with(self, px_siglip.to(self.dev), px_dino.to(self.dev), image_size, store)
+        The connector and Q-Former operands are lossy (measured contract: section 14).
+        gaps (compact sets only; default None: no table, the set as it always was): "auto" or an int >= 1 - the set also carries
+        the similarities of the 16-bit rows across that many frame gaps (section 16), so a call whose a1 SUB-SAMPLES selects
+        the lossless path's key frames bit for bit as well, without an a5 launch.  "auto" covers every prompt length and frame
+        cap: ceil(T0 / (max_num_segments + 2)) gaps, 4 * G * (T0 - 1) bytes."""
+        return export_features_with(self, px_siglip.to(self.dev), px_dino.to(self.dev), image_size, store, gaps)
 
-    def compact_features(self, fs):
-        """a lossless FeatureSet -> the compact one, on the device: the bytes export_features(store="e4m3") gives"""
-        return compact_features_with(self, fs)
+    def compact_features(self, fs, gaps=None):
+        """a lossless FeatureSet -> the compact one, on the device: the bytes export_features(store="e4m3", gaps=gaps) gives.
+        A set that is compact already comes back as it is; asked for more gaps than it holds, ValueError."""
+        return compact_features_with(self, fs, gaps)
 
     def encode_features(self, fs, budget_text_len, n_text_tokens, prompt_ids, audio=None, frame_cap=224, splice=None,
                         video_index=None, info=None, check_signature=True, image=False):
@@ -1128,8 +1155,8 @@ class VideoEncoder:
         return encode_frames_prompts_with(self, frames, prompts, audio, frame_cap, video_index, infos, cache, max_prompts,
                                           pad_fraction, image_size)
 
-    def export_features_from_frames(self, frames, store="f16", image_size=None, slab=None):
+    def export_features_from_frames(self, frames, store="f16", image_size=None, slab=None, gaps=None):
         """export_features from decoded frames: every frame, preprocessed and run through the towers `slab` frames at a time
         (default encode.EXPORT_FRAMES_SLAB; the rows do not depend on it) - the set export_features gives for
         preprocess.process_images of the frames, bit for bit, without the pixels of all frames ever being resident"""
-        return export_features_from_frames_with(self, frames, store, image_size, slab)
+        return export_features_from_frames_with(self, frames, store, image_size, slab, gaps)
