@@ -416,6 +416,19 @@ typedef struct {
      * (needs cross_out_tiled); 2 = the whole block in one kernel per layer (needs cross_k / cross_v / both tiled weights) */
     int xattn_mode;
     const tdc_qformer_prompts* prompts;                     /* NULL: one prompt (the form described above) */
+    /* kept cross-attention K/V.  kv_keep == NULL (and kv_state 0): the stacked K/V projection writes
+     * the workspace's K/V region, as described above.  kv_keep != NULL: a caller-owned, 256-byte aligned buffer
+     * [U*Nenc, cross_kv.n] of 16-bit values, row stride cross_kv.n (U = prompts->enc_frames in the multi-prompt form, else F),
+     * takes that region's place: the stacked GEMM's C and every cross layer's K / V operands point into it.  The workspace
+     * layout and tdc_qformer_workspace_bytes do not change.  kv_state 0 (fill): the composite runs the stacked GEMM into
+     * kv_keep - the same launch on the same operands with another C pointer, so the rows are the workspace form's bit for bit.
+     * kv_state 1 (ready): kv_keep holds the rows of an earlier fill over the same enc rows and weights; the GEMM is skipped
+     * and `enc` may be NULL.  Any other kv_state, a misaligned kv_keep, or kv_state != 0 without kv_keep: TDC_E_BADARG.
+     * A model and shape that resolve to xattn_mode 2 return TDC_E_BADARG with kv_keep (the whole-block kernel keeps K and
+     * transposed V in two buffers of other shapes); xattn_mode 0 / 1 are served.
+     * writes (fill): kv_keep[r, 0 .. cross_kv.n) for r < U*Nenc, nothing else of it.  ready: no byte of kv_keep is written,
+     * those rows are read, and no byte of enc is read. */
+    void* kv_keep; int kv_state;
 } tdc_qformer_model;
 size_t tdc_qformer_workspace_bytes(const tdc_qformer_model* m, int F, int K, int Lt, int Nenc);
 

@@ -14,6 +14,12 @@ collision-free for honest inputs, not against crafted collisions.  The frame row
 ([slots, N, Hp] and [slots, P, Dp]) that grow up to the byte budget; frames are evicted least recently used first, never one
 the running call needs, and the stored bytes never exceed the budget.  BEATs window features take at most 1/16 of the budget
 (AUDIO_SHARE), the frames the rest.
+
+Kept cross-attention K/V (kv_bytes > 0): the Q-Former's stacked K/V projection of a call's compressed
+frames reads their connector rows alone, so it is a property of the (video, a1 selection), not of the prompt.  One entry per
+such selection - a device buffer [U * Nf, n_cross * 2 * dim] under a key made of the frames' content keys (encode.kv_key) -
+lives in a budget of its own (kv_bytes), least recently used entries leaving first.  Its counters are kv_stats(); stats(),
+bytes and the frame budget do not know about it.
 """
 from collections import OrderedDict
 
@@ -68,15 +74,27 @@ def engine_signature(e):
             bool(getattr(e, "native_connector", True)), getattr(e, "selection_eps", None))
 
 
+class KeptKV:
+    """compress_frames' kv= value: the kept K/V buffer of a call's compressed frames and whether an earlier pass filled it"""
+    __slots__ = ("buf", "ready")
+
+    def __init__(self, buf, ready):
+        self.buf, self.ready = buf, bool(ready)
+
+
 class FrameCache:
     """Connector rows, DINOv2 rows and similarities of frames already encoded, keyed by content (module docstring).
-    max_bytes: budget of the stored rows (slab slots actually allocated never exceed it either)."""
+    max_bytes: budget of the stored rows (slab slots actually allocated never exceed it either).  kv_bytes: budget of the
+    kept cross-attention K/V entries, 0 = none are kept."""
     AUDIO_SHARE = 16                             # BEATs windows: at most max_bytes // AUDIO_SHARE
 
-    def __init__(self, max_bytes, signature=None):
+    def __init__(self, max_bytes, signature=None, kv_bytes=0):
         self.max_bytes = int(max_bytes)
         if self.max_bytes <= 0:
             raise ValueError("FrameCache needs a positive byte budget, got %r" % (max_bytes,))
+        self.kv_max_bytes = int(kv_bytes)
+        if self.kv_max_bytes < 0:
+            raise ValueError("FrameCache needs a K/V byte budget >= 0, got %r" % (kv_bytes,))
         self.signature = signature
         self._pairs = OrderedDict()              # (dkey a, dkey b) / ("precise", ...) -> float
         self.clear()
@@ -90,6 +108,9 @@ class FrameCache:
         self._audio_bytes = 0
         self._counts = dict(hits=0, misses=0, frames_encoded=0, pairs_computed=0, evictions=0, windows_encoded=0,
                             windows_hit=0)
+        self._kv = OrderedDict()                 # encode.kv_key -> (buffer, bytes), least recently used first
+        self._kv_bytes = 0
+        self._kv_counts = dict(hits=0, misses=0, fills=0, evictions=0, bypassed=0)
 
     def _clear_rows(self):
         self._slots = OrderedDict()              # key -> slot, least recently used first
@@ -320,6 +341,50 @@ class FrameCache:
                 self.pair_put(pk[j], v)
             self._counts["pairs_computed"] += len(todo)
         return vals
+
+    # ------------------------------------------------------------------------------------------------ kept K/V
+    @property
+    def kv_enabled(self):
+        return self.kv_max_bytes > 0
+
+    def kv_stats(self):
+        return dict(self._kv_counts, entries=len(self._kv), bytes=self._kv_bytes, max_bytes=self.kv_max_bytes)
+
+    def kv_clear(self):
+        """drop the kept K/V entries (and release their device memory); the frames and every counter stay"""
+        self._kv.clear()
+        self._kv_bytes = 0
+
+    def kv_get(self, key):
+        """the buffer kept under `key` (it becomes the most recent entry), or None"""
+        hit = self._kv.get(key)
+        if hit is None:
+            self._kv_counts["misses"] += 1
+            return None
+        self._kv.move_to_end(key)
+        self._kv_counts["hits"] += 1
+        return hit[0]
+
+    def kv_room(self, nbytes, pinned=()):
+        """make room for a new entry of nbytes BEFORE the caller allocates it: least recently used entries leave until it
+        fits, never one of `pinned` (the keys the running call has used).  -> False (nothing evicted) when the entry exceeds
+        the budget, or what the pinned entries leave of it."""
+        held = sum(nb for k, (_, nb) in self._kv.items() if k in pinned)
+        if nbytes + held > self.kv_max_bytes:
+            self._kv_counts["bypassed"] += 1
+            return False
+        while self._kv_bytes + nbytes > self.kv_max_bytes:
+            victim = next(k for k in self._kv if k not in pinned)
+            self._kv_bytes -= self._kv.pop(victim)[1]
+            self._kv_counts["evictions"] += 1
+        return True
+
+    def kv_put(self, key, buf, nbytes):
+        """keep the filled buffer under `key` (kv_room(nbytes) said it fits)"""
+        assert key not in self._kv and self._kv_bytes + nbytes <= self.kv_max_bytes
+        self._kv[key] = (buf, nbytes)
+        self._kv_bytes += nbytes
+        self._kv_counts["fills"] += 1
 
     # ------------------------------------------------------------------------------------------------ BEATs windows
     def windows(self, keys, encode):

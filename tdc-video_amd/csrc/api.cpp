@@ -174,7 +174,12 @@ extern "C" size_t tdc_qformer_workspace_bytes(const tdc_qformer_model* m, int F,
 extern "C" int tdc_qformer_fwd(const tdc_qformer_model* m, const void* enc, int ldenc, int F, int Nenc,
                                const void* query, int ldq, const int* qsrc, const int* ids, int Lt, int K, void* out,
                                int ldo, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!m || !enc || !query || !qsrc || !out || !workspace || F <= 0 || K <= 0 || Lt < 0) return TDC_E_BADARG;
+    if (!m || !query || !qsrc || !out || !workspace || F <= 0 || K <= 0 || Lt < 0) return TDC_E_BADARG;
+    // kept K/V (tdc_qformer_model.kv_keep): a caller-owned buffer takes the place of the workspace's K/V region; once it is
+    // ready (kv_state 1) the stacked projection is skipped and enc is not read
+    if (m->kv_keep ? (m->kv_state != 0 && m->kv_state != 1) || ((uintptr_t)m->kv_keep & 255) : m->kv_state != 0) return TDC_E_BADARG;
+    const bool kv_ready = m->kv_keep && m->kv_state == 1;
+    if (!enc && !kv_ready) return TDC_E_BADARG;
     // multi-prompt form (tdc_qformer_prompts): F virtual frames over U distinct ones
     const tdc_qformer_prompts* mp = m->prompts;
     if (mp && (mp->n_prompts <= 0 || mp->enc_frames <= 0 || !mp->kv_src || !mp->frame_prompt || !mp->prompt_len || !mp->self_len))
@@ -187,7 +192,7 @@ extern "C" int tdc_qformer_fwd(const tdc_qformer_model* m, const void* enc, int 
     const int hd = D / m->heads;
     float* h32 = (float*)(ws + w.h32);
     void* h16 = ws + w.h16;
-    char* kv = ws + w.kv;
+    char* kv = m->kv_keep ? (char*)m->kv_keep : ws + w.kv;
     char* qkv = ws + w.qkv;
     void* ctx = ws + w.ctx;
     void* ctxq = ws + w.ctxq;
@@ -219,6 +224,10 @@ extern "C" int tdc_qformer_fwd(const tdc_qformer_model* m, const void* enc, int 
         fprintf(stderr, "[tdc_hip] tdc_qformer_fwd: the multi-prompt form runs xattn_mode 0 / 1 only\n");
         return TDC_E_BADARG;
     }
+    if (m->kv_keep && fused) {
+        fprintf(stderr, "[tdc_hip] tdc_qformer_fwd: kept K/V (kv_keep) runs xattn_mode 0 / 1 only\n");
+        return TDC_E_BADARG;
+    }
     {
     TdcProfTagGuard tag_kv(TDC_PROF_TAG_XATTN_BLOCK);   // the cross-attention block's launches, for tdc_profile_*
     if (fused) {
@@ -227,7 +236,7 @@ extern "C" int tdc_qformer_fwd(const tdc_qformer_model* m, const void* enc, int 
         RET_IF(Gemm(enc, ldenc, m->cross_k, kv, m->cross_k.n, F * Nenc, dt).run(stream));
         const tdc_lin enc_t = {enc, nullptr, F * Nenc, m->cross_v.k};
         RET_IF(Gemm(m->cross_v.w, m->cross_v.k, enc_t, ws + w.vt, (int)w.ldvt, m->cross_v.n, dt).ldw(ldenc).c_pad8().run(stream));
-    } else {
+    } else if (!kv_ready) {
         RET_IF(Gemm(enc, ldenc, m->cross_kv, kv, m->cross_kv.n, U * Nenc, dt).run(stream));
     }
     }

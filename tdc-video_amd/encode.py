@@ -4,6 +4,8 @@ function here, called by the serial path, the batched, cached and multi-prompt o
 The engine is pipeline.VideoEncoder on GPUs; the CPU tests plug in doubles.  The engine protocol:
   required   cfg, K, H, dtype; tower(name, px), sims_tensor(dino, T), connector(sig, dino, T, sizes, keep), local_audio,
              with_audio, make_queries, learned_queries, query_width, compress_frames, emit
+  kept K/V   probed: kv_cache_ok(Nf), kv_entry_bytes(U, Nf), kv_alloc(U, Nf) and compress_frames(..., kv=) (DESIGN.md
+             section 17) - an engine without kv_cache_ok reports "unsupported" and runs the plain path
   refinement selection_eps, selection_max_fraction, precise_dino(px), pair_sims(feats, pairs)
   frame cache fingerprint(px, rows), slot_sims(slab, pairs, defer), compact_rows(src, idx, cols), beats / beats_windows /
              audio_tokens (raw-waveform audio)
@@ -39,21 +41,81 @@ def text_prompt(cfg, prompt_ids):
     return prompt_ids if cfg.get("text_input", True) else None
 
 
-def compress_with(e, X, T, N, seg_indices, prompt_ids, max_visual_len, audio=None, keep=None, splice=None, info=None):
+def compress_with(e, X, T, N, seg_indices, prompt_ids, max_visual_len, audio=None, keep=None, splice=None, info=None,
+                  kvs=None):
     Xf, Nf = e.with_audio(X, T, N, audio)
     plan, learned = emission_plan(e, T, Nf, seg_indices, max_visual_len)
-    return compress_planned(e, Xf, N, Nf, plan, learned, prompt_ids, keep, splice, info)
+    return compress_planned(e, Xf, N, Nf, plan, learned, prompt_ids, keep, splice, info, kvs)
 
 
-def compress_planned(e, Xf, N, Nf, plan, learned, prompt_ids, keep=None, splice=None, info=None):
-    """compress_with after its planning: one prompt's Q-Former pass and emission over the rows Xf (with_audio) by `plan`"""
+# ---- kept cross-attention K/V: one entry per (video, a1 selection) in the frame cache ----------------
+def kv_store(cache, keys, image_size, audio_key=None):
+    """the K/V store of one front over the frames keyed `keys` (FrameCache.frame_keys, one per kept frame): what
+    compress_planned / compress_many_with take as kvs=.  audio_key: same_video_key's audio material, None without audio."""
+    return dict(cache=cache, keys=list(keys), image_size=tuple(image_size), audio=audio_key, used=set())
+
+
+def kv_key(kvs, frames, Nf):
+    """everything that changes a bit of the K/V of the compressed frames `frames`: their content keys in order, the rows per
+    frame, image_size, and with audio (whose rows with_audio puts into Xf) its content and sampled seconds"""
+    return (tuple(kvs["keys"][f] for f in frames), int(Nf), kvs["image_size"], kvs["audio"])
+
+
+def kv_begin(e, kvs, frames, Nf, info=None):
+    """look the entry of `frames` up -> (kv for compress_frames - None: the plain path -, commit() to call after the pass).
+    hit: a ready buffer; miss: room is made, a buffer allocated, and commit() stores it once the pass has filled it; an entry
+    above the budget, or an engine that cannot take kv= here, runs the plain path.  info["kv"] receives the record that
+    info["cache"]["kv"] reports (cache_info_of)."""
+    from .cache import KeptKV
+    cache, U = kvs["cache"], len(frames)
+    ok = getattr(e, "kv_cache_ok", None)
+    rec = dict(state="unsupported", frames=U, bytes=0)
+    kv, commit = None, (lambda: None)
+    if ok is not None and ok(Nf):
+        nbytes = rec["bytes"] = e.kv_entry_bytes(U, Nf)
+        key = kv_key(kvs, frames, Nf)
+        buf = cache.kv_get(key)
+        if buf is not None:
+            rec["state"], kv = "hit", KeptKV(buf, True)
+            kvs["used"].add(key)
+        elif not cache.kv_room(nbytes, kvs["used"]):
+            rec["state"] = "bypassed"
+        else:
+            rec["state"], kv = "filled", KeptKV(e.kv_alloc(U, Nf), False)
+
+            def commit():
+                cache.kv_put(key, kv.buf, nbytes)
+                kvs["used"].add(key)
+    if info is not None:
+        info["kv"] = rec
+    return kv, commit
+
+
+def cache_info_of(f, info):
+    """info["cache"] of a call over the front f, read after the compressor ran; with a K/V budget it carries "kv": the
+    record kv_begin left in info (a call without compressed frames: bypassed, no frames)"""
+    ci = f["cache_info"]()
+    rec = info.pop("kv", None)
+    if f.get("kv") is not None:
+        ci["kv"] = rec or dict(state="bypassed", frames=0, bytes=0)
+    return ci
+
+
+def compress_planned(e, Xf, N, Nf, plan, learned, prompt_ids, keep=None, splice=None, info=None, kvs=None):
+    """compress_with after its planning: one prompt's Q-Former pass and emission over the rows Xf (with_audio) by `plan`.
+    kvs (kv_store): the pass takes the cross-attention K/V of its compressed frames from the store, or fills its entry."""
     comp = None
     if plan["comp_frames"]:
         if learned:
             qtable, qsrc = e.learned_queries(), [0] * len(plan["comp_frames"])
         else:
             qtable, qsrc = e.make_queries(Xf, N, Nf, plan["key_frames"]), plan["comp_chunk"]
-        comp = e.compress_frames(Xf, Nf, plan["comp_frames"], qtable, qsrc, prompt_ids, keep)
+        kv, commit = kv_begin(e, kvs, plan["comp_frames"], Nf, info) if kvs is not None and keep is None else (None, None)
+        if kv is None:
+            comp = e.compress_frames(Xf, Nf, plan["comp_frames"], qtable, qsrc, prompt_ids, keep)
+        else:
+            comp = e.compress_frames(Xf, Nf, plan["comp_frames"], qtable, qsrc, prompt_ids, keep, kv=kv)
+            commit()
     pairs = seg.emit_pairs(plan, Nf, e.K)
     if keep is not None:
         keep["plan"] = plan
@@ -115,12 +177,14 @@ def prompt_maps(plans, learned=False):
                 offsets=offsets)
 
 
-def compress_many_with(e, X, T, N, seg_indices, prompts, audio=None, infos=None, max_prompts=8, pad_fraction=0.25):
+def compress_many_with(e, X, T, N, seg_indices, prompts, audio=None, infos=None, max_prompts=8, pad_fraction=0.25,
+                       kvs=None):
     """a11-a19 for several prompts over ONE video's connector rows X (audio: the a20 tokens, as compress_with takes them):
     prompts = dicts of n_text_tokens, prompt_ids, optional splice -> one emitted tensor per prompt, bit for bit compress_with's.
     Per group (prompt_groups) the distinct compressed frames are gathered and projected to K/V once, the distinct key frames
     pooled once, and ONE Q-Former pass runs over the prompts' virtual frames (prompt_maps); a group of one, and every group on
-    an engine whose compress_frames cannot take the form (multi_prompt_ok), runs compress_with."""
+    an engine whose compress_frames cannot take the form (multi_prompt_ok), runs compress_with.  kvs (kv_store): a group's
+    pass takes the K/V of its distinct frames from the store or fills their entry; every member's info reports that record."""
     cfg = getattr(e, "cfg", {})
     K = e.K
     P = len(prompts)
@@ -139,13 +203,20 @@ def compress_many_with(e, X, T, N, seg_indices, prompts, audio=None, infos=None,
         maps = prompt_maps(gplans, learned) if multi else None
         if multi:
             qtable = e.learned_queries() if learned else e.make_queries(Xf, N, Nf, maps["key_frames"])
-            comp = e.compress_frames(Xf, Nf, maps["enc_frames"], qtable, maps["qsrc"], [pids[p] or [] for p in g], None,
-                                     dict(kv_src=maps["kv_src"], frame_prompt=maps["frame_prompt"]))
+            mm = dict(kv_src=maps["kv_src"], frame_prompt=maps["frame_prompt"])
+            grec = {}
+            kv, commit = kv_begin(e, kvs, maps["enc_frames"], Nf, grec) if kvs is not None else (None, None)
+            if kv is None:
+                comp = e.compress_frames(Xf, Nf, maps["enc_frames"], qtable, maps["qsrc"], [pids[p] or [] for p in g], None, mm)
+            else:
+                comp = e.compress_frames(Xf, Nf, maps["enc_frames"], qtable, maps["qsrc"], [pids[p] or [] for p in g], None, mm,
+                                         kv=kv)
+                commit()
         for j, p in enumerate(g):
             info = infos[p] if infos is not None else None
             splice = prompts[p].get("splice")
             if not multi:                                         # today's path, on the plan made above
-                out[p] = compress_planned(e, Xf, N, Nf, plans[p], learned, pids[p], None, splice, info)
+                out[p] = compress_planned(e, Xf, N, Nf, plans[p], learned, pids[p], None, splice, info, kvs)
                 if info is not None:
                     info["prompts"] = dict(group=gi, group_size=1, pad_rows=0, shared_kv_frames=len(plans[p]["comp_frames"]))
                 continue
@@ -154,6 +225,8 @@ def compress_many_with(e, X, T, N, seg_indices, prompts, audio=None, infos=None,
             out[p] = e.emit(Xf, comp[lo * K:hi * K], pairs, splice) if splice is not None else \
                 e.emit(Xf, comp[lo * K:hi * K], pairs)
             if info is not None:
+                if "kv" in grec:
+                    info["kv"] = dict(grec["kv"])
                 info["n_visual"] = len(pairs)
                 info["prompts"] = dict(group=gi, group_size=len(g), pad_rows=(Lmax - lens[p]) * len(plans[p]["comp_frames"]),
                                        shared_kv_frames=len(maps["enc_frames"]))
@@ -192,7 +265,7 @@ def prompts_over_fronts(e, T0, prompts, front, frame_cap=224, infos=None, max_pr
         f = front(btl, finfo)
         sub = [infos[p] for p in members] if infos is not None else None
         res = compress_many_with(e, f["X"], f["T"], f["N"], f["seg_idx"], [prompts[p] for p in members], f["audio"], sub,
-                                 max_prompts, pad_fraction)
+                                 max_prompts, pad_fraction, f.get("kv"))
         for p, r in zip(members, res):
             out[p] = r
             if infos is not None:
@@ -201,7 +274,7 @@ def prompts_over_fronts(e, T0, prompts, front, frame_cap=224, infos=None, max_pr
                 info.update(frame_indices=f["idx"], selected=list(range(f["T"])), seg_indices=f["seg_idx"],
                             final_size=f["final_size"])
                 if "cache_info" in f:
-                    info["cache"] = f["cache_info"]()
+                    info["cache"] = cache_info_of(f, info)
                 info["prompts"]["group"] += base
         if infos is not None and members:
             base = max(infos[p]["prompts"]["group"] for p in members) + 1
@@ -394,14 +467,15 @@ def encode_front(e, f, n_text_tokens, prompt_ids, keep=None, splice=None, info=N
     X, T, N, seg_idx, idx, final_size = f["X"], f["T"], f["N"], f["seg_idx"], f["idx"], f["final_size"]
     max_visual_len = visual_budget(cfg, n_text_tokens)
     pid = text_prompt(cfg, prompt_ids)
-    vis = compress_with(e, X, T, N, seg_idx, pid, max_visual_len, f["audio"], keep, splice, info)   # a11-a19 (+a21)
+    vis = compress_with(e, X, T, N, seg_idx, pid, max_visual_len, f["audio"], keep, splice, info,   # a11-a19 (+a21)
+                        f.get("kv"))
     if keep is not None:                    # selected: what a5's second frame cap keeps - every frame (frame_indices)
         keep.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, siglip_feat=f["sig"], dino_feat=f["dino"],
                     final_size=final_size, X=X)
     if info is not None:
         info.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, final_size=final_size)
         if "cache_info" in f:               # read after the compressor ran
-            info["cache"] = f["cache_info"]()
+            info["cache"] = cache_info_of(f, info)
     return vis
 
 
@@ -606,6 +680,8 @@ def front_cached_selected(e, cache, px_siglip, px_dino, rows, idx, T0, image_siz
     if new is None:
         if info is not None:
             info["cache"] = dict(bypassed=True, frames=T, frames_hit=0, frames_encoded=T, pairs_computed=0)
+            if cache.kv_enabled:            # no frame keys to name an entry by: the compressor runs as without a store
+                info["cache"]["kv"] = dict(state="bypassed", frames=0, bytes=0)
         return None
     if not segmented:                                                                               # a5
         seg_idx = list(range(T))
@@ -620,10 +696,19 @@ def front_cached_selected(e, cache, px_siglip, px_dino, rows, idx, T0, image_siz
     X = cache.assemble(e, keys)
     N = cache.rows_per_frame
     final_size = cache.final_sizes(keys)
+    kvs = None
+    if cache.kv_enabled:                    # the kept K/V of this selection: named by the frames' keys and, with audio, by
+        akey = None                         # what same_video_key compares of it
+        if audio is not None:
+            akey = (content_key(e, audio), tuple(sample_indicator(T0, idx, video_index)))
+        kvs = kv_store(cache, keys, image_size, akey)
     if audio is not None:                                                                           # a20
         audio = cached_audio(e, cache, audio, sample_indicator(T0, idx, video_index), T)
-    return dict(X=X, T=T, N=N, seg_idx=seg_idx, audio=audio, idx=idx, final_size=final_size,
-                cache_info=lambda: cache.call_info(before, cache.stats(), keys, new))
+    f = dict(X=X, T=T, N=N, seg_idx=seg_idx, audio=audio, idx=idx, final_size=final_size,
+             cache_info=lambda: cache.call_info(before, cache.stats(), keys, new))
+    if kvs is not None:
+        f["kv"] = kvs
+    return f
 
 
 def encode_video_cached(e, cache, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio=None,

@@ -129,7 +129,7 @@ class QformerModel(C.Structure):
                 ("emb_ln_g", C.c_void_p), ("emb_ln_b", C.c_void_p), ("cross_kv", Lin), ("vision_proj", Lin),
                 ("layers_host", C.POINTER(QformerLayer)),
                 ("cross_k", Lin), ("cross_v", Lin), ("cross_bv", C.c_void_p), ("xattn_mode", C.c_int),
-                ("prompts", C.POINTER(QformerPrompts))]
+                ("prompts", C.POINTER(QformerPrompts)), ("kv_keep", C.c_void_p), ("kv_state", C.c_int)]
 
 
 class XattnDesc(C.Structure):

@@ -374,7 +374,7 @@ class CambrianMetaModel:
         the cap of both frame sub-samplings; `config.tdc_shard_frames`: see prepare_inputs_labels_for_multimodal;
         `config.tdc_video_cache_bytes`: see tdc_video_cache; `config.tdc_shard_cache_bytes`: see tdc_shard_cache;
         `config.tdc_batch_frames`: see tdc_batch_frames; `config.tdc_feature_inputs`: see tdc_feature_inputs;
-        `config.tdc_frame_inputs`: see tdc_frame_inputs.
+        `config.tdc_frame_inputs`: see tdc_frame_inputs; `config.tdc_kv_cache_bytes`: see tdc_kv_cache_bytes.
         bench.py's line is reproduced by dtype=float16, tdc_tower_dtype="bfloat16", tdc_tower_res_dtype="float16",
         tdc_frame_cap=T (its `product_setting` field says so; `bench.py --via-mixin` runs exactly that)."""
         if self._tdc_encoder is None or refresh:
@@ -431,19 +431,42 @@ class CambrianMetaModel:
         is absent or 0.  Videos and single images then skip the towers and the connector for frames whose content the
         cache holds - the results are bit for bit those without it.  Ignored (None) under `config.tdc_shard_frames`:
         the frame-sharded path has a per-rank cache of its own (tdc_shard_cache).  A new engine (tdc_engine(refresh=True))
-        gets a new, empty cache."""
+        gets a new, empty cache.  `config.tdc_kv_cache_bytes` (tdc_kv_cache_bytes) gives it a K/V budget."""
         n = getattr(self.config, "tdc_video_cache_bytes", None)
         if isinstance(n, bool) or not (n is None or isinstance(n, int)) or (n or 0) < 0:
             raise ValueError("config.tdc_video_cache_bytes must be a byte budget (a non-negative int; 0 / absent = off), "
                              "got %r" % (n,))
+        kv = self.tdc_kv_cache_bytes()
         if not n or getattr(self.config, "tdc_shard_frames", False):
             return None
         eng = self.tdc_engine()
         c = getattr(self, "_tdc_video_cache", None)
-        if c is None or getattr(self, "_tdc_video_cache_engine", None) is not eng or c.max_bytes != n:
-            c = self._tdc_video_cache = eng.new_cache(n)
+        if c is None or getattr(self, "_tdc_video_cache_engine", None) is not eng or c.max_bytes != n or \
+                getattr(c, "kv_max_bytes", 0) != kv:
+            c = self._tdc_video_cache = eng.new_cache(n, kv) if kv else eng.new_cache(n)
             self._tdc_video_cache_engine = eng
         return c
+
+    def tdc_kv_cache_bytes(self):
+        """`config.tdc_kv_cache_bytes`: a byte budget of its own inside the frame cache for the Q-Former's cross-attention K/V
+        (DESIGN.md section 17): one entry per (video, a1 selection), so a later question about a cached video skips the stacked
+        K/V projection and the row gather in front of it - the 10-tuple is bit for bit the key-off call's.  0 / absent: off.
+        It lives in the frame cache, so it needs `config.tdc_video_cache_bytes`, and composes with `config.tdc_batch_prompts`
+        and `tdc_frame_inputs`, which go through that cache; set together with `config.tdc_shard_frames`,
+        `tdc_shard_cache_bytes`, `tdc_batch_frames` or `tdc_feature_inputs` it raises: those paths keep no K/V."""
+        n = getattr(self.config, "tdc_kv_cache_bytes", None)
+        if isinstance(n, bool) or not (n is None or isinstance(n, int)) or (n or 0) < 0:
+            raise ValueError("config.tdc_kv_cache_bytes must be a byte budget (a non-negative int; 0 / absent = off), "
+                             "got %r" % (n,))
+        if not n:
+            return 0
+        if not getattr(self.config, "tdc_video_cache_bytes", None):
+            raise ValueError("config.tdc_kv_cache_bytes needs config.tdc_video_cache_bytes: the K/V entries live in the "
+                             "frame cache and are keyed by its fingerprints")
+        for other in ("tdc_shard_frames", "tdc_shard_cache_bytes", "tdc_batch_frames", "tdc_feature_inputs"):
+            if getattr(self.config, other, None):
+                raise ValueError("config.tdc_kv_cache_bytes and config.%s cannot be set together" % other)
+        return n
 
     def tdc_video_cache_clear(self):
         """empty the frame cache (and release its device memory); no-op when it is off"""

@@ -453,10 +453,11 @@ class VideoEncoder:
         fp = ops.fingerprint_rows(px.contiguous(), rows, row_bytes, row_stride)
         return [(a & 0xFFFFFFFFFFFFFFFF, b & 0xFFFFFFFFFFFFFFFF) for a, b in self.fetch(fp, self.mark())]
 
-    def new_cache(self, max_bytes):
-        """a FrameCache of max_bytes for encode_video(cache=...) of this engine (cache.py)"""
+    def new_cache(self, max_bytes, kv_bytes=0):
+        """a FrameCache of max_bytes for encode_video(cache=...) of this engine (cache.py); kv_bytes > 0: it also keeps the
+        Q-Former's cross-attention K/V per (video, a1 selection) within that budget of their own"""
         from .cache import FrameCache, engine_signature
-        return FrameCache(max_bytes, engine_signature(self))
+        return FrameCache(max_bytes, engine_signature(self), kv_bytes)
 
     # ---- stored tower features (features.py, DESIGN.md section 13) --------------------------------------------------------
     def tower_width(self, name):
@@ -682,12 +683,14 @@ class VideoEncoder:
         return X, sizes
 
     # ------------------------------------------------------------------------------------------------ a11-a19
-    def qformer(self, enc, F, Nenc, query, qsrc, prompt_ids, multi=None):
+    def qformer(self, enc, F, Nenc, query, qsrc, prompt_ids, multi=None, kv=None):
         """Batched Q-Former (tdc/Qformer.py:804-965) over F compressed frames.
         enc [F*Nenc, Hp] 16-bit; query [nC*K, Dq_pad] (query_proj output per chunk); qsrc int32 [F] chunk of frame.
         Returns last hidden state rows of the K query tokens as the combined buffer h16 [F*S, Dq_pad] and S.
         multi (the multi-prompt form): dict of HOST lists kv_src [F], frame_prompt [F] and the int
-        enc_frames = U; prompt_ids is then a list of P id lists, F counts virtual frames, enc holds U frames and S = K + Lmax."""
+        enc_frames = U; prompt_ids is then a list of P id lists, F counts virtual frames, enc holds U frames and S = K + Lmax.
+        kv (kept K/V; checked by compress_frames): the stacked K/V GEMM writes kv.buf, or, when kv.ready,
+        is not launched - enc is then not read and may be None."""
         qf, dt = self.c.qformer, self.dtype
         Dq = qf.dim
         K = self.K
@@ -698,7 +701,7 @@ class VideoEncoder:
             if not self.multi_prompt_ok(Nenc):                    # refused before any launch
                 raise ValueError("the multi-prompt Q-Former runs xattn_mode 0 / 1 only")
             U = int(multi["enc_frames"])
-            assert enc.shape[0] >= U * Nenc
+            assert enc is None or enc.shape[0] >= U * Nenc
             lens = [len(p or []) for p in prompt_ids]
             Lt = max(lens)
             ops.index_tensor(multi["kv_src"], 0, U, "cpu", "qformer kv_src")
@@ -714,6 +717,8 @@ class VideoEncoder:
         # the cross-attention block: fused form = key GEMM + transposed value GEMM + one kernel per cross layer
         mode = int(self.xattn_mode) if qf.cross_k is not None else 0
         fused = mode >= 2 and ops.qformer_xattn_supported(Dq, heads, K, Nenc)
+        if kv is not None and fused:                              # refused before any launch
+            raise ValueError("kept K/V (kv=) runs xattn_mode 0 / 1 only")
         out_fused = not fused and mode >= 1 and ops.qformer_xattn_supported(Dq, heads, K, 8)
         if fused or out_fused:
             self._tile_cross_weights()
@@ -722,8 +727,11 @@ class VideoEncoder:
             k_all = ops.gemm(enc, qf.cross_k.w, qf.cross_k.b, M=F * Nenc)     # [F*Nenc, n_cross*Dq]
             vt_all = torch.empty(qf.cross_v.w.shape[0], pad64(F * Nenc + 4), device=self.dev, dtype=dt)   # ldvt >= round_up(F*Nenc, 8)
             ops.gemm(qf.cross_v.w, enc[:F * Nenc], out=vt_all, c_pad8=True)   # V^T = Wv enc^T: [n_cross*Dq, F*Nenc]
+        elif kv is not None and kv.ready:
+            kv_all = kv.buf                                                   # the rows an earlier pass projected
         else:
-            kv_all = ops.gemm(enc, qf.cross_kv.w, qf.cross_kv.b, M=U * Nenc)  # [F*Nenc, n_cross*2*Dq] (multi: U frames)
+            kv_all = ops.gemm(enc, qf.cross_kv.w, qf.cross_kv.b, M=U * Nenc,  # [F*Nenc, n_cross*2*Dq] (multi: U frames)
+                              out=None if kv is None else kv.buf)
         ops.profile_tag(0)
         Dp = h16.shape[1]
         ctx = torch.zeros(F * S, Dp, device=self.dev, dtype=dt)
@@ -942,12 +950,18 @@ class VideoEncoder:
             hit = self._tables[key] = torch.tensor(key[1], dtype=torch.int32, device=self.dev)
         return hit
 
-    def _compress_native(self, enc, F, Nf, qtable, qs, prompt_ids, multi=None):
+    def _compress_native(self, enc, F, Nf, qtable, qs, prompt_ids, multi=None, kv=None):
         import ctypes as C
         m = self._qformer_struct()[0]
         K = self.K
         assert qs.dtype == torch.int32 and qs.numel() >= F        # value range checked on the host list (compress_frames)
         U = F
+        if kv is not None:
+            # kept K/V (tdc_qformer_model.kv_keep): a copy of the model struct carries the buffer, the cached one stays as is
+            mk = L.QformerModel()
+            C.pointer(mk)[0] = m
+            mk.kv_keep, mk.kv_state = kv.buf.data_ptr(), int(bool(kv.ready))
+            m = mk
         if multi is not None:
             # the multi-prompt form (tdc_qformer_prompts): a copy of the model struct carries the block, the cached one stays as is
             qf = self.c.qformer
@@ -969,11 +983,17 @@ class VideoEncoder:
         else:
             ids = self._prompt_tensor(prompt_ids)
             Lt = 0 if ids is None else ids.numel()
-        assert enc.shape[0] >= U * Nf and enc.shape[1] >= m.cross_kv.k and qtable.shape[1] >= pad64(m.dim)
+        assert qtable.shape[1] >= pad64(m.dim)
+        if enc is None:                                           # ready K/V: the composite does not read enc
+            assert kv is not None and kv.ready
+            enc_ptr, ldenc = C.c_void_p(0), 0
+        else:
+            assert enc.shape[0] >= U * Nf and enc.shape[1] >= m.cross_kv.k
+            enc_ptr, ldenc = ops._ptr(enc), enc.stride(0)
         lib = L.load()
         ws = self._workspace("_qf_ws", lib.tdc_qformer_workspace_bytes(C.byref(m), F, K, Lt, Nf))
         out = torch.empty(F * K, pad64(self.c.H), device=self.dev, dtype=self.dtype)
-        L.check(lib.tdc_qformer_fwd(C.byref(m), ops._ptr(enc), enc.stride(0), F, Nf, ops._ptr(qtable), qtable.stride(0),
+        L.check(lib.tdc_qformer_fwd(C.byref(m), enc_ptr, ldenc, F, Nf, ops._ptr(qtable), qtable.stride(0),
                                     ops._ptr(qs), ops._ptr(ids if Lt else None), Lt, K, ops._ptr(out), out.stride(0),
                                     ops._ptr(ws), ws.numel(), ops._stream()), "tdc_qformer_fwd")
         return out
@@ -985,11 +1005,27 @@ class VideoEncoder:
         return not (int(self.xattn_mode) >= 2 and qf.cross_k is not None and
                     ops.qformer_xattn_supported(qf.dim, self.qheads, self.K, Nf))
 
-    def compress_frames(self, Xf, Nf, frame_rows, qtable, qsrc, prompt_ids, keep=None, multi=None):
+    def kv_cache_ok(self, Nf):
+        """whether compress_frames takes kept K/V (kv=) here: as multi_prompt_ok, not under the whole-block cross-attention
+        kernel, which keeps K and transposed V in two buffers of other shapes - the callers then run the plain path"""
+        return self.multi_prompt_ok(Nf)
+
+    def kv_entry_bytes(self, U, Nf):
+        """bytes of the kept K/V of U frames of Nf rows: U * Nf * n_cross * 2 * dim 16-bit values"""
+        return U * Nf * self.c.qformer.cross_kv.w.shape[0] * 2
+
+    def kv_alloc(self, U, Nf):
+        """an unfilled kept-K/V buffer [U * Nf, n_cross * 2 * dim] for compress_frames(kv=KeptKV(buf, ready=False))"""
+        return torch.empty(U * Nf, self.c.qformer.cross_kv.w.shape[0], device=self.dev, dtype=self.dtype)
+
+    def compress_frames(self, Xf, Nf, frame_rows, qtable, qsrc, prompt_ids, keep=None, multi=None, kv=None):
         """a13-a18 for the frames `frame_rows` of Xf: Q-Former against queries qtable[qsrc[f]] -> [F*K, >=H] unit rows.
         multi = dict(kv_src, frame_prompt) (prompt_maps): frame_rows are the U DISTINCT frames, gathered and projected to K/V
         once; qsrc / kv_src / frame_prompt have one entry per virtual frame, prompt_ids is the list of the prompts' id lists;
-        -> [F*K, >=H] in virtual-frame order, each row block bit for bit that of the prompt's own call."""
+        -> [F*K, >=H] in virtual-frame order, each row block bit for bit that of the prompt's own call.
+        kv = cache.KeptKV(buf, ready): buf [U*Nf, n_cross*2*dim] (kv_alloc) holds the stacked cross-attention
+        K/V of the U frames instead of the workspace.  Not ready: this pass projects into it, by the launch that fills the
+        workspace otherwise.  Ready: neither the enc gather nor that GEMM is launched.  The result is the kv=None one bit for bit."""
         c, dev = self.c, self.dev
         K, H = self.K, c.H
         U = len(frame_rows)
@@ -997,21 +1033,29 @@ class VideoEncoder:
         Hp = Xf.shape[1]
         assert F == len(qsrc) and (max(qsrc) + 1) * K <= qtable.shape[0] and min(qsrc) >= 0
         assert min(frame_rows) >= 0 and (max(frame_rows) + 1) * Nf <= Xf.shape[0]
-        fr = torch.tensor(frame_rows, dtype=torch.int32, device=dev)
-        enc_idx = torch.zeros(U * Nf, 2, dtype=torch.int32, device=dev)
-        enc_idx[:, 1] = (fr[:, None] * Nf + torch.arange(Nf, dtype=torch.int32, device=dev)[None, :]).reshape(-1)
-        enc = ops.gather_rows([Xf], enc_idx, U * Nf, Hp, validated=True)      # frame_rows range-checked above
+        if kv is not None:
+            if not self.kv_cache_ok(Nf):
+                raise ValueError("compress_frames: kept K/V (kv=) runs xattn_mode 0 / 1 only (kv_cache_ok)")
+            b, n = kv.buf, c.qformer.cross_kv.w.shape[0]
+            assert b.is_cuda and b.device == Xf.device and b.dtype == self.dtype and b.dim() == 2 and b.is_contiguous() and \
+                tuple(b.shape) == (U * Nf, n) and b.data_ptr() % 256 == 0, "kv.buf is kv_alloc(U, Nf)"
+        enc = None
+        if kv is None or not kv.ready:
+            fr = torch.tensor(frame_rows, dtype=torch.int32, device=dev)
+            enc_idx = torch.zeros(U * Nf, 2, dtype=torch.int32, device=dev)
+            enc_idx[:, 1] = (fr[:, None] * Nf + torch.arange(Nf, dtype=torch.int32, device=dev)[None, :]).reshape(-1)
+            enc = ops.gather_rows([Xf], enc_idx, U * Nf, Hp, validated=True)  # frame_rows range-checked above
         qs = torch.tensor(qsrc, dtype=torch.int32, device=dev)
         if multi is not None:
             if not self.multi_prompt_ok(Nf):
                 raise ValueError("compress_frames: the multi-prompt form runs xattn_mode 0 / 1 only (multi_prompt_ok)")
             multi = dict(multi, enc_frames=U)
         if self.native_qformer:
-            comp = self._compress_native(enc, F, Nf, qtable, qs, prompt_ids, multi)
+            comp = self._compress_native(enc, F, Nf, qtable, qs, prompt_ids, multi, kv)
             if keep is not None:
                 keep.update(compressed=comp)
             return comp
-        h16, S = self.qformer(enc, F, Nf, qtable, qs, prompt_ids, multi)
+        h16, S = self.qformer(enc, F, Nf, qtable, qs, prompt_ids, multi, kv)
         comp = ops.gemm(h16, c.vision_proj.w, c.vision_proj.b, M=F * K, a_map=(K, S, 0, 1))
         ops.l2_normalize(comp, F * K, H)
         if keep is not None:
