@@ -1,6 +1,10 @@
 """Orchestration of the video encode over an "engine": every policy decision of the path has one
 function here, called by the serial path, the batched, cached and multi-prompt ones and the frame-sharded one (dist.py).
 
+A video comes as pixels, decoded frames or stored tower features: a source each (PixelSource, FrameSource, FeatureSource) that
+knows T0, image_size, front() - a2-a10 and a20 of the frames a1 kept - and image().  encode_source (one prompt) and
+encode_source_prompts (several) evaluate a1 and run any source; the *_with names are their adapters per input kind.
+
 The engine is pipeline.VideoEncoder on GPUs; the CPU tests plug in doubles.  The engine protocol:
   required   cfg, K, H, dtype; tower(name, px), sims_tensor(dino, T), connector(sig, dino, T, sizes, keep), local_audio,
              with_audio, make_queries, learned_queries, query_width, compress_frames, emit
@@ -101,6 +105,17 @@ def cache_info_of(f, info):
     return ci
 
 
+def compress_kept(e, kvs, info, Xf, Nf, frames, *rest):
+    """e.compress_frames(Xf, Nf, frames, *rest) through the K/V store kvs (None: no store): kv= is passed only when kv_begin
+    hands a buffer out - a hit or a fill, committed once the pass has run -, so an engine of today sees today's call"""
+    kv, commit = kv_begin(e, kvs, frames, Nf, info) if kvs is not None else (None, None)
+    if kv is None:
+        return e.compress_frames(Xf, Nf, frames, *rest)
+    comp = e.compress_frames(Xf, Nf, frames, *rest, kv=kv)
+    commit()
+    return comp
+
+
 def compress_planned(e, Xf, N, Nf, plan, learned, prompt_ids, keep=None, splice=None, info=None, kvs=None):
     """compress_with after its planning: one prompt's Q-Former pass and emission over the rows Xf (with_audio) by `plan`.
     kvs (kv_store): the pass takes the cross-attention K/V of its compressed frames from the store, or fills its entry."""
@@ -110,12 +125,7 @@ def compress_planned(e, Xf, N, Nf, plan, learned, prompt_ids, keep=None, splice=
             qtable, qsrc = e.learned_queries(), [0] * len(plan["comp_frames"])
         else:
             qtable, qsrc = e.make_queries(Xf, N, Nf, plan["key_frames"]), plan["comp_chunk"]
-        kv, commit = kv_begin(e, kvs, plan["comp_frames"], Nf, info) if kvs is not None and keep is None else (None, None)
-        if kv is None:
-            comp = e.compress_frames(Xf, Nf, plan["comp_frames"], qtable, qsrc, prompt_ids, keep)
-        else:
-            comp = e.compress_frames(Xf, Nf, plan["comp_frames"], qtable, qsrc, prompt_ids, keep, kv=kv)
-            commit()
+        comp = compress_kept(e, kvs if keep is None else None, info, Xf, Nf, plan["comp_frames"], qtable, qsrc, prompt_ids, keep)
     pairs = seg.emit_pairs(plan, Nf, e.K)
     if keep is not None:
         keep["plan"] = plan
@@ -205,13 +215,8 @@ def compress_many_with(e, X, T, N, seg_indices, prompts, audio=None, infos=None,
             qtable = e.learned_queries() if learned else e.make_queries(Xf, N, Nf, maps["key_frames"])
             mm = dict(kv_src=maps["kv_src"], frame_prompt=maps["frame_prompt"])
             grec = {}
-            kv, commit = kv_begin(e, kvs, maps["enc_frames"], Nf, grec) if kvs is not None else (None, None)
-            if kv is None:
-                comp = e.compress_frames(Xf, Nf, maps["enc_frames"], qtable, maps["qsrc"], [pids[p] or [] for p in g], None, mm)
-            else:
-                comp = e.compress_frames(Xf, Nf, maps["enc_frames"], qtable, maps["qsrc"], [pids[p] or [] for p in g], None, mm,
-                                         kv=kv)
-                commit()
+            comp = compress_kept(e, kvs, grec, Xf, Nf, maps["enc_frames"], qtable, maps["qsrc"], [pids[p] or [] for p in g], None,
+                                 mm)
         for j, p in enumerate(g):
             info = infos[p] if infos is not None else None
             splice = prompts[p].get("splice")
@@ -240,18 +245,25 @@ def encode_video_prompts_with(e, px_siglip, px_dino, image_size, prompts, audio=
     through compress_many_with.  prompts: dicts of budget_text_len, n_text_tokens, prompt_ids, optional splice.  infos: one dict
     per prompt, filled as encode_video's info= plus info["prompts"] (the selection's front facts - info["cache"] among them -
     are those of the ONE front pass the selection's prompts share)."""
-    def front(btl, finfo):
-        return video_front(e, cache, px_siglip, px_dino, image_size, btl, audio, frame_cap, None, video_index, finfo)
-    return prompts_over_fronts(e, px_siglip.shape[0], prompts, front, frame_cap, infos, max_prompts, pad_fraction)
+    return encode_source_prompts(e, PixelSource(px_siglip, px_dino, image_size, cache), prompts, audio, frame_cap, video_index,
+                                 infos, max_prompts, pad_fraction)
 
 
-def prompts_over_fronts(e, T0, prompts, front, frame_cap=224, infos=None, max_prompts=8, pad_fraction=0.25):
-    """encode_video_prompts_with behind its input: the prompts of one T0-frame video grouped by their a1 selection,
-    front(budget_text_len, info) -> the front of a selection (run once per distinct selection), compress_many_with over each"""
-    cfg = e.cfg
+def encode_source_prompts(e, src, prompts, audio=None, frame_cap=224, video_index=None, infos=None, max_prompts=8,
+                          pad_fraction=0.25):
+    """encode_video_prompts_with over any source (PixelSource, FrameSource, FeatureSource): a1 per prompt, here and nowhere
+    below; the front of each distinct selection runs once (prompts_over_fronts)"""
+    sels = [frame_indices(e.cfg, src.T0, pr["budget_text_len"], frame_cap) for pr in prompts]       # a1
+    return prompts_over_fronts(e, sels, prompts, lambda idx, finfo: src.front(e, idx, audio, video_index, finfo), infos,
+                               max_prompts, pad_fraction)
+
+
+def prompts_over_fronts(e, selections, prompts, front, infos=None, max_prompts=8, pad_fraction=0.25):
+    """encode_source_prompts behind a1: the prompts of one video grouped by their a1 selection (selections[p]),
+    front(idx, info) -> the front of the selection idx (run once per distinct selection), compress_many_with over each"""
     sels, order = {}, []
-    for p, pr in enumerate(prompts):
-        key = tuple(frame_indices(cfg, T0, pr["budget_text_len"], frame_cap))                       # a1
+    for p, idx in enumerate(selections):
+        key = tuple(idx)
         if key not in sels:
             sels[key] = []
             order.append(key)
@@ -260,9 +272,8 @@ def prompts_over_fronts(e, T0, prompts, front, frame_cap=224, infos=None, max_pr
     base = 0
     for key in order:
         members = sels[key]
-        btl = prompts[members[0]]["budget_text_len"]
         finfo = {} if infos is not None else None
-        f = front(btl, finfo)
+        f = front(selections[members[0]], finfo)
         sub = [infos[p] for p in members] if infos is not None else None
         res = compress_many_with(e, f["X"], f["T"], f["N"], f["seg_idx"], [prompts[p] for p in members], f["audio"], sub,
                                  max_prompts, pad_fraction, f.get("kv"))
@@ -271,8 +282,7 @@ def prompts_over_fronts(e, T0, prompts, front, frame_cap=224, infos=None, max_pr
             if infos is not None:
                 info = infos[p]
                 info.update(finfo)
-                info.update(frame_indices=f["idx"], selected=list(range(f["T"])), seg_indices=f["seg_idx"],
-                            final_size=f["final_size"])
+                selection_facts(info, f)
                 if "cache_info" in f:
                     info["cache"] = cache_info_of(f, info)
                 info["prompts"]["group"] += base
@@ -295,17 +305,24 @@ def content_key(e, v):
     return ("value", repr(v))
 
 
+def audio_key(e, audio, T0, idx, video_index=None):
+    """what two calls must share of their audio: its content and the seconds it is sampled at (None without audio) - part of
+    the same-video keys and of the name of a kept K/V entry"""
+    if audio is None:
+        return None
+    return (content_key(e, audio), tuple(sample_indicator(T0, idx, video_index)))
+
+
+def same_source_key(e, src, budget_text_len, frame_cap, audio=None, video_index=None):
+    """`config.tdc_batch_prompts`: what two samples of one call must share to be questions about the SAME video: the content
+    of what a1 keeps of their source (PixelSource.same_key, FeatureSource.same_key) and their audio (audio_key)"""
+    idx = frame_indices(e.cfg, src.T0, budget_text_len, frame_cap)                                  # a1
+    return src.same_key(e, idx, audio, video_index)
+
+
 def same_video_key(e, px_siglip, px_dino, image_size, budget_text_len, frame_cap, audio=None, video_index=None):
-    """`config.tdc_batch_prompts`: what two samples of one call must share to be questions about the SAME video - the frame
-    cache's key material (FrameCache.frame_keys: the fingerprints of their a1-selected pixels, pixel geometry, image_size), and
-    the content of their audio with the seconds it is sampled at.  Frames a1 drops are never read, so they do not count."""
-    from .cache import FrameCache
-    idx = frame_indices(e.cfg, px_siglip.shape[0], budget_text_len, frame_cap)
-    keys, _ = FrameCache.frame_keys(e, px_siglip.to(e.dev), px_dino.to(e.dev), idx, image_size)
-    akey = None
-    if audio is not None:
-        akey = (content_key(e, audio), tuple(sample_indicator(px_siglip.shape[0], idx, video_index)))
-    return (px_siglip.shape[0], tuple(idx), tuple(keys), akey)
+    """same_source_key of a video's pixels"""
+    return same_source_key(e, PixelSource(px_siglip, px_dino, image_size), budget_text_len, frame_cap, audio, video_index)
 
 
 def frame_indices(cfg, T0, budget_text_len, frame_cap):
@@ -413,26 +430,33 @@ def towers_and_selection(e, px_s, px_d, spans, infos=None):
     return sig, dino, seg_idx
 
 
-def video_front_with(e, px_siglip, px_dino, image_size, budget_text_len, audio=None, frame_cap=224, keep=None,
-                     video_index=None, info=None):
-    """the prompt-independent part of encode_video_with (a1-a10, a20): -> dict(X, T, N, seg_idx, audio, idx, final_size, sig,
-    dino).  Only a1 reads the prompt (through budget_text_len)."""
-    cfg = e.cfg
-    T0 = px_siglip.shape[0]
-    idx = frame_indices(cfg, T0, budget_text_len, frame_cap)                                        # a1
-    if len(idx) != T0:                      # every frame kept: the pixels stay where they lie
-        sel = torch.tensor(idx, device=px_siglip.device)
-        px_siglip, px_dino = px_siglip[sel], px_dino[sel]
+def segmented(cfg, T):
+    """whether a5 runs over T kept frames: only more than max_num_segments + 1 of them are segmented"""
+    return T > cfg.get("max_num_segments", 24) + 1
+
+
+def pixel_front(e, cache, px_siglip, px_dino, rows, idx, T0, image_size, audio=None, keep=None, video_index=None, info=None):
+    """the prompt-independent part of an encode behind a1 (a2-a10, a20) from pixels: the kept frames are the rows `rows` of
+    px_siglip / px_dino and the frames idx of the T0-frame video -> dict(X, T, N, seg_idx, audio, idx, final_size, sig, dino).
+    Through the cache (front_cached_selected, which adds `cache_info` and leaves sig / dino out) unless there is none, keep=
+    asks for the stage tensors only the uncached per-kernel connector form produces, or the call is over the cache's budget."""
+    f = None
+    if cache is not None and keep is None:
+        f = front_cached_selected(e, cache, px_siglip, px_dino, rows, idx, T0, image_size, audio, video_index, info)
+    if f is not None:
+        return f
     T = len(idx)
-    sig, dino, (seg_idx,) = towers_and_selection(e, px_siglip, px_dino, [(0, T, T > cfg.get("max_num_segments", 24) + 1)],
+    if T != px_siglip.shape[0]:             # every frame kept: the pixels stay where they lie
+        sel = torch.tensor(rows, device=px_siglip.device)
+        px_siglip, px_dino = px_siglip[sel], px_dino[sel]
+    sig, dino, (seg_idx,) = towers_and_selection(e, px_siglip, px_dino, [(0, T, segmented(e.cfg, T))],
                                                  None if info is None else [info])                  # a3-a5
     return front_after_towers(e, sig, dino, seg_idx, T0, idx, image_size, audio, keep, video_index)
 
 
 def front_after_towers(e, sig, dino, seg_idx, T0, idx, image_size, audio=None, keep=None, video_index=None):
     """what a front does once the tower rows of the a1-kept frames idx (of T0) and their a5 selection are known - the
-    connector (a6-a10) and the frames' audio (a20) -> the front's dict.  Shared by the pixel front (video_front_with) and the
-    front from stored features (video_front_from_features)."""
+    connector (a6-a10) and the frames' audio (a20) -> the front's dict.  Shared by pixel_front and FeatureSource.front."""
     T = len(idx)
     sizes = [tuple(image_size)] * T
     X, final_size = e.connector(sig, dino, T, sizes, keep)                                          # a6-a10
@@ -442,38 +466,78 @@ def front_after_towers(e, sig, dino, seg_idx, T0, idx, image_size, audio=None, k
     return dict(X=X, T=T, N=N, seg_idx=seg_idx, audio=audio, idx=idx, final_size=final_size, sig=sig, dino=dino)
 
 
-def video_front(e, cache, px_siglip, px_dino, image_size, budget_text_len, audio=None, frame_cap=224, keep=None,
-                video_index=None, info=None):
-    """the front of one video: video_front_cached when a FrameCache is given and takes the call, else video_front_with (no
-    cache; keep=, whose stage tensors only the uncached per-kernel connector form produces; a call over the cache's budget)"""
-    f = None
-    if cache is not None and keep is None:
-        f = video_front_cached(e, cache, px_siglip, px_dino, image_size, budget_text_len, audio, frame_cap, video_index, info)
-    return f or video_front_with(e, px_siglip, px_dino, image_size, budget_text_len, audio, frame_cap, keep, video_index, info)
+def image_rows(e, px_siglip, px_dino, image_size, cache=None):
+    """a single image ([1, 3, H, W] each): no a1 / a5 / Q-Former -> (connector rows [N, Hp], [final size]); through the frame
+    cache when one is given"""
+    if cache is not None:
+        return encode_image_cached(e, cache, px_siglip, px_dino, image_size)
+    return e.connector(e.tower("siglip", px_siglip), e.tower("dino", px_dino), 1, [tuple(image_size)])
+
+
+class PixelSource:
+    """what an encode reads its frames from: here the pixels of ALL T0 frames of a video (px_siglip, px_dino [T0, 3, H, W]),
+    through a FrameCache when one is given.  A source has T0 and image_size, front(e, idx, audio, video_index, info, keep) ->
+    the front (a2-a10, a20) of the frames idx a1 kept, and image(e, info) -> the connector rows of its one frame as a single
+    image (info receives what that entry reports).  FrameSource and FeatureSource are the other two."""
+
+    def __init__(self, px_siglip, px_dino, image_size, cache=None):
+        self.px_siglip, self.px_dino, self.image_size, self.cache = px_siglip, px_dino, image_size, cache
+        self.T0 = px_siglip.shape[0]
+
+    def front(self, e, idx, audio=None, video_index=None, info=None, keep=None):
+        return pixel_front(e, self.cache, self.px_siglip, self.px_dino, idx, idx, self.T0, self.image_size, audio, keep,
+                           video_index, info)
+
+    def image(self, e, info=None):
+        X, sizes = image_rows(e, self.px_siglip, self.px_dino, self.image_size, self.cache)
+        if info is not None:
+            info["final_size"] = sizes
+        return X
+
+    def same_key(self, e, idx, audio=None, video_index=None):
+        """same_source_key behind a1: the frame cache's key material (FrameCache.frame_keys: the fingerprints of the a1-selected
+        pixels, pixel geometry, image_size) and the audio.  Frames a1 drops are never read, so they do not count."""
+        from .cache import FrameCache
+        keys, _ = FrameCache.frame_keys(e, self.px_siglip.to(e.dev), self.px_dino.to(e.dev), idx, self.image_size)
+        return (self.T0, tuple(idx), tuple(keys), audio_key(e, audio, self.T0, idx, video_index))
+
+
+def encode_source(e, src, budget_text_len, n_text_tokens, prompt_ids, audio=None, frame_cap=224, keep=None, splice=None,
+                  video_index=None, info=None, image=False):
+    """One video from any source (PixelSource, FrameSource, FeatureSource) -> emitted visual tokens [n, H]
+    (VideoEncoder.encode_video documents the arguments).  a1 is evaluated here and nowhere below.  image=True: the source's one
+    frame as a single image - its connector rows [:, :H], as prepare_inputs_labels_for_multimodal's image branch; a1 is not
+    evaluated and budget_text_len may be None."""
+    if image:
+        return src.image(e, info)[:, :e.H]
+    idx = frame_indices(e.cfg, src.T0, budget_text_len, frame_cap)                                  # a1
+    f = src.front(e, idx, audio, video_index, info, keep)
+    return encode_front(e, f, n_text_tokens, prompt_ids, keep, splice, info)
 
 
 def encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio=None,
                       frame_cap=224, keep=None, splice=None, video_index=None, info=None, cache=None):
-    """One video: pixels -> emitted visual tokens [n, H] (VideoEncoder.encode_video documents the arguments).  cache: a
-    FrameCache - the front runs through it (video_front), the result is bit for bit that of cache=None, and info["cache"]
-    says what the call reused and encoded."""
-    f = video_front(e, cache, px_siglip, px_dino, image_size, budget_text_len, audio, frame_cap, keep, video_index, info)
-    return encode_front(e, f, n_text_tokens, prompt_ids, keep, splice, info)
+    """One video: pixels -> emitted visual tokens [n, H].  cache: a FrameCache - the front runs through it, the result is bit
+    for bit that of cache=None, and info["cache"] says what the call reused and encoded."""
+    return encode_source(e, PixelSource(px_siglip, px_dino, image_size, cache), budget_text_len, n_text_tokens, prompt_ids,
+                         audio, frame_cap, keep, splice, video_index, info)
+
+
+def selection_facts(info, f):
+    """what info= (and keep=) report of the front f.  selected: what a5's second frame cap keeps - every frame (frame_indices)"""
+    info.update(frame_indices=f["idx"], selected=list(range(f["T"])), seg_indices=f["seg_idx"], final_size=f["final_size"])
 
 
 def encode_front(e, f, n_text_tokens, prompt_ids, keep=None, splice=None, info=None):
-    """one prompt over the front f (video_front / video_front_from_features): a11-a19 (+a21) -> emitted visual tokens [n, H]"""
+    """one prompt over the front f (a source's front): a11-a19 (+a21) -> emitted visual tokens [n, H]"""
     cfg = e.cfg
-    X, T, N, seg_idx, idx, final_size = f["X"], f["T"], f["N"], f["seg_idx"], f["idx"], f["final_size"]
-    max_visual_len = visual_budget(cfg, n_text_tokens)
-    pid = text_prompt(cfg, prompt_ids)
-    vis = compress_with(e, X, T, N, seg_idx, pid, max_visual_len, f["audio"], keep, splice, info,   # a11-a19 (+a21)
-                        f.get("kv"))
-    if keep is not None:                    # selected: what a5's second frame cap keeps - every frame (frame_indices)
-        keep.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, siglip_feat=f["sig"], dino_feat=f["dino"],
-                    final_size=final_size, X=X)
+    vis = compress_with(e, f["X"], f["T"], f["N"], f["seg_idx"], text_prompt(cfg, prompt_ids),      # a11-a19 (+a21)
+                        visual_budget(cfg, n_text_tokens), f["audio"], keep, splice, info, f.get("kv"))
+    if keep is not None:
+        selection_facts(keep, f)
+        keep.update(siglip_feat=f["sig"], dino_feat=f["dino"], X=f["X"])
     if info is not None:
-        info.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx, final_size=final_size)
+        selection_facts(info, f)
         if "cache_info" in f:               # read after the compressor ran
             info["cache"] = cache_info_of(f, info)
     return vis
@@ -562,7 +626,7 @@ def encode_batch_with(e, samples, frame_cap, infos=None):
         out.append(compress_with(e, Xs, T, n // T, seg_idx[j], text_prompt(cfg, s["prompt_ids"]),   # a11-a19 (+a21)
                                  visual_budget(cfg, s["n_text_tokens"]), audio, None, s.get("splice"), info))
         if info is not None:
-            info.update(frame_indices=idx, selected=list(range(T)), seg_indices=seg_idx[j], final_size=fs)
+            selection_facts(info, dict(idx=idx, T=T, seg_idx=seg_idx[j], final_size=fs))
     assert r == X.shape[0], "connector rows %d, split %d" % (X.shape[0], r)
     return out
 
@@ -598,7 +662,7 @@ def encode_image_cached(e, cache, px_siglip, px_dino, image_size):
     cache.bind(e)
     keys, _ = cache.frame_keys(e, px_siglip, px_dino, [0], image_size)
     if encode_missing(e, cache, keys, px_siglip, px_dino, [0], image_size) is None:
-        return e.connector(e.tower("siglip", px_siglip), e.tower("dino", px_dino), 1, [tuple(image_size)])
+        return image_rows(e, px_siglip, px_dino, image_size)
     return cache.assemble(e, keys), cache.final_sizes(keys)
 
 
@@ -647,43 +711,34 @@ def fingerprint_mask(m):
     return fingerprint_rows_host(m.to(torch.uint8).numpy()[None])[0]
 
 
-def video_front_cached(e, cache, px_siglip, px_dino, image_size, budget_text_len, audio=None, frame_cap=224,
-                       video_index=None, info=None):
-    """the prompt-independent part of a cached encode (a1-a10, a20): a1 as in video_front_with; the a1-selected frames are
-    fingerprinted where they lie; only the frames the cache lacks run through the towers and the connector (frames are
-    independent through a3-a10) and are stored; the a5 similarities come from the cache or from the cached DINOv2 rows
-    (tdc_pair_cossim), the refinement's precise values from the cache or from the pixels passed; the connector rows of the kept
-    frames are gathered out of the slab.  -> video_front_with's dict plus `cache_info()` (the info["cache"] entry, read after
+def front_cached_selected(e, cache, px_siglip, px_dino, rows, idx, T0, image_size, audio=None, video_index=None, info=None):
+    """the prompt-independent part of a cached encode behind a1 (a2-a10, a20): the kept frames are the rows `rows` of
+    px_siglip / px_dino and the frames idx of the T0-frame video.  PixelSource passes rows = idx (the pixels of all T0 frames);
+    FrameSource has resized only the kept frames and passes rows = 0 .. T-1.  Audio and the returned idx refer to the video's
+    own frame numbers; the cache keys are the fingerprints of the pixels either way.
+    The kept frames are fingerprinted where they lie; only the frames the cache lacks run through the towers and the connector
+    (frames are independent through a3-a10) and are stored; the a5 similarities come from the cache or from the cached DINOv2
+    rows (tdc_pair_cossim), the refinement's precise values from the cache or from the pixels passed; the connector rows of the
+    kept frames are gathered out of the slab.  -> pixel_front's dict plus `cache_info()` (the info["cache"] entry, read after
     the compressor ran), or None when the call's frames exceed the budget (info["cache"] says bypassed; nothing stored).  The
     tower batches see the HBM the cache holds as taken (auto_tower_batch): the rate may change, not the bits."""
-    T0 = px_siglip.shape[0]
-    idx = frame_indices(e.cfg, T0, budget_text_len, frame_cap)                                      # a1
-    return front_cached_selected(e, cache, px_siglip, px_dino, idx, idx, T0, image_size, audio, video_index, info)
-
-
-def front_cached_selected(e, cache, px_siglip, px_dino, rows, idx, T0, image_size, audio=None, video_index=None, info=None):
-    """video_front_cached behind a1: the kept frames are the rows `rows` of px_siglip / px_dino and the frames idx of the
-    T0-frame video.  The pixel entry passes rows = idx (the pixels of all T0 frames); the frames entry
-    (video_front_from_frames) has resized only the kept frames and passes rows = 0 .. T-1.  Audio and the returned idx refer
-    to the video's own frame numbers; the cache keys are the fingerprints of the pixels either way."""
-    cfg = e.cfg
     cache.bind(e)
     T = len(idx)
     keys, dkeys = cache.frame_keys(e, px_siglip, px_dino, rows, image_size)
     before = cache.stats()
-    segmented = T > cfg.get("max_num_segments", 24) + 1
+    segs = segmented(e.cfg, T)
     early = {}
     # a3/a4, a6-a10 for the frames the cache lacks, a5 of the new frames' pairs enqueued BEFORE the SigLIP tower; a call whose
     # frames exceed the budget (known once the first frames fixed the row geometry) runs uncached
     new = encode_missing(e, cache, keys, px_siglip, px_dino, rows, image_size, lambda new, dino: early.update(
-        cache.early_sims(e, keys, dkeys, new, dino, segmented))) if cache.fits(keys) else None
+        cache.early_sims(e, keys, dkeys, new, dino, segs))) if cache.fits(keys) else None
     if new is None:
         if info is not None:
             info["cache"] = dict(bypassed=True, frames=T, frames_hit=0, frames_encoded=T, pairs_computed=0)
             if cache.kv_enabled:            # no frame keys to name an entry by: the compressor runs as without a store
                 info["cache"]["kv"] = dict(state="bypassed", frames=0, bytes=0)
         return None
-    if not segmented:                                                                               # a5
+    if not segs:                                                                                    # a5
         seg_idx = list(range(T))
     else:
         sims = cache.adjacent_sims(e, keys, dkeys, early)
@@ -697,11 +752,8 @@ def front_cached_selected(e, cache, px_siglip, px_dino, rows, idx, T0, image_siz
     N = cache.rows_per_frame
     final_size = cache.final_sizes(keys)
     kvs = None
-    if cache.kv_enabled:                    # the kept K/V of this selection: named by the frames' keys and, with audio, by
-        akey = None                         # what same_video_key compares of it
-        if audio is not None:
-            akey = (content_key(e, audio), tuple(sample_indicator(T0, idx, video_index)))
-        kvs = kv_store(cache, keys, image_size, akey)
+    if cache.kv_enabled:                    # the kept K/V of this selection: named by the frames' keys and its audio
+        kvs = kv_store(cache, keys, image_size, audio_key(e, audio, T0, idx, video_index))
     if audio is not None:                                                                           # a20
         audio = cached_audio(e, cache, audio, sample_indicator(T0, idx, video_index), T)
     f = dict(X=X, T=T, N=N, seg_idx=seg_idx, audio=audio, idx=idx, final_size=final_size,
@@ -714,8 +766,8 @@ def front_cached_selected(e, cache, px_siglip, px_dino, rows, idx, T0, image_siz
 def encode_video_cached(e, cache, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio=None,
                         frame_cap=224, splice=None, video_index=None, info=None):
     """encode_video_with(..., cache=cache): one video through a FrameCache (cache.py), bit for bit the uncached result"""
-    return encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio, frame_cap,
-                             None, splice, video_index, info, cache)
+    return encode_source(e, PixelSource(px_siglip, px_dino, image_size, cache), budget_text_len, n_text_tokens, prompt_ids,
+                         audio, frame_cap, None, splice, video_index, info)
 
 
 # ---- encode from stored tower features (features.FeatureSet; DESIGN.md section 13) ------------------------------------------
@@ -774,18 +826,28 @@ def gap_sims(e, dino, T0, G, sims=None):
 
 
 def export_features_with(e, px_siglip, px_dino, image_size, store="f16", gaps=None):
-    """a3 / a4 of EVERY input frame (no a1: it reads the prompt length and the cap) -> features.FeatureSet.  The towers run as
-    in towers_and_selection: SigLIP on the side stream under `two_streams`, after the DINOv2 tower otherwise.
+    """a3 / a4 of EVERY input frame (no a1: it reads the prompt length and the cap; both_towers) -> features.FeatureSet.
     store="e4m3": the compact set (compact_rows) - the bytes compact_features_with makes of the lossless set.  gaps (compact
     sets; resolve_gaps): the set also carries the similarities across that many frame gaps."""
-    from .features import FeatureSet, tower_signature
     check_store(store, gaps)
     T0 = px_siglip.shape[0]
     if px_dino.shape[0] != T0 or T0 < 1:
         raise ValueError("export_features: %d SigLIP and %d DINOv2 frames" % (T0, px_dino.shape[0]))
+    sig, dino = both_towers(e, px_siglip, px_dino)
+    return feature_set_of(e, sig, dino, T0, image_size, store, gaps)
+
+
+def both_towers(e, px_siglip, px_dino):
+    """a3 / a4 with no selection between them -> (SigLIP rows, DINOv2 rows): SigLIP on the side stream under `two_streams`,
+    after the DINOv2 tower otherwise"""
     side_sig = start_side_tower(e, px_siglip)
     dino = e.tower("dino", px_dino)                                                                 # a4
-    sig = join_side_tower(e, side_sig, px_siglip)                                                   # a3
+    return join_side_tower(e, side_sig, px_siglip), dino                                            # a3
+
+
+def feature_set_of(e, sig, dino, T0, image_size, store="f16", gaps=None):
+    """the tower rows of ALL T0 frames -> the FeatureSet an export returns: lossless, or compact (compact_rows)"""
+    from .features import FeatureSet, tower_signature
     if store == "e4m3":
         return compact_rows(e, sig, dino, T0, image_size, tower_signature(e), gaps)
     return FeatureSet(stored_rows(e, "siglip", sig, T0), stored_rows(e, "dino", dino, T0), image_size, tower_signature(e))
@@ -860,86 +922,92 @@ def feature_rows(e, fs, idx=None):
     return out
 
 
-def video_front_from_features(e, fs, budget_text_len, audio=None, frame_cap=224, video_index=None, info=None,
-                              check_signature=True):
-    """video_front_with from the stored tower rows of a video (features.FeatureSet) instead of its pixels: a1, the kept
-    frames' rows gathered, a5 by the pixel path's launch on the gathered DINOv2 rows, then front_after_towers -> the same dict,
-    the same bits.  A compact set: a5 ranks the stored similarities of the ORIGINAL rows wherever the set holds every gap between
-    neighbouring kept frames (features.stored_sims: every frame kept, or a gap table - section 16), else those of the decoded
-    rows; info["selection_sims"] says which.  The selection refinement needs pixels: under engine.selection_eps a non-empty band is ranked on the stored
-    similarities and reported as info["refine_unavailable_pairs"] (select_segments_with, refine=None)."""
-    from .features import is_compact, stored_sims
-    if check_signature:
-        check_features(e, fs)
-    cfg = e.cfg
-    T0 = fs.frames
-    idx = frame_indices(cfg, T0, budget_text_len, frame_cap)                                        # a1
-    T = len(idx)
-    sig, dino = feature_rows(e, fs, idx)
-    compact = is_compact(fs)
-    if T > cfg.get("max_num_segments", 24) + 1:                                                     # a5
-        # the similarities of the ORIGINAL 16-bit rows, stored with the set: every frame kept (gap 1), or sub-sampled within
-        # the set's gap table - no launch, and the lossless path's selection bit for bit
-        sims = stored = stored_sims(fs, idx) if compact else None
-        if sims is None:
-            sims_dev = e.sims_tensor(dino, T)
-            ev = e.mark() if hasattr(e, "mark") and sims_dev.is_cuda else None
-            sims = e.fetch(sims_dev, ev) if ev is not None else sims_dev.tolist()
-        if compact and info is not None:
-            info["selection_sims"] = "stored" if stored is not None else "decoded"
-        seg_idx = select_segments_with(e, sims, None, info)
-    else:
-        seg_idx = list(range(T))
-    return front_after_towers(e, sig, dino, seg_idx, T0, idx, fs.image_size, audio, None, video_index)
+class FeatureSource:
+    """the stored tower rows of a video (features.FeatureSet) as an encode's source (PixelSource documents the members).
+    check_signature: the set's signature is compared with the engine's towers (check_features) once, before the first rows are
+    read"""
+
+    def __init__(self, fs, check_signature=True):
+        self.fs, self.unchecked = fs, check_signature
+        self.T0, self.image_size = fs.frames, fs.image_size
+
+    def check(self, e):
+        if self.unchecked:
+            check_features(e, self.fs)
+            self.unchecked = False
+
+    def front(self, e, idx, audio=None, video_index=None, info=None, keep=None):
+        """pixel_front from the stored rows instead of pixels: the kept frames' rows gathered, a5 by the pixel path's launch on
+        the gathered DINOv2 rows, then front_after_towers -> the same dict, the same bits.  A compact set: a5 ranks the stored
+        similarities of the ORIGINAL rows wherever the set holds every gap between neighbouring kept frames
+        (features.stored_sims: every frame kept, or a gap table - section 16), else those of the decoded rows;
+        info["selection_sims"] says which.  The selection refinement needs pixels: under engine.selection_eps a non-empty band is
+        ranked on the stored similarities and reported as info["refine_unavailable_pairs"] (select_segments_with,
+        refine=None)."""
+        from .features import is_compact, stored_sims
+        self.check(e)
+        fs, T = self.fs, len(idx)
+        sig, dino = feature_rows(e, fs, idx)
+        compact = is_compact(fs)
+        if segmented(e.cfg, T):                                                                     # a5
+            # the similarities of the ORIGINAL 16-bit rows, stored with the set: every frame kept (gap 1), or sub-sampled within
+            # the set's gap table - no launch, and the lossless path's selection bit for bit
+            sims = stored = stored_sims(fs, idx) if compact else None
+            if sims is None:
+                sims_dev = e.sims_tensor(dino, T)
+                ev = e.mark() if hasattr(e, "mark") and sims_dev.is_cuda else None
+                sims = e.fetch(sims_dev, ev) if ev is not None else sims_dev.tolist()
+            if compact and info is not None:
+                info["selection_sims"] = "stored" if stored is not None else "decoded"
+            seg_idx = select_segments_with(e, sims, None, info)
+        else:
+            seg_idx = list(range(T))
+        return front_after_towers(e, sig, dino, seg_idx, self.T0, idx, fs.image_size, audio, keep, video_index)
+
+    def image(self, e, info=None):
+        if self.T0 != 1:
+            raise ValueError("image=True takes a one-frame feature set, got %d frames" % self.T0)
+        self.check(e)
+        sig, dino = feature_rows(e, self.fs)
+        X, sizes = e.connector(sig, dino, 1, [tuple(self.image_size)])
+        if info is not None:
+            info["final_size"] = sizes
+        return X
+
+    def same_key(self, e, idx, audio=None, video_index=None):
+        """same_source_key behind a1: the content of both feature tensors (content_key), image_size, the a1 selection and the
+        audio; a compact set: its scales too, and its gap table (a set with one selects on other similarities than a set
+        without)"""
+        from .features import is_compact
+        fs = self.fs
+        akey = audio_key(e, audio, self.T0, idx, video_index)
+        key = (content_key(e, fs.siglip), content_key(e, fs.dino), tuple(fs.image_size), tuple(idx), akey)
+        if is_compact(fs):                      # the same bytes under other scales are other rows
+            key += (content_key(e, fs.siglip_scale), content_key(e, fs.dino_scale), str(fs.rows_dtype))
+            if getattr(fs, "gap_sims", None) is not None:
+                key += (content_key(e, fs.gap_sims),)
+        return key
 
 
 def encode_features_with(e, fs, budget_text_len, n_text_tokens, prompt_ids, audio=None, frame_cap=224, splice=None,
                          video_index=None, info=None, check_signature=True, image=False):
     """encode_video_with from a FeatureSet: bit for bit its result for the pixels the set was exported from, whenever that
-    call refines nothing.  image=True (a one-frame set): the connector rows [:, :H] of the image, as
-    prepare_inputs_labels_for_multimodal's image branch (info receives final_size)."""
-    if image:
-        if fs.frames != 1:
-            raise ValueError("image=True takes a one-frame feature set, got %d frames" % fs.frames)
-        if check_signature:
-            check_features(e, fs)
-        sig, dino = feature_rows(e, fs)
-        X, sizes = e.connector(sig, dino, 1, [tuple(fs.image_size)])
-        if info is not None:
-            info["final_size"] = sizes
-        return X[:, :e.H]
-    f = video_front_from_features(e, fs, budget_text_len, audio, frame_cap, video_index, info, check_signature)
-    return encode_front(e, f, n_text_tokens, prompt_ids, None, splice, info)
+    call refines nothing.  image=True (a one-frame set): the connector rows [:, :H] of the image (info receives final_size)."""
+    return encode_source(e, FeatureSource(fs, check_signature), budget_text_len, n_text_tokens, prompt_ids, audio, frame_cap,
+                         None, splice, video_index, info, image)
 
 
 def encode_features_prompts_with(e, fs, prompts, audio=None, frame_cap=224, video_index=None, infos=None, max_prompts=8,
                                  pad_fraction=0.25, check_signature=True):
     """encode_video_prompts_with from a FeatureSet: the front from features once per distinct a1 selection, the selection's
     prompts through compress_many_with -> one result per prompt, bit for bit encode_features_with's"""
-    if check_signature:
-        check_features(e, fs)
-
-    def front(btl, finfo):
-        return video_front_from_features(e, fs, btl, audio, frame_cap, video_index, finfo, False)
-    return prompts_over_fronts(e, fs.frames, prompts, front, frame_cap, infos, max_prompts, pad_fraction)
+    return encode_source_prompts(e, FeatureSource(fs, check_signature), prompts, audio, frame_cap, video_index, infos,
+                                 max_prompts, pad_fraction)
 
 
 def same_features_key(e, fs, budget_text_len, frame_cap, audio=None, video_index=None):
-    """`config.tdc_batch_prompts` over feature inputs: what two samples must share to be questions about the SAME stored
-    video - the content of both feature tensors (content_key), image_size, the a1 selection, and their audio as
-    same_video_key compares it; a compact set: its scales too, and its gap table (a set with one selects on other similarities
-    than a set without)"""
-    from .features import is_compact
-    idx = frame_indices(e.cfg, fs.frames, budget_text_len, frame_cap)
-    akey = None
-    if audio is not None:
-        akey = (content_key(e, audio), tuple(sample_indicator(fs.frames, idx, video_index)))
-    key = (content_key(e, fs.siglip), content_key(e, fs.dino), tuple(fs.image_size), tuple(idx), akey)
-    if is_compact(fs):                      # the same bytes under other scales are other rows
-        key += (content_key(e, fs.siglip_scale), content_key(e, fs.dino_scale), str(fs.rows_dtype))
-        if getattr(fs, "gap_sims", None) is not None:
-            key += (content_key(e, fs.gap_sims),)
-    return key
+    """same_source_key of a stored video"""
+    return same_source_key(e, FeatureSource(fs), budget_text_len, frame_cap, audio, video_index)
 
 
 # ---- encode from decoded uint8 frames: select, then resize what runs (DESIGN.md section 15) ----------------------------------
@@ -954,50 +1022,44 @@ def frames_size(frames, image_size=None):
     return int(shape[0]), (tuple(image_size) if image_size is not None else (int(shape[1]), int(shape[2])))
 
 
-def video_front_from_frames(e, frames, image_size, budget_text_len, audio=None, frame_cap=224, video_index=None, info=None,
-                            cache=None):
-    """video_front from the decoded frames of a video (uint8 [T0, H, W, 3]) instead of its pixels: a1 FIRST, on the frame
-    count alone, then only the kept frames are resized and normalised (engine.pixels_from_frames), then the pixel front's
-    towers_and_selection and front_after_towers with T0 and idx handed over as video_front_with hands them - the same
-    launches on the same operands, so the same dict and the same bits as the pixel front on process_images of ALL frames.
-    Audio and info["frame_indices"] refer to the video's own frame numbers.  cache: the kept pixels go through
-    front_cached_selected (a1 is not run again on the selected set); the keys are the pixel fingerprints, so a video asked
-    first through pixels hits here.  info gains frames_in = T0 and frames_resized = len(idx)."""
-    cfg = e.cfg
-    T0, image_size = frames_size(frames, image_size)
-    idx = frame_indices(cfg, T0, budget_text_len, frame_cap)                                        # a1
-    T = len(idx)
-    px_siglip, px_dino = e.pixels_from_frames(frames, idx)
-    if info is not None:
-        info.update(frames_in=T0, frames_resized=T)
-    if cache is not None:
-        f = front_cached_selected(e, cache, px_siglip, px_dino, list(range(T)), idx, T0, image_size, audio, video_index, info)
-        if f is not None:
-            return f
-    sig, dino, (seg_idx,) = towers_and_selection(e, px_siglip, px_dino, [(0, T, T > cfg.get("max_num_segments", 24) + 1)],
-                                                 None if info is None else [info])                  # a3-a5
-    return front_after_towers(e, sig, dino, seg_idx, T0, idx, image_size, audio, None, video_index)
+class FrameSource:
+    """the decoded frames of a video (uint8 [T0, H, W, 3]) as an encode's source (PixelSource documents the members): a1 has
+    run FIRST, on the frame count alone, and only the kept frames are resized and normalised (engine.pixels_from_frames).
+    image_size defaults to the frames' (H, W); frames of another shape raise here, before any engine call."""
+
+    def __init__(self, frames, image_size=None, cache=None):
+        self.frames, self.cache = frames, cache
+        self.T0, self.image_size = frames_size(frames, image_size)
+
+    def front(self, e, idx, audio=None, video_index=None, info=None, keep=None):
+        """the kept frames' pixels (rows 0 .. T-1), then pixel_front with T0 and idx handed over as PixelSource hands them - the
+        same launches on the same operands, so the same dict and the same bits as the pixel front on process_images of ALL
+        frames.  Audio and info["frame_indices"] refer to the video's own frame numbers.  The cache keys are the pixel
+        fingerprints, so a video asked first through pixels hits here.  info gains frames_in = T0 and frames_resized =
+        len(idx)."""
+        T = len(idx)
+        px_siglip, px_dino = e.pixels_from_frames(self.frames, idx)
+        if info is not None:
+            info.update(frames_in=self.T0, frames_resized=T)
+        return pixel_front(e, self.cache, px_siglip, px_dino, list(range(T)), idx, self.T0, self.image_size, audio, keep,
+                           video_index, info)
+
+    def image(self, e, info=None):
+        if self.T0 != 1:
+            raise ValueError("image=True takes one frame, got %d" % self.T0)
+        px_siglip, px_dino = e.pixels_from_frames(self.frames, None)
+        X, sizes = image_rows(e, px_siglip, px_dino, self.image_size, self.cache)
+        if info is not None:
+            info.update(final_size=sizes, frames_in=1, frames_resized=1)
+        return X
 
 
 def encode_frames_with(e, frames, budget_text_len, n_text_tokens, prompt_ids, audio=None, frame_cap=224, splice=None,
                        video_index=None, info=None, cache=None, image_size=None, image=False):
     """encode_video_with from decoded frames: bit for bit its result on process_images of the same frames.  image=True (one
-    frame): the connector rows [:, :H] of the image, as prepare_inputs_labels_for_multimodal's image branch (through the
-    cache when one is given; info receives final_size)."""
-    if image:
-        T0, image_size = frames_size(frames, image_size)
-        if T0 != 1:
-            raise ValueError("image=True takes one frame, got %d" % T0)
-        px_siglip, px_dino = e.pixels_from_frames(frames, None)
-        if cache is not None:
-            X, sizes = encode_image_cached(e, cache, px_siglip, px_dino, image_size)
-        else:
-            X, sizes = e.connector(e.tower("siglip", px_siglip), e.tower("dino", px_dino), 1, [tuple(image_size)])
-        if info is not None:
-            info.update(final_size=sizes, frames_in=1, frames_resized=1)
-        return X[:, :e.H]
-    f = video_front_from_frames(e, frames, image_size, budget_text_len, audio, frame_cap, video_index, info, cache)
-    return encode_front(e, f, n_text_tokens, prompt_ids, None, splice, info)
+    frame): the connector rows [:, :H] of the image (through the cache when one is given; info receives final_size)."""
+    return encode_source(e, FrameSource(frames, image_size, cache), budget_text_len, n_text_tokens, prompt_ids, audio,
+                         frame_cap, None, splice, video_index, info, image)
 
 
 def encode_frames_prompts_with(e, frames, prompts, audio=None, frame_cap=224, video_index=None, infos=None, cache=None,
@@ -1005,18 +1067,14 @@ def encode_frames_prompts_with(e, frames, prompts, audio=None, frame_cap=224, vi
     """encode_video_prompts_with from decoded frames: the front from frames once per distinct a1 selection (each resizes its
     own kept frames), the selection's prompts through compress_many_with -> one result per prompt, bit for bit
     encode_frames_with's"""
-    T0, image_size = frames_size(frames, image_size)
-
-    def front(btl, finfo):
-        return video_front_from_frames(e, frames, image_size, btl, audio, frame_cap, video_index, finfo, cache)
-    return prompts_over_fronts(e, T0, prompts, front, frame_cap, infos, max_prompts, pad_fraction)
+    return encode_source_prompts(e, FrameSource(frames, image_size, cache), prompts, audio, frame_cap, video_index, infos,
+                                 max_prompts, pad_fraction)
 
 
 def export_features_from_frames_with(e, frames, store="f16", image_size=None, slab=None, gaps=None):
     """export_features_with from decoded frames: EVERY frame (no a1), preprocessed and run through both towers `slab` frames
     at a time (default EXPORT_FRAMES_SLAB), the rows concatenated.  Tower rows do not depend on the tower batch, so the set equals
     export_features_with(*process_images(frames)) bit for bit - without the pixels of all T0 frames ever existing."""
-    from .features import FeatureSet, tower_signature
     check_store(store, gaps)
     T0, image_size = frames_size(frames, image_size)
     slab = EXPORT_FRAMES_SLAB if slab is None else int(slab)
@@ -1024,12 +1082,9 @@ def export_features_from_frames_with(e, frames, store="f16", image_size=None, sl
         raise ValueError("export_features: slab must be a positive frame count, got %r" % (slab,))
     sigs, dinos = [], []
     for s in range(0, T0, slab):
-        px_siglip, px_dino = e.pixels_from_frames(frames, list(range(s, min(s + slab, T0))))
-        side_sig = start_side_tower(e, px_siglip)
-        dinos.append(e.tower("dino", px_dino))                                                      # a4
-        sigs.append(join_side_tower(e, side_sig, px_siglip))                                        # a3
+        sig, dino = both_towers(e, *e.pixels_from_frames(frames, list(range(s, min(s + slab, T0)))))
+        sigs.append(sig)
+        dinos.append(dino)
     sig = sigs[0] if len(sigs) == 1 else torch.cat(sigs, 0)
     dino = dinos[0] if len(dinos) == 1 else torch.cat(dinos, 0)
-    if store == "e4m3":
-        return compact_rows(e, sig, dino, T0, image_size, tower_signature(e), gaps)
-    return FeatureSet(stored_rows(e, "siglip", sig, T0), stored_rows(e, "dino", dino, T0), image_size, tower_signature(e))
+    return feature_set_of(e, sig, dino, T0, image_size, store, gaps)

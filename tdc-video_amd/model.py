@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import lib as L
 from . import segment as seg
-from .encode import batch_groups, encode_image_cached, frame_indices, same_features_key, same_video_key
+from .encode import FeatureSource, FrameSource, PixelSource, batch_groups, encode_source, frame_indices, same_source_key
 from .features import FeatureSet, is_feature_set
 from .pipeline import VideoEncoder
 
@@ -736,7 +736,6 @@ class CambrianMetaForCausalLM(ABC):
         pad_fraction = model.tdc_prompt_pad_fraction()
         cfgd = self._cfg()
         K = cfgd.get("context_token_num", 16)
-        H = model.config.hidden_size
         if feature_inputs or frame_inputs:
             is_video = isinstance(images[0], (list, tuple))
         else:
@@ -752,17 +751,33 @@ class CambrianMetaForCausalLM(ABC):
         final_size = []
 
         def facts(i):
-            """the host-side facts of sample i: pixels, text lengths, prompt ids, audio, a21 hand-off, frame cap"""
+            """the host-side facts of sample i: its source (encode.py: what its frames are read from) with the engine's entries
+            for that input kind, text lengths, prompt ids, audio, a21 hand-off, frame cap"""
             if feature_inputs:
-                vid_s, vid_d = feature_sets[i], None
+                # config.tdc_feature_inputs: the towers ran when the set was exported (a set made of bare tensors carries no
+                # signature to compare)
+                fs = feature_sets[i]
+                src, side_stream = FeatureSource(fs), False
+                kw = dict(check_signature=fs.signature is not None)
+                entry = lambda *a, **k: eng.encode_features(fs, *a, **kw, **k)
+                entry_prompts = lambda qs, **k: eng.encode_features_prompts(fs, qs, **kw, **k)
             elif frame_inputs:
-                vid_s, vid_d = (images[0][i] if is_video else images[0][i:i + 1]), None
-            elif is_video:
-                vid_s, vid_d = images[0][i], images[1][i]
+                # config.tdc_frame_inputs: a1 first, then only the kept frames are uploaded and resized
+                kw = dict(cache=vcache, image_size=None if image_sizes is None else tuple(image_sizes[i]))
+                src, side_stream = FrameSource(images[0][i] if is_video else images[0][i:i + 1], **kw), True
+                entry, entry_prompts = (lambda *a, **k: eng.encode_frames(src.frames, *a, **kw, **k)), None
+            else:
+                vid_s, vid_d = (images[0][i], images[1][i]) if is_video else (images[0][i:i + 1], images[1][i:i + 1])
                 if vid_s.ndim == 3:
                     vid_s, vid_d = vid_s.unsqueeze(0), vid_d.unsqueeze(0)
-            else:
-                vid_s, vid_d = images[0][i:i + 1], images[1][i:i + 1]
+                src, side_stream = PixelSource(vid_s, vid_d, tuple(image_sizes[i]), vcache), True
+                kw = {} if vcache is None else {"cache": vcache}                  # config.tdc_video_cache_bytes
+                px = lambda: (vid_s.to(eng.dev), vid_d.to(eng.dev), src.image_size)      # uploaded when the sample is encoded
+                if is_video:
+                    entry = lambda *a, **k: eng.encode_video(*px(), *a, **kw, **k)
+                else:       # single images: every image is a static frame, no segmentation / Q-Former (cambrian_arch.py:980-983)
+                    entry = lambda *a, **k: encode_source(eng, PixelSource(*px(), vcache), *a, **k)
+                entry_prompts = lambda qs, **k: eng.encode_video_prompts(*px(), qs, **kw, **k)
             cur_ids = ids_host[i]
             if mask_host is not None:
                 cur_ids = cur_ids[mask_host[i] | (cur_ids == IMAGE_TOKEN_INDEX)]
@@ -789,7 +804,8 @@ class CambrianMetaForCausalLM(ABC):
                         and audio.get("audio_tokens") is None:
                     # the reference's own audio dict (cambrian_arch.py:1547): raw waveform -> BEATs on the device
                     eng.beats = model.tdc_beats()
-            f = dict(i=i, vid_s=vid_s, vid_d=vid_d, n_text=n_text, prompt_ids=prompt_ids, audio=audio, splice=None)
+            f = dict(i=i, src=src, entry=entry, entry_prompts=entry_prompts, side_stream=side_stream, n_text=n_text,
+                     prompt_ids=prompt_ids, audio=audio, splice=None)
             if is_video:
                 # a21 hand-off: when embed_tokens lives on the engine device in the engine dtype the
                 # emission gather also fetches the text embeddings and writes the inputs_embeds rows directly
@@ -809,69 +825,40 @@ class CambrianMetaForCausalLM(ABC):
 
         def encode_one(f):
             """sample f through the engine on its own -> (visual tokens, spliced, final sizes)"""
-            i, vid_s, vid_d, n_text, prompt_ids, audio, splice = (f[k] for k in ("i", "vid_s", "vid_d", "n_text", "prompt_ids",
-                                                                                  "audio", "splice"))
+            src, n_text, prompt_ids, audio, splice = (f[k] for k in ("src", "n_text", "prompt_ids", "audio", "splice"))
             keep = {}
-            if feature_inputs:
-                # config.tdc_feature_inputs: the towers ran when the set was exported (a set made of bare tensors carries no
-                # signature to compare)
-                kw = dict(info=keep, check_signature=vid_s.signature is not None)
-                if is_video:
-                    vis = eng.encode_features(vid_s, f["btl"], n_text, prompt_ids, audio=audio, frame_cap=f["cap"], splice=splice,
-                                              video_index=f["vindex"], **kw)
-                else:
-                    vis = eng.encode_features(vid_s, None, n_text, None, image=True, **kw)
-            elif frame_inputs:
-                # config.tdc_frame_inputs: a1 first, then only the kept frames are uploaded and resized
-                kw = dict(info=keep, cache=vcache, image_size=None if image_sizes is None else tuple(image_sizes[i]))
-                if is_video:
-                    eng.two_streams = model.tdc_side_stream(min(len(vid_s), f["cap"]))
-                    vis = eng.encode_frames(vid_s, f["btl"], n_text, prompt_ids, audio=audio, frame_cap=f["cap"], splice=splice,
-                                            video_index=f["vindex"], **kw)
-                else:
-                    vis = eng.encode_frames(vid_s, None, n_text, None, image=True, **kw)
-            elif is_video:
-                vindex, cap, btl, sharded = f["vindex"], f["cap"], f["btl"], f["sharded"]
-                if sharded is not None:
-                    # config.tdc_shard_frames under an initialised torch.distributed (one process per GPU, every rank called
-                    # with the same video - how the reference's eval drivers start their workers, eval/eval_mlvu.py:129-157 -
-                    # but here the ranks split the FRAMES of the one video): this rank encodes frames [lo, hi) of the a1
-                    # selection, dist.ShardedVideoEncoder exchanges what crosses the rank boundaries and all-gathers the
-                    # emitted tokens, so every rank returns the same 10-tuple as the serial path, bit for bit.  The serial frame
-                    # cache (config.tdc_video_cache_bytes) is not used here; config.tdc_shard_cache_bytes gives each rank a
-                    # cache of its own frames (tdc_shard_cache)
-                    fp = sharded.frame_plan(vid_s.shape[0], btl, cap, vindex)
-                    eng.two_streams = model.tdc_side_stream(fp["hi"] - fp["lo"])
-                    sel_s = torch.as_tensor(fp["siglip_frames"], dtype=torch.long, device=vid_s.device)
-                    sel_d = torch.as_tensor(fp["dino_frames"], dtype=torch.long, device=vid_d.device)
-                    vis = sharded.encode_video(vid_s[sel_s].to(eng.dev), vid_d[sel_d].to(eng.dev), fp["T"],
-                                               tuple(image_sizes[i]), n_text, prompt_ids, audio=audio,
-                                               sample_indices=fp["sample_indices"], cache=model.tdc_shard_cache(), info=keep)
-                    keep["final_size"] = [seg.unpad_newline_map(eng.side, tuple(image_sizes[i]), 0)[1]] * fp["T"]
-                    splice = None
-                else:
-                    eng.two_streams = model.tdc_side_stream(min(vid_s.shape[0], cap))
-                    cached = {} if vcache is None else {"cache": vcache}          # config.tdc_video_cache_bytes
-                    vis = eng.encode_video(vid_s.to(eng.dev), vid_d.to(eng.dev), tuple(image_sizes[i]),
-                                           budget_text_len=btl, n_text_tokens=n_text, prompt_ids=prompt_ids, audio=audio,
-                                           frame_cap=cap, info=keep, splice=splice, video_index=vindex, **cached)
+            if not is_video:
+                vis = f["entry"](None, n_text, None, image=True, info=keep)
+            elif f["sharded"] is not None:
+                # config.tdc_shard_frames under an initialised torch.distributed (one process per GPU, every rank called
+                # with the same video - how the reference's eval drivers start their workers, eval/eval_mlvu.py:129-157 -
+                # but here the ranks split the FRAMES of the one video): this rank encodes frames [lo, hi) of the a1
+                # selection, dist.ShardedVideoEncoder exchanges what crosses the rank boundaries and all-gathers the
+                # emitted tokens, so every rank returns the same 10-tuple as the serial path, bit for bit.  The serial frame
+                # cache (config.tdc_video_cache_bytes) is not used here; config.tdc_shard_cache_bytes gives each rank a
+                # cache of its own frames (tdc_shard_cache)
+                vid_s, vid_d = src.px_siglip, src.px_dino
+                fp = f["sharded"].frame_plan(src.T0, f["btl"], f["cap"], f["vindex"])
+                eng.two_streams = model.tdc_side_stream(fp["hi"] - fp["lo"])
+                sel_s = torch.as_tensor(fp["siglip_frames"], dtype=torch.long, device=vid_s.device)
+                sel_d = torch.as_tensor(fp["dino_frames"], dtype=torch.long, device=vid_d.device)
+                vis = f["sharded"].encode_video(vid_s[sel_s].to(eng.dev), vid_d[sel_d].to(eng.dev), fp["T"], src.image_size,
+                                                n_text, prompt_ids, audio=audio, sample_indices=fp["sample_indices"],
+                                                cache=model.tdc_shard_cache(), info=keep)
+                keep["final_size"] = [seg.unpad_newline_map(eng.side, src.image_size, 0)[1]] * fp["T"]
+                splice = None
             else:
-                # single images: every image is a static frame, no segmentation / Q-Former (cambrian_arch.py:980-983)
-                if vcache is not None:
-                    X, sizes = encode_image_cached(eng, vcache, vid_s.to(eng.dev), vid_d.to(eng.dev), tuple(image_sizes[i]))
-                else:
-                    sig = eng.tower("siglip", vid_s.to(eng.dev))
-                    dino = eng.tower("dino", vid_d.to(eng.dev))
-                    X, sizes = eng.connector(sig, dino, 1, [tuple(image_sizes[i])])
-                vis = X[:, :H]
-                keep["final_size"] = sizes
+                if f["side_stream"]:
+                    eng.two_streams = model.tdc_side_stream(min(src.T0, f["cap"]))
+                vis = f["entry"](f["btl"], n_text, prompt_ids, audio=audio, frame_cap=f["cap"], splice=splice,
+                                 video_index=f["vindex"], info=keep)
             return vis, splice is not None, keep["final_size"]
 
         def encode_group(fs, n_frames):
             """config.tdc_batch_frames: the samples fs in one tower and connector pass (VideoEncoder.encode_batch) -> what
             encode_one returns for each, bit for bit"""
             infos = [{} for _ in fs]
-            samples = [dict(px_siglip=f["vid_s"], px_dino=f["vid_d"], image_size=tuple(image_sizes[f["i"]]),
+            samples = [dict(px_siglip=f["src"].px_siglip, px_dino=f["src"].px_dino, image_size=f["src"].image_size,
                             image=not is_video, budget_text_len=f.get("btl"), n_text_tokens=f["n_text"], prompt_ids=f["prompt_ids"],
                             audio=f["audio"], video_index=f.get("vindex"), splice=f["splice"]) for f in fs]
             eng.two_streams = model.tdc_side_stream(n_frames)
@@ -879,22 +866,17 @@ class CambrianMetaForCausalLM(ABC):
             return [(v, f["splice"] is not None, info["final_size"]) for v, f, info in zip(vis, fs, infos)]
 
         def encode_prompts(fs):
-            """config.tdc_batch_prompts: the samples fs carry ONE video (same_video_key) - the towers and the connector once, one
-            compressor pass per group of prompts (VideoEncoder.encode_video_prompts) -> what encode_one returns for each, bit
+            """config.tdc_batch_prompts: the samples fs carry ONE video (same_source_key) - its front once, one compressor pass
+            per group of prompts (the engine's multi-prompt entry for the input kind) -> what encode_one returns for each, bit
             for bit"""
             f0 = fs[0]
             infos = [{} for _ in fs]
             qs = [dict(budget_text_len=f["btl"], n_text_tokens=f["n_text"], prompt_ids=f["prompt_ids"], splice=f["splice"])
                   for f in fs]
-            if feature_inputs:
-                vis = eng.encode_features_prompts(f0["vid_s"], qs, audio=f0["audio"], frame_cap=f0["cap"],
-                                                  video_index=f0["vindex"], infos=infos, max_prompts=batch_prompts,
-                                                  pad_fraction=pad_fraction, check_signature=f0["vid_s"].signature is not None)
-                return [(v, f["splice"] is not None, info["final_size"]) for v, f, info in zip(vis, fs, infos)]
-            eng.two_streams = model.tdc_side_stream(min(f0["vid_s"].shape[0], f0["cap"]))
-            vis = eng.encode_video_prompts(f0["vid_s"].to(eng.dev), f0["vid_d"].to(eng.dev), tuple(image_sizes[f0["i"]]), qs,
-                                           audio=f0["audio"], frame_cap=f0["cap"], video_index=f0["vindex"], infos=infos,
-                                           cache=vcache, max_prompts=batch_prompts, pad_fraction=pad_fraction)
+            if f0["side_stream"]:
+                eng.two_streams = model.tdc_side_stream(min(f0["src"].T0, f0["cap"]))
+            vis = f0["entry_prompts"](qs, audio=f0["audio"], frame_cap=f0["cap"], video_index=f0["vindex"], infos=infos,
+                                      max_prompts=batch_prompts, pad_fraction=pad_fraction)
             return [(v, f["splice"] is not None, info["final_size"]) for v, f, info in zip(vis, fs, infos)]
 
         if batch_prompts and bsz > 1 and is_video:
@@ -903,12 +885,7 @@ class CambrianMetaForCausalLM(ABC):
             fs = [facts(i) for i in range(bsz)]
             same = {}
             for f in fs:
-                if feature_inputs:
-                    key = same_features_key(eng, f["vid_s"], f["btl"], f["cap"], f["audio"], f["vindex"])
-                else:
-                    key = same_video_key(eng, f["vid_s"], f["vid_d"], tuple(image_sizes[f["i"]]), f["btl"], f["cap"], f["audio"],
-                                         f["vindex"])
-                same.setdefault(key, []).append(f)
+                same.setdefault(same_source_key(eng, f["src"], f["btl"], f["cap"], f["audio"], f["vindex"]), []).append(f)
             results = [None] * bsz
             for members in same.values():
                 rs = [encode_one(members[0])] if len(members) == 1 else encode_prompts(members)
@@ -920,9 +897,8 @@ class CambrianMetaForCausalLM(ABC):
             # config.tdc_batch_frames: every sample's host-side facts first (the same exceptions as the loop above, raised
             # before any encode), then the groups of batch_groups in sample order; a group of one runs encode_one
             fs = [facts(i) for i in range(bsz)]
-            fr = [len(frame_indices(eng.cfg, f["vid_s"].shape[0], f["btl"], f["cap"])) if is_video else 1 for f in fs]
-            geo = [(tuple(f["vid_s"].shape[1:]), f["vid_s"].dtype, f["vid_s"].device, tuple(f["vid_d"].shape[1:]),
-                    f["vid_d"].dtype, f["vid_d"].device) for f in fs]
+            fr = [len(frame_indices(eng.cfg, f["src"].T0, f["btl"], f["cap"])) if is_video else 1 for f in fs]
+            geo = [tuple((tuple(px.shape[1:]), px.dtype, px.device) for px in (f["src"].px_siglip, f["src"].px_dino)) for f in fs]
             results = []
             for g in batch_groups(fr, batch_frames, geo):
                 results += [encode_one(fs[g[0]])] if len(g) == 1 else encode_group([fs[i] for i in g], sum(fr[i] for i in g))

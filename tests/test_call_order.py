@@ -42,12 +42,12 @@ def _describe(a):
     return "callable" if callable(a) else type(a).__name__
 
 
-def record(eng, log):
-    """the recording proxy: every engine-protocol method of `eng` logs (name, arguments, keyword arguments) before it runs;
-    mark / fetch are supplied (the doubles have none) and sims_tensor's result counts as a device tensor"""
+def record(eng, log, names=RECORDED):
+    """the recording proxy: every engine-protocol method of `eng` among `names` logs (name, arguments, keyword arguments)
+    before it runs; mark / fetch are supplied (the doubles have none) and sims_tensor's result counts as a device tensor"""
     eng.mark = lambda: "event"
     eng.fetch = lambda t, ev: t.tolist()
-    for name in RECORDED:
+    for name in names:
         fn = getattr(eng, name, None)
         if fn is None:
             continue
@@ -195,9 +195,8 @@ def test_the_fixture_holds_every_case(logs):
     assert sorted(logs) == sorted(WANT)
 
 
-@pytest.mark.parametrize("case", sorted(WANT))
-def test_call_order(logs, case):
-    got, want = logs[case], WANT[case]
+def assert_same_log(case, got, want):
+    """one case's log against the fixture's (a dict: one log per rank), naming the first call that differs"""
     if isinstance(want, dict):
         assert sorted(got) == sorted(want)
         for rank in sorted(want):
@@ -207,6 +206,11 @@ def test_call_order(logs, case):
     else:
         assert got == want, "%s: first difference at call %d" % (
             case, next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want))))
+
+
+@pytest.mark.parametrize("case", sorted(WANT))
+def test_call_order(logs, case):
+    assert_same_log(case, logs[case], WANT[case])
 
 
 def test_siglip_is_enqueued_before_the_host_read(logs):
