@@ -85,21 +85,29 @@ __device__ __forceinline__ f32x4 mma128_fp8(V8 a0, V8 a1, V8 b0, V8 b1, f32x4 c)
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
-// erf(x) by Abramowitz-Stegun 7.1.26 (|abs error| <= 1.5e-7, i.e. below fp32 round-off of the surrounding math)
-__device__ __forceinline__ float erf_as(float x) {
-    const float ax = fabsf(x);
-    const float t = fast_rcp(__builtin_fmaf(0.3275911f, ax, 1.0f));
+// nn.GELU() / ACT2FN["gelu"]: 0.5 x (1 + erf(x / sqrt(2))).  erfc(|z|) = poly(t) exp(-z^2), t = 1 / (1 + 0.3275911 |z|), by Abramowitz-Stegun
+// 7.1.26 (|abs error| <= 1.5e-7), and 1 + erf(z) = erfc(-z) is taken WITHOUT a subtraction on the negative side:
+//   x < 0: 0.5 x (poly e);   x >= 0: 0.5 x (2 - poly e) = x - 0.5 x poly e,
+// both as ONE fma, -(0.5 |x| poly) e + max(x, 0), with max(x, 0) = 0.5 x + |0.5 x| (exact) - no more VALU instructions than forming
+// erf = copysign(1 - poly e, x) and then 1 + erf.  (That former form made the approximation's 1.5e-7 an ABSOLUTE error of 1 + erf:
+// a bf16 result twice the true value on [-6, -5].)  Error of this form against fp64 (tests/gemm_cases.py: fp32 emulation with
+// exact exp2 / reciprocal; the tests carry twice these figures for the 1-ulp v_exp_f32 / v_rcp_f32, gemm_cases.erf_act_err):
+//   everywhere <= 2.7e-7 |x| absolute (the tests carry 3e-7 |x|);  for x < 0 also RELATIVE to |gelu(x)|:
+//   5.3e-5 on [-3, 0), 4.7e-4 on [-4, -3), 1.6e-3 on [-5, -4), 3.6e-3 on [-6, -5), 1.03e-2 on [-8, -6), 3.2e-2 on [-12, -8),
+//   8.4e-2 below (|gelu| < 1e-32 there) - at most 0.92 roundoffs of a bf16 result on [-6, 0] (2.6 / 7.9 on [-8, -6] / [-12, -8],
+//   where |gelu| < 1e-10), at most 0.65 of an fp16 result (with its subnormal floor) everywhere.
+__device__ __forceinline__ float gelu_erf(float x) {
+    const float az = fabsf(x) * 0.70710678118654752f;
+    const float t = fast_rcp(__builtin_fmaf(0.3275911f, az, 1.0f));
     float poly = __builtin_fmaf(1.061405429f, t, -1.453152027f);
     poly = __builtin_fmaf(poly, t, 1.421413741f);
     poly = __builtin_fmaf(poly, t, -0.284496736f);
     poly = __builtin_fmaf(poly, t, 0.254829592f);
     poly *= t;
-    const float e = fast_exp2(-1.4426950408889634f * ax * ax);
-    const float r = __builtin_fmaf(-poly, e, 1.0f);
-    return copysignf(r, x);
+    const float e = fast_exp2(-1.4426950408889634f * az * az);
+    const float h = 0.5f * x;
+    return __builtin_fmaf(-(fabsf(h) * poly), e, h + fabsf(h));
 }
-// nn.GELU() / ACT2FN["gelu"]: 0.5 x (1 + erf(x / sqrt(2)))
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erf_as(x * 0.70710678118654752f)); }
 // "gelu_pytorch_tanh": 0.5 x (1 + tanh(u)) == x * sigmoid(2u), u = sqrt(2/pi) (x + 0.044715 x^3)   (exact identity),
 // as x / (1 + 2^(x (c0 + c1 x^2))).  The GEMM epilogues are VALU-bound on this, so the arithmetic around the two
 // transcendentals is written on float pairs (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32: two lanes' worth per issue).

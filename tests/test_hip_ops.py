@@ -174,7 +174,8 @@ def test_gemm_layernorm_fusion_over_a_16bit_stream(ops, dtype, M):
 def test_gemm_layernorm_fusion(ops, dtype, M):
     """LayerNorm fused into the GEMMs around it: the producer (fp32 residual update) also emits the 16-bit row copy and
     per-slot (mean, M2) partials, tdc_ln_finalize turns them into (mean, rstd), the consumer folds them into its
-    epilogue.  The three M exercise the 128x128, the 256x256 and the persistent kernel; every output of the small launch
+    epilogue.  There are two kernels: M = 300 and M = 8192 (160 tiles of 256 x 256 at N = 1216, fewer than the 192 the persistent
+    kernel is launched from) run on the 128x128 kernel, M = 80 * 256 - 19 on the persistent one; every output of the small launch
     of a row range must be BITWISE equal to the same rows of the large launch (kernel-independent rows)."""
     from tdc_video_amd import lib as L
     g = torch.Generator(device="cuda").manual_seed(11)
@@ -225,9 +226,9 @@ def test_gemm_layernorm_fusion(ops, dtype, M):
 
 
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("M", [300, 8192, 40 * 256 + 7, 80 * 256 - 19])    # 128x128 (x2), 256x256, persistent
+@pytest.mark.parametrize("M", [300, 8192, 40 * 256 + 7, 80 * 256 - 19])    # 128x128 (x2); persistent with one tile per workgroup (205 tiles), persistent
 def test_gemm_fp8_operands(ops, dtype, M):
-    """A and W as OCP e4m3 bytes through v_mfma_f32_16x16x128_f8f6f4 (all three GEMM kernels), per-row activation scale x
+    """A and W as OCP e4m3 bytes through v_mfma_f32_16x16x128_f8f6f4 (both GEMM kernels), per-row activation scale x
     per-tensor weight scale applied through the LayerNorm-fold operands.  The reference is the SAME quantised operands
     multiplied in fp32, so the tolerance is the 16-bit output rounding, not the fp8 quantisation."""
     from tdc_video_amd import lib as L
@@ -269,7 +270,7 @@ def test_gemm_fp8_operands(ops, dtype, M):
 
 
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("M", [300, 40 * 256 + 7, 256 * 300 + 77])       # 128x128, 256x256 and persistent kernels
+@pytest.mark.parametrize("M", [300, 40 * 256 + 7, 256 * 300 + 77])       # 128x128; the persistent kernel with one tile per workgroup and with many
 def test_gemm_fp8_output(ops, dtype, M):
     """tdc_gemm_desc.out_fp8 (fp8 towers level 3): act(A8 W8^T + b) leaves as e4m3 with the analytic per-row scale
     s_h = (rstd * norm * w2max + bmax)^p / 448; out_stats = (0, s_h * out_wscale).  Checked against the same fp32 product:
@@ -390,7 +391,7 @@ def test_gemm_row_mapped_a_on_the_persistent_kernel(ops, dtype, seg, stride, off
     L_ACT_NONE, L_ACT_GELU_ERF = L.ACT_NONE, L.ACT_GELU_ERF
     g = torch.Generator(device="cuda").manual_seed(13)
     N, K = 1280, 192
-    M = 256 * 40 + 77                                   # 41 x 5 = 205 tiles of 256 x 256 (>= 192: the 256 x 256 path)
+    M = 256 * 40 + 77                                   # 41 x 5 = 205 tiles of 256 x 256 (>= 192: the persistent kernel)
     nseg = (M + seg - 1) // seg
     rows = max((nseg - 1) * stride + off + seg, nseg * stride + off) + 1
     a = torch.randn(rows, K, device="cuda", generator=g).to(dtype)
@@ -757,7 +758,7 @@ def test_qformer_xattn_output_projection_only(ops, dtype, F, K, Lt):
 
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("cdtype", DT)
-@pytest.mark.parametrize("M", [300, 40 * 256 + 7, 80 * 256 - 19])    # 128x128, 256x256 and persistent kernels
+@pytest.mark.parametrize("M", [300, 40 * 256 + 7, 80 * 256 - 19])    # 128x128; the persistent kernel with one tile per workgroup and with several
 def test_gemm_16bit_residual_read_modify_write(ops, dtype, cdtype, M):
     """C = T16(acc + bias + float(res)) with ONE rounding - the update of a 16-bit residual stream (tdc_vit_model.res_dtype_p1) -
     for both 16-bit types of C / res under both operand types (tdc_gemm_desc.c16_dtype_p1), in place and out of place, ragged
