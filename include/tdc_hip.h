@@ -500,6 +500,17 @@ typedef struct {
     const float *ones_C, *zeros_C;                   /* [pad64(C)] (the un-affine LayerNorm of the k/v inputs) */
     const tdc_sva_layer* layers_host;
     tdc_lin mm1, mm2;                                /* mm_projector: Linear(C, H) + GELU, Linear(H, H) */
+    /* kept aux rows.  All three NULL: the aux LayerNorm rows of tower i and the per-frame mean of tower
+     * 0's rows live in the workspace, as described above.  All three set: caller-owned, 256-byte aligned buffers of 16-bit
+     * values take those regions' place - aux_keep[i] [T*P, pad64(C)] and ctx_keep [T, pad64(C)], row stride pad64(C).  The aux
+     * LayerNorm writes aux_keep[i], tdc_token_mean reads aux_keep[0] and writes ctx_keep, and every later reader (each layer's
+     * un-affine LayerNorm, each layer's proj_context GEMM) reads them there: the same launches on the same operands with
+     * other pointers, so the rows are the workspace form's bit for bit and `out` is too.  The workspace layout and
+     * tdc_connector_workspace_bytes do not change.  Some but not all of the three set, or a misaligned one: TDC_E_BADARG before
+     * the first launch.
+     * writes: exactly the elements the workspace regions received - aux_keep[i][row, 0 .. pad64(C)) for row < T*P (pad columns
+     * zero, as tdc_layernorm leaves them) and ctx_keep[t, 0 .. pad64(C)) for t < T -, nothing else of them. */
+    void* aux_keep[2]; void* ctx_keep;
 } tdc_connector_model;
 size_t tdc_connector_workspace_bytes(const tdc_connector_model* m, int T);
 int tdc_connector_fwd(const tdc_connector_model* m, const void* sig, int ld_s, const void* dino, int ld_d, int T,

@@ -514,6 +514,13 @@ extern "C" int tdc_connector_fwd(const tdc_connector_model* m, const void* sig, 
     const ConnWs w = conn_layout(m, T);
     if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return TDC_E_WORKSPACE;
     char* ws = (char*)workspace;
+    // kept aux rows (tdc_connector_model.aux_keep / ctx_keep): all three or none; caller-owned buffers take the place of the
+    // workspace's aux / ctx regions for the launches that write them and for every later reader
+    const int n_keep = (m->aux_keep[0] != nullptr) + (m->aux_keep[1] != nullptr) + (m->ctx_keep != nullptr);
+    if (n_keep != 0 && n_keep != 3) return TDC_E_BADARG;
+    if (n_keep && (((uintptr_t)m->aux_keep[0] | (uintptr_t)m->aux_keep[1] | (uintptr_t)m->ctx_keep) & 255)) return TDC_E_BADARG;
+    char* const aux[2] = {n_keep ? (char*)m->aux_keep[0] : ws + w.aux[0], n_keep ? (char*)m->aux_keep[1] : ws + w.aux[1]};
+    char* const ctx = n_keep ? (char*)m->ctx_keep : ws + w.ctx;
     const int C = m->C, Cp = pad64i(C), dt = m->dtype, side = m->side, r = m->r;
     const int P = side * r * side * r, nq = side * side, rows = T * P, qrows = T * nq;
     const float eps = 1e-5f;
@@ -525,9 +532,9 @@ extern "C" int tdc_connector_fwd(const tdc_connector_model* m, const void* sig, 
         const tdc_aux_proj& a = m->aux[i];
         RET_IF(Gemm(feats[i], lds[i], a.fc1, ws + w.h, Cp, rows, dt).act(TDC_ACT_GELU_ERF).run(stream));
         RET_IF(Gemm(ws + w.h, Cp, a.fc2, ws + w.y32, Cp, rows, dt).out_f32().run(stream));
-        RET_IF(Ln(ws + w.y32, Cp, 1, a.ln_g, a.ln_b, eps, rows, C, dt).y16(ws + w.aux[i], Cp).run(stream));
+        RET_IF(Ln(ws + w.y32, Cp, 1, a.ln_g, a.ln_b, eps, rows, C, dt).y16(aux[i], Cp).run(stream));
     }
-    RET_IF(tdc_token_mean(ws + w.aux[0], P, Cp, ws + w.ctx, T, dt, stream));
+    RET_IF(tdc_token_mean(aux[0], P, Cp, ctx, T, dt, stream));
     // queries start as vision_query broadcast to every window of every frame (cambrian_arch.py:1018-1023)
     RET_IF(tdc_fill_rows(m->vision_query, ws + w.q16[0], Cp, qrows, stream));
     int cur = 0;
@@ -535,14 +542,14 @@ extern "C" int tdc_connector_fwd(const tdc_connector_model* m, const void* sig, 
         const tdc_sva_layer& L = m->layers_host[l];
         char* q16 = ws + w.q16[cur];
         char* q16n = ws + w.q16[cur ^ 1];
-        RET_IF(Gemm(ws + w.ctx, Cp, L.proj_context, ws + w.cproj, Cp, T, dt).run(stream));
+        RET_IF(Gemm(ctx, Cp, L.proj_context, ws + w.cproj, Cp, T, dt).run(stream));
         RET_IF(Gemm(ws + w.cproj, Cp, L.proj_in_c, ws + w.cin, Cp, T, dt).out_f32().run(stream));
         {   // proj_in(cat[q, ctx]) = proj_in_q(q) + (per-frame) proj_in_c(ctx)
             const tdc_rowmap rmap = {nq, 1, 0, 0};
             RET_IF(Gemm(q16, Cp, L.proj_in_q, ws + w.qin, Cp, qrows, dt).out_f32().res(ws + w.cin, Cp, 1).r_map(rmap).run(stream));
         }
         for (int tw = 0; tw < 2; ++tw) {    // un-affine LayerNorm of the tower's tokens + window position (the affines live in kv[tw])
-            RET_IF(Ln(ws + w.aux[tw], Cp, 0, m->ones_C, m->zeros_C, eps, rows, C, dt).y16(ws + w.xn, Cp)
+            RET_IF(Ln(aux[tw], Cp, 0, m->ones_C, m->zeros_C, eps, rows, C, dt).y16(ws + w.xn, Cp)
                        .add(L.pos[tw], L.ldpos, P, 1).run(stream));
             RET_IF(Gemm(ws + w.xn, Cp, L.kv[tw], ws + w.kv[tw], L.kv[tw].n, rows, dt).run(stream));
         }

@@ -435,12 +435,27 @@ def segmented(cfg, T):
     return T > cfg.get("max_num_segments", 24) + 1
 
 
-def pixel_front(e, cache, px_siglip, px_dino, rows, idx, T0, image_size, audio=None, keep=None, video_index=None, info=None):
+def aux_kw(aux, cache=None):
+    """the keyword that carries aux= (VideoEncoder.connector: the reference's three aux outputs) one level
+    down - nothing when it was not asked for, so engines and sources that predate it are called as they always were.  With a
+    frame cache it raises: the cache keeps connector rows, not aux rows."""
+    if aux is None:
+        return {}
+    if not isinstance(aux, dict):
+        raise ValueError("aux= is a dict that receives features / masks / global_context, got %r" % type(aux).__name__)
+    if cache is not None:
+        raise ValueError("aux= and cache= cannot be given together: the frame cache keeps connector rows, not aux rows")
+    return {"aux": aux}
+
+
+def pixel_front(e, cache, px_siglip, px_dino, rows, idx, T0, image_size, audio=None, keep=None, video_index=None, info=None,
+                aux=None):
     """the prompt-independent part of an encode behind a1 (a2-a10, a20) from pixels: the kept frames are the rows `rows` of
     px_siglip / px_dino and the frames idx of the T0-frame video -> dict(X, T, N, seg_idx, audio, idx, final_size, sig, dino).
     Through the cache (front_cached_selected, which adds `cache_info` and leaves sig / dino out) unless there is none, keep=
     asks for the stage tensors only the uncached per-kernel connector form produces, or the call is over the cache's budget."""
     f = None
+    aux = aux_kw(aux, cache)
     if cache is not None and keep is None:
         f = front_cached_selected(e, cache, px_siglip, px_dino, rows, idx, T0, image_size, audio, video_index, info)
     if f is not None:
@@ -451,27 +466,28 @@ def pixel_front(e, cache, px_siglip, px_dino, rows, idx, T0, image_size, audio=N
         px_siglip, px_dino = px_siglip[sel], px_dino[sel]
     sig, dino, (seg_idx,) = towers_and_selection(e, px_siglip, px_dino, [(0, T, segmented(e.cfg, T))],
                                                  None if info is None else [info])                  # a3-a5
-    return front_after_towers(e, sig, dino, seg_idx, T0, idx, image_size, audio, keep, video_index)
+    return front_after_towers(e, sig, dino, seg_idx, T0, idx, image_size, audio, keep, video_index, **aux)
 
 
-def front_after_towers(e, sig, dino, seg_idx, T0, idx, image_size, audio=None, keep=None, video_index=None):
+def front_after_towers(e, sig, dino, seg_idx, T0, idx, image_size, audio=None, keep=None, video_index=None, aux=None):
     """what a front does once the tower rows of the a1-kept frames idx (of T0) and their a5 selection are known - the
     connector (a6-a10) and the frames' audio (a20) -> the front's dict.  Shared by pixel_front and FeatureSource.front."""
     T = len(idx)
     sizes = [tuple(image_size)] * T
-    X, final_size = e.connector(sig, dino, T, sizes, keep)                                          # a6-a10
+    X, final_size = e.connector(sig, dino, T, sizes, keep, **aux_kw(aux))                           # a6-a10
     N = X.shape[0] // T
     if audio is not None:                                                                           # a20
         audio = e.local_audio(audio, sample_indicator(T0, idx, video_index), T, 0, T)
     return dict(X=X, T=T, N=N, seg_idx=seg_idx, audio=audio, idx=idx, final_size=final_size, sig=sig, dino=dino)
 
 
-def image_rows(e, px_siglip, px_dino, image_size, cache=None):
+def image_rows(e, px_siglip, px_dino, image_size, cache=None, aux=None):
     """a single image ([1, 3, H, W] each): no a1 / a5 / Q-Former -> (connector rows [N, Hp], [final size]); through the frame
     cache when one is given"""
+    aux = aux_kw(aux, cache)
     if cache is not None:
         return encode_image_cached(e, cache, px_siglip, px_dino, image_size)
-    return e.connector(e.tower("siglip", px_siglip), e.tower("dino", px_dino), 1, [tuple(image_size)])
+    return e.connector(e.tower("siglip", px_siglip), e.tower("dino", px_dino), 1, [tuple(image_size)], **aux)
 
 
 class PixelSource:
@@ -484,12 +500,12 @@ class PixelSource:
         self.px_siglip, self.px_dino, self.image_size, self.cache = px_siglip, px_dino, image_size, cache
         self.T0 = px_siglip.shape[0]
 
-    def front(self, e, idx, audio=None, video_index=None, info=None, keep=None):
+    def front(self, e, idx, audio=None, video_index=None, info=None, keep=None, aux=None):
         return pixel_front(e, self.cache, self.px_siglip, self.px_dino, idx, idx, self.T0, self.image_size, audio, keep,
-                           video_index, info)
+                           video_index, info, aux)
 
-    def image(self, e, info=None):
-        X, sizes = image_rows(e, self.px_siglip, self.px_dino, self.image_size, self.cache)
+    def image(self, e, info=None, aux=None):
+        X, sizes = image_rows(e, self.px_siglip, self.px_dino, self.image_size, self.cache, aux)
         if info is not None:
             info["final_size"] = sizes
         return X
@@ -503,24 +519,26 @@ class PixelSource:
 
 
 def encode_source(e, src, budget_text_len, n_text_tokens, prompt_ids, audio=None, frame_cap=224, keep=None, splice=None,
-                  video_index=None, info=None, image=False):
+                  video_index=None, info=None, image=False, aux=None):
     """One video from any source (PixelSource, FrameSource, FeatureSource) -> emitted visual tokens [n, H]
     (VideoEncoder.encode_video documents the arguments).  a1 is evaluated here and nowhere below.  image=True: the source's one
     frame as a single image - its connector rows [:, :H], as prepare_inputs_labels_for_multimodal's image branch; a1 is not
-    evaluated and budget_text_len may be None."""
+    evaluated and budget_text_len may be None.  aux: a dict that receives the connector's three aux outputs (aux_kw); refused
+    before any launch when the source carries a frame cache."""
+    aux = aux_kw(aux, getattr(src, "cache", None))
     if image:
-        return src.image(e, info)[:, :e.H]
+        return src.image(e, info, **aux)[:, :e.H]
     idx = frame_indices(e.cfg, src.T0, budget_text_len, frame_cap)                                  # a1
-    f = src.front(e, idx, audio, video_index, info, keep)
+    f = src.front(e, idx, audio, video_index, info, keep, **aux)
     return encode_front(e, f, n_text_tokens, prompt_ids, keep, splice, info)
 
 
 def encode_video_with(e, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio=None,
-                      frame_cap=224, keep=None, splice=None, video_index=None, info=None, cache=None):
+                      frame_cap=224, keep=None, splice=None, video_index=None, info=None, cache=None, aux=None, image=False):
     """One video: pixels -> emitted visual tokens [n, H].  cache: a FrameCache - the front runs through it, the result is bit
-    for bit that of cache=None, and info["cache"] says what the call reused and encoded."""
+    for bit that of cache=None, and info["cache"] says what the call reused and encoded.  aux / image: encode_source's."""
     return encode_source(e, PixelSource(px_siglip, px_dino, image_size, cache), budget_text_len, n_text_tokens, prompt_ids,
-                         audio, frame_cap, keep, splice, video_index, info)
+                         audio, frame_cap, keep, splice, video_index, info, image, aux)
 
 
 def selection_facts(info, f):
@@ -936,7 +954,7 @@ class FeatureSource:
             check_features(e, self.fs)
             self.unchecked = False
 
-    def front(self, e, idx, audio=None, video_index=None, info=None, keep=None):
+    def front(self, e, idx, audio=None, video_index=None, info=None, keep=None, aux=None):
         """pixel_front from the stored rows instead of pixels: the kept frames' rows gathered, a5 by the pixel path's launch on
         the gathered DINOv2 rows, then front_after_towers -> the same dict, the same bits.  A compact set: a5 ranks the stored
         similarities of the ORIGINAL rows wherever the set holds every gap between neighbouring kept frames
@@ -962,14 +980,14 @@ class FeatureSource:
             seg_idx = select_segments_with(e, sims, None, info)
         else:
             seg_idx = list(range(T))
-        return front_after_towers(e, sig, dino, seg_idx, self.T0, idx, fs.image_size, audio, keep, video_index)
+        return front_after_towers(e, sig, dino, seg_idx, self.T0, idx, fs.image_size, audio, keep, video_index, aux)
 
-    def image(self, e, info=None):
+    def image(self, e, info=None, aux=None):
         if self.T0 != 1:
             raise ValueError("image=True takes a one-frame feature set, got %d frames" % self.T0)
         self.check(e)
         sig, dino = feature_rows(e, self.fs)
-        X, sizes = e.connector(sig, dino, 1, [tuple(self.image_size)])
+        X, sizes = e.connector(sig, dino, 1, [tuple(self.image_size)], **aux_kw(aux))
         if info is not None:
             info["final_size"] = sizes
         return X
@@ -990,11 +1008,11 @@ class FeatureSource:
 
 
 def encode_features_with(e, fs, budget_text_len, n_text_tokens, prompt_ids, audio=None, frame_cap=224, splice=None,
-                         video_index=None, info=None, check_signature=True, image=False):
+                         video_index=None, info=None, check_signature=True, image=False, aux=None):
     """encode_video_with from a FeatureSet: bit for bit its result for the pixels the set was exported from, whenever that
     call refines nothing.  image=True (a one-frame set): the connector rows [:, :H] of the image (info receives final_size)."""
     return encode_source(e, FeatureSource(fs, check_signature), budget_text_len, n_text_tokens, prompt_ids, audio, frame_cap,
-                         None, splice, video_index, info, image)
+                         None, splice, video_index, info, image, aux)
 
 
 def encode_features_prompts_with(e, fs, prompts, audio=None, frame_cap=224, video_index=None, infos=None, max_prompts=8,
@@ -1031,7 +1049,7 @@ class FrameSource:
         self.frames, self.cache = frames, cache
         self.T0, self.image_size = frames_size(frames, image_size)
 
-    def front(self, e, idx, audio=None, video_index=None, info=None, keep=None):
+    def front(self, e, idx, audio=None, video_index=None, info=None, keep=None, aux=None):
         """the kept frames' pixels (rows 0 .. T-1), then pixel_front with T0 and idx handed over as PixelSource hands them - the
         same launches on the same operands, so the same dict and the same bits as the pixel front on process_images of ALL
         frames.  Audio and info["frame_indices"] refer to the video's own frame numbers.  The cache keys are the pixel
@@ -1042,24 +1060,24 @@ class FrameSource:
         if info is not None:
             info.update(frames_in=self.T0, frames_resized=T)
         return pixel_front(e, self.cache, px_siglip, px_dino, list(range(T)), idx, self.T0, self.image_size, audio, keep,
-                           video_index, info)
+                           video_index, info, aux)
 
-    def image(self, e, info=None):
+    def image(self, e, info=None, aux=None):
         if self.T0 != 1:
             raise ValueError("image=True takes one frame, got %d" % self.T0)
         px_siglip, px_dino = e.pixels_from_frames(self.frames, None)
-        X, sizes = image_rows(e, px_siglip, px_dino, self.image_size, self.cache)
+        X, sizes = image_rows(e, px_siglip, px_dino, self.image_size, self.cache, aux)
         if info is not None:
             info.update(final_size=sizes, frames_in=1, frames_resized=1)
         return X
 
 
 def encode_frames_with(e, frames, budget_text_len, n_text_tokens, prompt_ids, audio=None, frame_cap=224, splice=None,
-                       video_index=None, info=None, cache=None, image_size=None, image=False):
+                       video_index=None, info=None, cache=None, image_size=None, image=False, aux=None):
     """encode_video_with from decoded frames: bit for bit its result on process_images of the same frames.  image=True (one
     frame): the connector rows [:, :H] of the image (through the cache when one is given; info receives final_size)."""
     return encode_source(e, FrameSource(frames, image_size, cache), budget_text_len, n_text_tokens, prompt_ids, audio,
-                         frame_cap, None, splice, video_index, info, image)
+                         frame_cap, None, splice, video_index, info, image, aux)
 
 
 def encode_frames_prompts_with(e, frames, prompts, audio=None, frame_cap=224, video_index=None, infos=None, cache=None,

@@ -106,7 +106,7 @@ class ConnectorModel(C.Structure):
     _fields_ = [("dtype", C.c_int), ("C", C.c_int), ("side", C.c_int), ("r", C.c_int), ("heads", C.c_int),
                 ("n_layers", C.c_int), ("aux", AuxProj * 2), ("vision_query", C.c_void_p),
                 ("ones_C", C.c_void_p), ("zeros_C", C.c_void_p), ("layers_host", C.POINTER(SvaLayer)),
-                ("mm1", Lin), ("mm2", Lin)]
+                ("mm1", Lin), ("mm2", Lin), ("aux_keep", C.c_void_p * 2), ("ctx_keep", C.c_void_p)]
 
 
 class QformerLayer(C.Structure):

@@ -571,6 +571,26 @@ class CambrianMetaModel:
                     raise ValueError("config.tdc_frame_inputs and config.%s cannot be set together" % other)
         return v
 
+    def tdc_return_aux(self):
+        """`config.tdc_return_aux`: True = prepare_inputs_labels_for_multimodal fills slots 6, 7 and 9 of its 10-tuple with the
+        reference's vision_tower_aux_feature_list_final, vision_tower_aux_attention_masks_list_final and
+        global_context_feature_final (tdc/cambrian_arch.py:1187-1193, 1295-1303, 1833-1844), concatenated
+        over the samples of the call in sample order, on the engine device; everything else of the tuple is the key-off
+        call's.  Absent / False: the three slots are None.  Composes with `tdc_frame_inputs` and `tdc_feature_inputs`; set
+        together with `config.tdc_video_cache_bytes`, `tdc_kv_cache_bytes`, `tdc_shard_frames`, `tdc_shard_cache_bytes`,
+        `tdc_batch_frames` or `tdc_batch_prompts` it raises: those paths keep or move connector rows, not aux rows."""
+        v = getattr(self.config, "tdc_return_aux", None)
+        if v is None:
+            return False
+        if not isinstance(v, bool):
+            raise ValueError("config.tdc_return_aux must be True / False (absent = off), got %r" % (v,))
+        if v:
+            for other in ("tdc_video_cache_bytes", "tdc_kv_cache_bytes", "tdc_shard_frames", "tdc_shard_cache_bytes",
+                          "tdc_batch_frames", "tdc_batch_prompts"):
+                if getattr(self.config, other, None):
+                    raise ValueError("config.tdc_return_aux and config.%s cannot be set together" % other)
+        return v
+
     def tdc_prompt_pad_fraction(self):
         """`config.tdc_prompt_pad_fraction`: the share of a prompt group's rows that may be padding (encode.prompt_groups);
         absent: 1/4."""
@@ -727,6 +747,7 @@ class CambrianMetaForCausalLM(ABC):
             return (input_ids, position_ids, attention_mask, past_key_values, None, labels, None, None, None, None)
         frame_inputs = model.tdc_frame_inputs()      # config.tdc_frame_inputs: `images` holds decoded uint8 frames
         feature_inputs = model.tdc_feature_inputs()  # config.tdc_feature_inputs: `images` holds stored tower features
+        return_aux = model.tdc_return_aux()          # config.tdc_return_aux: slots 6 / 7 / 9 of the 10-tuple
         if feature_inputs:
             feature_sets = self._feature_sets(images, image_sizes, input_ids.shape[0])      # validated before any engine call
         eng = model.tdc_engine()
@@ -749,6 +770,7 @@ class CambrianMetaForCausalLM(ABC):
         visual = []          # per sample: [n_tokens, H] tensor on the engine device
         spliced = []         # per sample: `visual[i]` already holds the text rows around the visual tokens
         final_size = []
+        aux_out = []         # config.tdc_return_aux: per sample the dict VideoEncoder.connector(aux=) filled
 
         def facts(i):
             """the host-side facts of sample i: its source (encode.py: what its frames are read from) with the engine's entries
@@ -827,8 +849,12 @@ class CambrianMetaForCausalLM(ABC):
             """sample f through the engine on its own -> (visual tokens, spliced, final sizes)"""
             src, n_text, prompt_ids, audio, splice = (f[k] for k in ("src", "n_text", "prompt_ids", "audio", "splice"))
             keep = {}
+            akw = {}
+            if return_aux:      # the keyword goes down only when the key is on
+                aux_out.append({})
+                akw = {"aux": aux_out[-1]}
             if not is_video:
-                vis = f["entry"](None, n_text, None, image=True, info=keep)
+                vis = f["entry"](None, n_text, None, image=True, info=keep, **akw)
             elif f["sharded"] is not None:
                 # config.tdc_shard_frames under an initialised torch.distributed (one process per GPU, every rank called
                 # with the same video - how the reference's eval drivers start their workers, eval/eval_mlvu.py:129-157 -
@@ -851,7 +877,7 @@ class CambrianMetaForCausalLM(ABC):
                 if f["side_stream"]:
                     eng.two_streams = model.tdc_side_stream(min(src.T0, f["cap"]))
                 vis = f["entry"](f["btl"], n_text, prompt_ids, audio=audio, frame_cap=f["cap"], splice=splice,
-                                 video_index=f["vindex"], info=keep)
+                                 video_index=f["vindex"], info=keep, **akw)
             return vis, splice is not None, keep["final_size"]
 
         def encode_group(fs, n_frames):
@@ -977,7 +1003,15 @@ class CambrianMetaForCausalLM(ABC):
         new_labels_out = None if _labels is None else lab_pad
         att_out = None if _attention_mask is None else att.to(dtype=_attention_mask.dtype)
         pos_out = None if _position_ids is None else pos
-        return (None, pos_out, att_out, past_key_values, new_input_embeds, new_labels_out, None, None, final_size, None)
+        aux_feats = aux_masks = aux_ctx = None
+        if return_aux:      # per tower / overall: the samples' rows in sample order along dim 0 (cambrian_arch.py:678-683, 1300-1303)
+            def cat(xs):
+                return xs[0] if len(xs) == 1 else torch.cat(xs, 0)
+            aux_feats = [cat([d["features"][i] for d in aux_out]) for i in range(2)]
+            aux_masks = [cat([d["masks"][i] for d in aux_out]) for i in range(2)]
+            aux_ctx = cat([d["global_context"] for d in aux_out])
+        return (None, pos_out, att_out, past_key_values, new_input_embeds, new_labels_out, aux_feats, aux_masks, final_size,
+                aux_ctx)
 
     def initialize_vision_tokenizer(self, model_args, tokenizer):
         raise NotImplementedError("tokenizer surgery for training (tdc/cambrian_arch.py:1846-1898) is out of scope")

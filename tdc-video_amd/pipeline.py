@@ -542,8 +542,9 @@ class VideoEncoder:
         y16, _ = ops.layernorm(y, a.ln_g, a.ln_b, 1e-5, self.c.C, self.dtype)
         return y16
 
-    def sva(self, aux, T, image_sizes):
-        """aux: two [T*P, pad64(C)] 16-bit tensors -> queries [T*nq, pad64(C)] (vision_sampler_0, 3 layers)."""
+    def sva(self, aux, T, image_sizes, ctx=None):
+        """aux: two [T*P, pad64(C)] 16-bit tensors -> queries [T*nq, pad64(C)] (vision_sampler_0, 3 layers).  ctx: the token
+        mean of aux[0] when the caller has launched it already (connector with aux=)."""
         c, dt, dev = self.c, self.dtype, self.dev
         C, Cp = c.C, pad64(c.C)
         side = self.side
@@ -552,7 +553,8 @@ class VideoEncoder:
         n = int(round(P ** 0.5))
         r = n // side
         mask, _ = self._window_mask(T, P, image_sizes)      # host geometry, cached per (T, image size)
-        ctx = ops.token_mean(aux[0], T, P)                                    # [T, Cp]
+        if ctx is None:
+            ctx = ops.token_mean(aux[0], T, P)                                # [T, Cp]
         q16 = torch.zeros(T * nq, Cp, device=dev, dtype=dt)
         q16[:, :C] = c.vision_query.to(dt).to(dev)[None, :]
         for Lr in c.sva:
@@ -654,12 +656,24 @@ class VideoEncoder:
             hit = self._tables[key] = torch.from_numpy(np.concatenate(rows, 0)).to(self.dev).contiguous()
         return hit, r
 
-    def _connector_native(self, sig_feat, dino_feat, T, image_sizes):
+    def _connector_native(self, sig_feat, dino_feat, T, image_sizes, kept=None):
+        """kept (aux0, aux1, ctx): buffers of _aux_keep_alloc that receive the aux rows and their per-frame mean instead of the
+        workspace (tdc_connector_model.aux_keep / ctx_keep); `out` is the kept=None one bit for bit."""
         import ctypes as C
         m = self._connector_struct()[0]
         P = sig_feat.shape[0] // T
         mask, r = self._window_mask(T, P, image_sizes)
         m.r = r
+        if kept is not None:
+            # kept aux rows: a copy of the model struct carries the buffers, the cached one stays as is
+            mk = L.ConnectorModel()
+            C.pointer(mk)[0] = m
+            Cp = pad64(self.c.C)
+            for b, rows in zip(kept, (T * P, T * P, T)):
+                assert b.is_cuda and b.device == sig_feat.device and b.dtype == self.dtype and b.is_contiguous() and \
+                    tuple(b.shape) == (rows, Cp) and b.data_ptr() % 256 == 0, "kept is _aux_keep_alloc(T, P)"
+            mk.aux_keep[0], mk.aux_keep[1], mk.ctx_keep = kept[0].data_ptr(), kept[1].data_ptr(), kept[2].data_ptr()
+            m = mk
         assert dino_feat.shape[0] == T * P and P == (self.side * r) ** 2
         assert sig_feat.shape[1] >= m.aux[0].fc1.k and dino_feat.shape[1] >= m.aux[1].fc1.k
         lib = L.load()
@@ -670,16 +684,78 @@ class VideoEncoder:
                                       ws.numel(), ops._stream()), "tdc_connector_fwd")
         return out
 
-    def connector(self, sig_feat, dino_feat, T, image_sizes, keep=None):
+    def _aux_keep_alloc(self, T, P):
+        """the three caller-owned buffers of tdc_connector_model.aux_keep / ctx_keep: aux rows [T*P, pad64(C)] of both towers
+        and their per-frame mean [T, pad64(C)] (torch's allocator hands out 512-byte aligned blocks)"""
+        Cp = pad64(self.c.C)
+        return tuple(torch.empty(n, Cp, device=self.dev, dtype=self.dtype) for n in (T * P, T * P, T))
+
+    def _aux_maps(self, T, P, image_sizes):
+        """host geometry of the three aux outputs (segment.aux_window_map per frame), built once per (T, image sizes) and kept
+        on the device: (feat_idx [n*r*r, 2], ctx_idx [n, 2], masks bool [n, r*r], n) - gather maps into the [T*P] aux rows and
+        the [T] mean rows, range-checked on the host before upload."""
+        side = self.side
+        r = int(round(P ** 0.5)) // side
+        key = ("aux", T, P, tuple(image_sizes[0]) if len(set(map(tuple, image_sizes))) == 1 else tuple(map(tuple, image_sizes)))
+        hit = self._tables.get(key)
+        if hit is None:
+            import numpy as np
+            assert T * P < 2 ** 31
+            cache, feat, ctx, masks = {}, [], [], []
+            for t in range(T):
+                k = tuple(image_sizes[t])
+                if k not in cache:
+                    cache[k] = seg.aux_window_map(side, r, k)[:2]
+                src, m = cache[k]
+                feat.append(src.reshape(-1) + t * P)
+                ctx.append(np.full(src.shape[0], t, dtype=np.int64))
+                masks.append(m)
+
+            def pairs(rows, limit):
+                p = np.zeros((rows.shape[0], 2), dtype=np.int32)
+                p[:, 1] = rows
+                ops.check_pairs_host(p, [limit])
+                return torch.from_numpy(p).to(self.dev).contiguous()
+            ctx_rows = np.concatenate(ctx, 0)
+            hit = self._tables[key] = (pairs(np.concatenate(feat, 0), T * P), pairs(ctx_rows, T),
+                                       torch.from_numpy(np.concatenate(masks, 0)).to(self.dev).contiguous(),
+                                       int(ctx_rows.shape[0]))
+        return hit + (r,)
+
+    def aux_outputs(self, aux0, aux1, ctx, T, image_sizes, aux):
+        """slots 6, 7 and 9 of the reference's 10-tuple (tdc/cambrian_arch.py:1187-1193, 1295-1303) from the aux rows
+        [T*P, pad64(C)] of both towers and their per-frame mean [T, pad64(C)]: three tdc_gather_rows launches into contiguous
+        [n, r*r, C] / [n, 1, C] tensors of exactly C columns; the masks are host geometry.  Fills the dict `aux`."""
+        C = self.c.C
+        P = aux0.shape[0] // T
+        feat_idx, ctx_idx, masks, n, r = self._aux_maps(T, P, image_sizes)
+        if n == 0:
+            raise ValueError("aux outputs: un-padding image sizes %r keeps no window" % (list(map(tuple, image_sizes)),))
+        assert aux1.shape[0] == T * P and ctx.shape[0] == T
+        feats = [ops.gather_rows([a], feat_idx, n * r * r, C, validated=True).view(n, r * r, C) for a in (aux0, aux1)]
+        gctx = ops.gather_rows([ctx], ctx_idx, n, C, validated=True).view(n, 1, C)
+        aux.update(features=feats, masks=[masks, masks.clone()], global_context=gctx)
+
+    def connector(self, sig_feat, dino_feat, T, image_sizes, keep=None, aux=None):
+        """a6-a10.  aux: a dict that receives the reference's three aux outputs (aux_outputs) - the native
+        composite then leaves its aux rows in buffers of this call (aux_keep), the per-kernel route holds them anyway; X is
+        the aux=None one bit for bit."""
         if keep is None and self.native_connector:
-            feat = self._connector_native(sig_feat, dino_feat, T, image_sizes)
+            kept = None if aux is None else self._aux_keep_alloc(T, sig_feat.shape[0] // T)
+            feat = self._connector_native(sig_feat, dino_feat, T, image_sizes, kept)
+            if aux is not None:
+                self.aux_outputs(kept[0], kept[1], kept[2], T, image_sizes, aux)
             return self.unpad_newline(feat, T, image_sizes)
-        aux = [self.aux_project(sig_feat, 0), self.aux_project(dino_feat, 1)]
-        q = self.sva(aux, T, image_sizes)
+        rows = [self.aux_project(sig_feat, 0), self.aux_project(dino_feat, 1)]
+        ctx = None
+        if aux is not None:
+            ctx = ops.token_mean(rows[0], T, rows[0].shape[0] // T)
+            self.aux_outputs(rows[0], rows[1], ctx, T, image_sizes, aux)
+        q = self.sva(rows, T, image_sizes, ctx)
         feat = self.mm_project(q)
         X, sizes = self.unpad_newline(feat, T, image_sizes)
         if keep is not None:
-            keep.update(aux0=aux[0], aux1=aux[1], sva=q, mm_proj=feat)
+            keep.update(aux0=rows[0], aux1=rows[1], sva=q, mm_proj=feat)
         return X, sizes
 
     # ------------------------------------------------------------------------------------------------ a11-a19
@@ -1105,7 +1181,7 @@ class VideoEncoder:
 
     # ------------------------------------------------------------------------------------------------ top level
     def encode_video(self, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids, audio=None,
-                     frame_cap=224, keep=None, splice=None, video_index=None, info=None, cache=None):
+                     frame_cap=224, keep=None, splice=None, video_index=None, info=None, cache=None, aux=None, image=False):
         """One video: pixels -> emitted visual tokens [n, H] (S0-S10).  `budget_text_len` is the text length used by
         get_max_num_frames (cambrian_arch.py:753-759), `n_text_tokens` the non-image token count (:1499-1505).
         frame_cap: the reference's "in case of OOM" constant 224 of BOTH caps (cambrian_arch.py:907-916 before the towers,
@@ -1114,9 +1190,13 @@ class VideoEncoder:
         info: dict that receives the host-side facts only (frame_indices, selected, seg_indices, final_size, n_visual) - free.
         cache: a FrameCache (new_cache): frames whose content it holds skip the towers and the connector, new ones are stored -
         the result is bit for bit that of cache=None (encode_video_cached).  keep= bypasses the cache (its per-kernel
-        connector form is what produces the stage tensors)."""
+        connector form is what produces the stage tensors).
+        aux: a dict that receives the reference's three aux outputs for the kept frames: features (two
+        [n, r*r, C] tensors), masks (two bool [n, r*r]) and global_context [n, 1, C], n = the frames' un-padded windows; the
+        visual tokens are those of aux=None bit for bit.  With cache= it raises ValueError (the cache keeps connector rows, not
+        aux rows).  image=True: the one frame as a single image - the towers and the connector only, rows [:, :H]."""
         return encode_video_with(self, px_siglip, px_dino, image_size, budget_text_len, n_text_tokens, prompt_ids,
-                                 audio, frame_cap, keep, splice, video_index, info, cache)
+                                 audio, frame_cap, keep, splice, video_index, info, cache, aux, image)
 
     def encode_video_prompts(self, px_siglip, px_dino, image_size, prompts, audio=None, frame_cap=224, video_index=None,
                              infos=None, cache=None, max_prompts=8, pad_fraction=0.25):
@@ -1156,13 +1236,14 @@ class VideoEncoder:
         return compact_features_with(self, fs, gaps)
 
     def encode_features(self, fs, budget_text_len, n_text_tokens, prompt_ids, audio=None, frame_cap=224, splice=None,
-                        video_index=None, info=None, check_signature=True, image=False):
+                        video_index=None, info=None, check_signature=True, image=False, aux=None):
         """encode_video from a FeatureSet instead of pixels: bit for bit what encode_video returns for the pixels the set was
         exported from, whenever that call refines nothing (a band the refinement would re-encode is ranked as stored and
         reported in info["refine_unavailable_pairs"]).  check_signature=False: no comparison of the set's signature with this
-        engine's towers (an engine that holds none).  image=True: a one-frame set as a single image - the connector only."""
+        engine's towers (an engine that holds none).  image=True: a one-frame set as a single image - the connector only.
+        aux: as encode_video's."""
         return encode_features_with(self, fs, budget_text_len, n_text_tokens, prompt_ids, audio, frame_cap, splice, video_index,
-                                    info, check_signature, image)
+                                    info, check_signature, image, aux)
 
     def encode_features_prompts(self, fs, prompts, audio=None, frame_cap=224, video_index=None, infos=None, max_prompts=8,
                                 pad_fraction=0.25, check_signature=True):
@@ -1184,14 +1265,15 @@ class VideoEncoder:
         return px_siglip, px_dino
 
     def encode_frames(self, frames, budget_text_len, n_text_tokens, prompt_ids, audio=None, frame_cap=224, splice=None,
-                      video_index=None, info=None, cache=None, image_size=None, image=False):
+                      video_index=None, info=None, cache=None, image_size=None, image=False, aux=None):
         """encode_video from the decoded frames of a video, uint8 [T0, H, W, 3] as a decoder hands them over (host or device),
         instead of pixels: a1 runs first, on the frame count, and only the frames it keeps are uploaded, resized and normalised
         (pixels_from_frames) - bit for bit what encode_video returns for preprocess.process_images of all frames.  The other
         arguments are encode_video's; image_size defaults to the frames' (H, W), what the reference's drivers pass.  info
-        gains frames_in and frames_resized.  image=True: one frame as a single image - the towers and the connector only."""
+        gains frames_in and frames_resized.  image=True: one frame as a single image - the towers and the connector only.
+        aux: as encode_video's."""
         return encode_frames_with(self, frames, budget_text_len, n_text_tokens, prompt_ids, audio, frame_cap, splice,
-                                  video_index, info, cache, image_size, image)
+                                  video_index, info, cache, image_size, image, aux)
 
     def encode_frames_prompts(self, frames, prompts, audio=None, frame_cap=224, video_index=None, infos=None, cache=None,
                               max_prompts=8, pad_fraction=0.25, image_size=None):

@@ -136,6 +136,26 @@ def window_mask_bytes(side, r, image_size):
     return out
 
 
+def aux_window_map(side, r, image_size):
+    """One frame of rearrange_vision_tower_features_inference(..., unpad=True) (tdc/cambrian_arch.py:601-695) as host
+    geometry: the frame's P = (side*r)^2 aux tokens are viewed as side x side windows of r x r tokens, unpad_image then cuts
+    the WINDOW grid (its dims 1 and 2 are the two `side` axes) by unpad_bounds(side, side, image_size) - quirk D8 included -
+    and the kept windows are listed row-major.  Returns (src, mask, (cur_h, cur_w)): src int [cur_h*cur_w, r*r], the token
+    index of every element within the frame; mask bool [cur_h*cur_w, r*r], unmask_attention_mask's padding mask of the same
+    elements with the all-False rows forced True (:667-669; window_mask_bytes applies it before the cut, which is the same
+    per row).  A size whose un-padding keeps no window gives [0, r*r] arrays."""
+    import numpy as np
+    n = side * r
+    r0, r1, c0, c1 = unpad_bounds(side, side, image_size)
+    wins = [i * side + j for i in range(r0, r1) for j in range(c0, c1)]
+    ab = np.arange(r, dtype=np.int64)
+    inner = (ab[:, None] * n + ab[None, :]).reshape(-1)                                 # element (a, b) of a window
+    origin = np.asarray([(w // side) * r * n + (w % side) * r for w in wins], dtype=np.int64)
+    src = (origin[:, None] + inner[None, :]).reshape(len(wins), r * r)
+    full = np.asarray(window_mask_bytes(side, r, image_size), dtype=bool).reshape(side * side, r * r)
+    return src, full[np.asarray(wins, dtype=np.int64)].reshape(len(wins), r * r), (max(r1 - r0, 0), max(c1 - c0, 0))
+
+
 def unpad_newline_map(side, image_size, frame, newline_table=1, newline_row=0, feat_table=0):
     """gather map (table,row) pairs for one frame of tdc/cambrian_arch.py:1195-1293: side x side tokens, unpadded,
     one newline token appended to every kept row.  feat rows are frame*side*side + y*side + x."""
