@@ -531,6 +531,34 @@ int tdc_preprocess_frames(const unsigned char* frames, int T, int H, int W, int 
                           int ksize, int pad_r, int pad_g, int pad_b, const float* lut, void* out, int out_f32,
                           int dtype, unsigned char* scratch, void* stream);
 
+/* ---- YUV 4:2:0 -> RGB ------------------------------------------------------------------------
+ * T frames of 8-bit 4:2:0 (NV12 / NV21 as a hardware decoder writes them, planar I420 as a software decoder does) ->
+ * rgb uint8 [T, H, W, 3] contiguous, what tdc_preprocess_frames takes.  Pixel (y, x) takes luma Y[y, x] and the chroma
+ * sample (U, V)[y >> 1, x >> 1] (replication); the chroma planes have Hc = (H + 1) / 2 rows of Wc = (W + 1) / 2 samples.
+ * With Y' = Y - y_off, Cb = U - 128, Cr = V - 128, in int32 (>> arithmetic, clip8 to [0, 255]):
+ *     R = clip8((cy*Y' + crv*Cr          + 32768) >> 16)
+ *     G = clip8((cy*Y' - cgu*Cb - cgv*Cr + 32768) >> 16)
+ *     B = clip8((cy*Y' + cbu*Cb          + 32768) >> 16)
+ * The coefficients are the host's: floor(real * 65536 + 0.5) of the matrix and range it chose (preprocess.yuv_coefficients).
+ * One kernel serves every layout through the two chroma pointers and c_step; the host picks its 8-pixel vector form when W,
+ * the pointers, the pitches and the frame strides are multiples of the access widths (8 bytes luma and rgb; chroma 4 bytes
+ * each planar, or 8 bytes at the lower pointer when u and v are neighbours), its 2 x 2 byte form otherwise: same bytes.
+ * TDC_E_BADARG before any launch: a null pointer; T, H or W outside [1, 65535]; c_step not 1 or 2; y_pitch < W; c_pitch <
+ * c_step * Wc; for T > 1 a frame stride that does not clear the plane's last row; y_off not 0 or 16; a coefficient outside
+ * [0, 2^18] (the accumulators then stay below 2^28 for every input byte).
+ * writes: rgb [T, H, W, 3] and nothing else.  reads: W bytes of each of the H luma rows and, of each of the Hc chroma rows,
+ * c_step * (Wc - 1) + 1 bytes from u and from v.  never read: pitch padding, the rows between a plane's end and the next
+ * frame. */
+typedef struct {
+    const unsigned char *y, *u, *v;   /* first byte of frame 0's planes; NV12: u = uv, v = uv + 1 (NV21: the other way) */
+    long long y_frame, c_frame;       /* bytes from one frame's plane to the next frame's (u and v share c_frame) */
+    int y_pitch, c_pitch;             /* bytes per plane row */
+    int c_step;                       /* bytes between chroma samples of a row: 1 planar (I420), 2 interleaved (NV12) */
+} tdc_yuv420_planes;
+typedef struct { int y_off, cy, crv, cgu, cgv, cbu; } tdc_yuv_coef;      /* host struct, passed by value into the kernel */
+int tdc_yuv420_to_rgb(const tdc_yuv420_planes* p, const tdc_yuv_coef* c, int T, int H, int W,
+                      unsigned char* rgb /* [T, H, W, 3] contiguous */, void* stream);
+
 /* ---- BEATs audio front end --------------------------------------------------------------------------
  * kaldi fbank as BEATs.preprocess calls it (tdc/audio_models/beats/BEATs.py:115-129: torchaudio.compliance.kaldi.fbank,
  * 128 mel bins, 16 kHz, 25 ms / 10 ms, povey window, pre-emphasis 0.97, DC removal, dither 0, snip_edges) on B

@@ -1043,7 +1043,9 @@ def frames_size(frames, image_size=None):
 class FrameSource:
     """the decoded frames of a video (uint8 [T0, H, W, 3]) as an encode's source (PixelSource documents the members): a1 has
     run FIRST, on the frame count alone, and only the kept frames are resized and normalised (engine.pixels_from_frames).
-    image_size defaults to the frames' (H, W); frames of another shape raise here, before any engine call."""
+    image_size defaults to the frames' (H, W); frames of another shape raise here, before any engine call.  A
+    preprocess.YuvFrames (4:2:0 planes; .shape is that of the RGB frames they convert to) is a source like any other: the
+    engine converts what it keeps."""
 
     def __init__(self, frames, image_size=None, cache=None):
         self.frames, self.cache = frames, cache

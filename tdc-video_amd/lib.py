@@ -143,6 +143,15 @@ class XattnDesc(C.Structure):
                 ("ctx", C.c_void_p), ("ldctx", C.c_int), ("res16", C.c_int)]
 
 
+class Yuv420Planes(C.Structure):
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("y_frame", C.c_longlong), ("c_frame", C.c_longlong),
+                ("y_pitch", C.c_int), ("c_pitch", C.c_int), ("c_step", C.c_int)]
+
+
+class YuvCoef(C.Structure):
+    _fields_ = [("y_off", C.c_int), ("cy", C.c_int), ("crv", C.c_int), ("cgu", C.c_int), ("cgv", C.c_int), ("cbu", C.c_int)]
+
+
 class ProfRec(C.Structure):
     _fields_ = [("kind", C.c_int), ("tag", C.c_int), ("ms", C.c_float), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
                 ("act", C.c_int), ("res", C.c_int), ("out_f32", C.c_int), ("W", C.c_void_p), ("flops", C.c_double)]
@@ -202,6 +211,8 @@ SIGNATURES = {
     "tdc_preprocess_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p]),
+    "tdc_yuv420_to_rgb": (C.c_int, [C.POINTER(Yuv420Planes), C.POINTER(YuvCoef), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p]),
     "tdc_fbank_frames": (C.c_int, [C.c_longlong]),
     "tdc_fbank": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),

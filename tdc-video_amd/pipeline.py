@@ -1257,7 +1257,9 @@ class VideoEncoder:
         """decoded frames uint8 [T0, H, W, 3] (torch tensor - pageable, pinned or on the device - or numpy array) and the
         ascending host list idx of the frames to keep (None: all) -> (px_siglip, px_dino) of the kept frames in the engine's
         `dtype`, bit for bit preprocess.process_images(frames[idx], dtype, frame_towers): the reference's process_images on the
-        device.  Only the kept frames are uploaded and resized (preprocess.preprocess_selected)."""
+        device.  Only the kept frames are uploaded and resized (preprocess.preprocess_selected).  frames may also be a
+        preprocess.YuvFrames (NV12 / I420 planes): the kept frames' planes are uploaded and converted to
+        RGB on the device in front of the same resize, and `frames[idx]` above reads as the RGB frames they convert to."""
         if len(self.frame_towers) != 2:
             raise ValueError("frame_towers is a pair of {R, mean, std} dicts (SigLIP, DINOv2), got %d" % len(self.frame_towers))
         px_siglip, px_dino = preprocess.preprocess_selected(frames, idx, self.frame_towers, self.dtype, self.frame_slab,
@@ -1271,18 +1273,21 @@ class VideoEncoder:
         (pixels_from_frames) - bit for bit what encode_video returns for preprocess.process_images of all frames.  The other
         arguments are encode_video's; image_size defaults to the frames' (H, W), what the reference's drivers pass.  info
         gains frames_in and frames_resized.  image=True: one frame as a single image - the towers and the connector only.
-        aux: as encode_video's."""
+        aux: as encode_video's.  frames may be a preprocess.YuvFrames (4:2:0 planes as the decoder wrote them): the result is
+        that of the RGB frames the planes convert to."""
         return encode_frames_with(self, frames, budget_text_len, n_text_tokens, prompt_ids, audio, frame_cap, splice,
                                   video_index, info, cache, image_size, image, aux)
 
     def encode_frames_prompts(self, frames, prompts, audio=None, frame_cap=224, video_index=None, infos=None, cache=None,
                               max_prompts=8, pad_fraction=0.25, image_size=None):
-        """encode_video_prompts from decoded frames: one result per prompt, bit for bit what encode_frames returns for it"""
+        """encode_video_prompts from decoded frames (uint8 RGB or a preprocess.YuvFrames): one result per prompt, bit for bit
+        what encode_frames returns for it"""
         return encode_frames_prompts_with(self, frames, prompts, audio, frame_cap, video_index, infos, cache, max_prompts,
                                           pad_fraction, image_size)
 
     def export_features_from_frames(self, frames, store="f16", image_size=None, slab=None, gaps=None):
         """export_features from decoded frames: every frame, preprocessed and run through the towers `slab` frames at a time
         (default encode.EXPORT_FRAMES_SLAB; the rows do not depend on it) - the set export_features gives for
-        preprocess.process_images of the frames, bit for bit, without the pixels of all frames ever being resident"""
+        preprocess.process_images of the frames, bit for bit, without the pixels of all frames ever being resident.  frames may
+        be a preprocess.YuvFrames."""
         return export_features_from_frames_with(self, frames, store, image_size, slab, gaps)

@@ -142,22 +142,221 @@ def selected_frames(frames, idx, device):
     return frames.to(device, non_blocking=True), frames.numel()
 
 
+# ---- YUV 4:2:0 frames ------------------------------------------------------------------------------
+YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}      # (Kr, Kb)
+
+
+def yuv_coefficients(matrix="bt601", full_range=False):
+    """(y_off, cy, crv, cgu, cgv, cbu) of tdc_yuv420_to_rgb: floor(real * 65536 + 0.5) of the matrix's real coefficients, in
+    double precision.  Limited range: luma 16 .. 235, chroma 16 .. 240; full range: 0 .. 255 both."""
+    if matrix not in YUV_MATRICES:
+        raise ValueError("matrix must be one of %s, got %r" % (sorted(YUV_MATRICES), matrix))
+    if not isinstance(full_range, bool):
+        raise ValueError("full_range must be True / False, got %r" % (full_range,))
+    kr, kb = YUV_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    ys, cs = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
+    real = (ys, 2 * (1 - kr) * cs, 2 * (1 - kb) * kb / kg * cs, 2 * (1 - kr) * kr / kg * cs, 2 * (1 - kb) * cs)
+    return (0 if full_range else 16,) + tuple(int(math.floor(r * 65536 + 0.5)) for r in real)
+
+
+def _plane(p, name):
+    """one plane as a uint8 torch tensor [T0, rows, bytes] over the same memory, the last dimension dense"""
+    if isinstance(p, np.ndarray):
+        if p.dtype != np.uint8:
+            raise ValueError("%s must be uint8, got %s" % (name, p.dtype))
+        if any(s < 0 for s in p.strides):
+            raise ValueError("%s has a negative stride" % name)
+        p = torch.from_numpy(p)
+    if not torch.is_tensor(p):
+        raise ValueError("%s must be a uint8 torch tensor or numpy array, got %s" % (name, type(p).__name__))
+    if p.dtype != torch.uint8 or p.dim() != 3 or 0 in p.shape:
+        raise ValueError("%s must be uint8 [T0, rows, bytes] with no empty dimension, got %s %s" % (name, p.dtype, tuple(p.shape)))
+    if p.stride(2) != 1 and p.shape[2] > 1:
+        raise ValueError("%s: the last dimension must be dense, got stride %d" % (name, p.stride(2)))
+    return p
+
+
+class YuvFrames:
+    """T0 frames of 8-bit YUV 4:2:0 of one size, described and not copied: what a decoder hands over before any colour
+    conversion.  y is [T0, H, >= W]; the chroma planes have Hc = (H + 1) // 2 rows of Wc = (W + 1) // 2 samples -
+    interleaved uv [T0, Hc, >= 2 * Wc] bytes (nv12) or planar u, v [T0, Hc, >= Wc] with equal strides (i420).  Planes are
+    uint8 torch tensors, all on the host or all on one device, or numpy arrays; row and frame strides may exceed the plane
+    (a decoder surface with a pitch and an aligned height, taken as a view) and rows may be longer than `width` (default: the
+    luma row length).  matrix "bt601" / "bt709" and full_range choose the coefficients of the conversion (yuv_coefficients),
+    which is the stated formula of include/tdc_hip.h and no decoder library's.  .shape is (T0, H, W, 3), that of the RGB
+    frames the planes convert to; yuv[a:b] is a YuvFrames over the same memory."""
+
+    def __init__(self, y, chroma, c_step, width=None, matrix="bt601", full_range=False):
+        if c_step not in (1, 2):
+            raise ValueError("c_step is 1 (planar u, v) or 2 (interleaved uv), got %r" % (c_step,))
+        names = ("uv",) if c_step == 2 else ("u", "v")
+        if len(chroma) != len(names):
+            raise ValueError("c_step %r takes %d chroma plane(s), got %d" % (c_step, len(names), len(chroma)))
+        self.y = _plane(y, "y")
+        self.chroma = tuple(_plane(c, n) for c, n in zip(chroma, names))
+        self.c_step, self.matrix, self.full_range = c_step, matrix, full_range
+        self.coef = yuv_coefficients(matrix, full_range)
+        T0, H, pitch = self.y.shape
+        W = pitch if width is None else int(width)
+        if not 1 <= W <= pitch:
+            raise ValueError("width must be in [1, %d] (the y rows), got %r" % (pitch, width))
+        if T0 > 65535 or H > 65535 or W > 65535:
+            raise ValueError("y %s: at most 65535 frames, rows and pixels per row" % (tuple(self.y.shape),))
+        Hc, Wc = (H + 1) // 2, (W + 1) // 2
+        for c, n in zip(self.chroma, names):
+            if c.shape[0] != T0 or c.shape[1] != Hc or c.shape[2] < c_step * Wc:
+                raise ValueError("%s must be [%d, %d, >= %d] for y %s and width %d, got %s"
+                                 % (n, T0, Hc, c_step * Wc, tuple(self.y.shape), W, tuple(c.shape)))
+            if c.device != self.y.device:
+                raise ValueError("%s is on %s, y on %s: the planes must share one device" % (n, c.device, self.y.device))
+        if len(self.chroma) == 2 and self.chroma[0].stride() != self.chroma[1].stride():
+            raise ValueError("u and v must have equal strides, got %s and %s" % (self.chroma[0].stride(), self.chroma[1].stride()))
+        self.shape = (T0, H, W, 3)
+
+    @classmethod
+    def nv12(cls, y, uv, width=None, matrix="bt601", full_range=False):
+        return cls(y, (uv,), 2, width, matrix, full_range)
+
+    @classmethod
+    def i420(cls, y, u, v, width=None, matrix="bt601", full_range=False):
+        return cls(y, (u, v), 1, width, matrix, full_range)
+
+    @property
+    def is_cuda(self):
+        return self.y.is_cuda
+
+    def __getitem__(self, s):
+        if not isinstance(s, slice) or s.step not in (None, 1):
+            raise TypeError("YuvFrames takes a slice of frames a:b, got %r" % (s,))
+        return YuvFrames(self.y[s], tuple(c[s] for c in self.chroma), self.c_step, self.shape[2], self.matrix, self.full_range)
+
+    def planes(self):
+        """the read set as views: (y [T0, H, W], one or two chroma planes [T0, Hc, c_step * Wc]) - the pitch padding cut off"""
+        W = self.shape[2]
+        return (self.y[:, :, :W],) + tuple(c[:, :, :self.c_step * ((W + 1) // 2)] for c in self.chroma)
+
+    def kernel_views(self, planes):
+        """(y, u, v) as ops.yuv420_to_rgb takes them, from `planes` laid out like planes()"""
+        return (planes[0], planes[1], planes[1][:, :, 1:]) if self.c_step == 2 else tuple(planes)
+
+
+def is_yuv_frames(x):
+    """a YuvFrames, recognised by its members (the package can be imported under two names: not by isinstance)"""
+    return all(hasattr(x, k) for k in ("y", "chroma", "c_step", "coef", "shape")) and not torch.is_tensor(x)
+
+
+def gather_planes(yuv, idx, pin=True):
+    """the frames idx (check_indices; not None) of host planes, gathered plane by plane with the pitch padding removed into
+    ONE staging tensor (pinned when `pin`) -> (the staged planes as views of it laid out like yuv.planes(), the staging
+    tensor).  Frames outside idx and bytes outside planes() are never read.  The staging holds T * (H*W + 2*Hc*Wc) bytes."""
+    sel = torch.tensor(idx)
+    src = yuv.planes()
+    sizes = [len(idx) * p.shape[1] * p.shape[2] for p in src]
+    stage = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=pin)
+    out, at = [], 0
+    for p, n in zip(src, sizes):
+        dst = stage[at:at + n].view(len(idx), p.shape[1], p.shape[2])
+        torch.index_select(p, 0, sel, out=dst)
+        out.append(dst)
+        at += n
+    return out, stage
+
+
+def selected_planes(yuv, idx, device):
+    """the frames idx (check_indices) of a YuvFrames as planes on `device`, laid out like yuv.planes() -> (planes, bytes
+    uploaded).  Host planes: the kept frames go through gather_planes and one upload of exactly their bytes (dense pinned
+    planes with every frame kept are uploaded from where they lie).  Device planes: used in place through their strides when
+    every frame is kept, gathered on the device otherwise."""
+    src = yuv.planes()
+    if yuv.is_cuda:
+        if idx is not None:
+            sel = torch.tensor(idx, device=yuv.y.device)
+            src = [torch.index_select(p, 0, sel) for p in src]
+        return [p.to(device) for p in src], 0
+    if idx is None and all(p.is_pinned() and p.is_contiguous() for p in src):
+        return [p.to(device, non_blocking=True) for p in src], sum(p.numel() for p in src)
+    staged, stage = gather_planes(yuv, list(range(yuv.shape[0])) if idx is None else idx)
+    dev = stage.to(device, non_blocking=True)
+    out, at = [], 0
+    for p in staged:
+        out.append(dev[at:at + p.numel()].view(p.shape))
+        at += p.numel()
+    return out, stage.numel()
+
+
+def _preprocess_selected_yuv(yuv, idx, towers, dtype, slab, device, out, stats):
+    """preprocess_selected for a YuvFrames: per slab of kept frames ONE tdc_yuv420_to_rgb launch into a [slab, H, W, 3] RGB
+    scratch, then tdc_preprocess_frames per tower on that scratch - the RGB path's launches on the frames the planes convert
+    to.  Both scratches are slab-sized and serve the whole video."""
+    idx = check_indices(idx, yuv.shape[0])
+    _check_dtype_slab(dtype, slab)
+    if device is None:
+        device = yuv.y.device if yuv.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    T0, H, W, _ = yuv.shape
+    planes, uploaded = selected_planes(yuv, idx, device)
+    y, u, v = yuv.kernel_views(planes)
+    T = y.shape[0]
+    if stats is not None:
+        stats.update(frames_in=T0, frames_resized=T, bytes_uploaded=uploaded)
+    out = _outputs(out, towers, T, dtype, device)
+    lib = L.load()
+    n0 = min(slab, T)
+    nscr = max(lib.tdc_preprocess_scratch_bytes(n0, H, W, t["R"]) for t in towers)
+    scratch = torch.empty(max(nscr, 1), dtype=torch.uint8, device=device)
+    rgb = torch.empty((n0, H, W, 3), dtype=torch.uint8, device=device)
+    tables = [_tables(max(H, W), t["R"], t["mean"], t["std"], device) for t in towers]
+    with torch.cuda.device(device):
+        for s in range(0, T, slab):
+            n = min(slab, T - s)
+            ops.yuv420_to_rgb(y[s:s + n], u[s:s + n], v[s:s + n], yuv.c_step, yuv.coef, H, W, out=rgb[:n])
+            for t, o, (bounds, coeffs, lut) in zip(towers, out, tables):
+                pad = [int(x * 255) for x in t["mean"]]   # expand2square background (tdc/mm_datautils.py:302-304)
+                L.check(lib.tdc_preprocess_frames(ops._ptr(rgb), n, H, W, t["R"], ops._ptr(bounds), ops._ptr(coeffs),
+                                                  coeffs.shape[1], pad[0], pad[1], pad[2], ops._ptr(lut), ops._ptr(o[s:s + n]), 0,
+                                                  ops._dtcode(dtype), ops._ptr(scratch), ops._stream()), "tdc_preprocess_frames")
+    return [o[:T] for o in out]
+
+
+def _check_dtype_slab(dtype, slab):
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError("preprocess_selected writes float16 or bfloat16 pixels, got %s" % (dtype,))
+    if isinstance(slab, bool) or not isinstance(slab, int) or not 1 <= slab <= 65535:
+        raise ValueError("slab must be a frame count in [1, 65535], got %r" % (slab,))
+
+
+def _outputs(out, towers, T, dtype, device):
+    """one [T, 3, R, R] tensor per tower: new ones, or the caller's `out` checked against the towers"""
+    if out is None:
+        return [torch.empty(T, 3, t["R"], t["R"], device=device, dtype=dtype) for t in towers]
+    out = list(out)
+    if len(out) != len(towers):
+        raise ValueError("out holds %d tensors for %d towers" % (len(out), len(towers)))
+    for o, t in zip(out, towers):
+        if not (torch.is_tensor(o) and o.device == device and o.dtype == dtype and o.is_contiguous() and o.dim() == 4
+                and o.shape[0] >= T and tuple(o.shape[1:]) == (3, t["R"], t["R"])):
+            raise ValueError("out must be contiguous %s [>= %d, 3, %d, %d] tensors on %s" % (dtype, T, t["R"], t["R"], device))
+    return out
+
+
 def preprocess_selected(frames, idx, towers=(SIGLIP, DINOV2), dtype=torch.float16, slab=64, device=None, out=None, stats=None):
     """process_images(frames[idx], dtype, towers) for a caller that holds a whole decoded video: frames uint8 [T0, H, W, 3]
     (a torch tensor - pageable, pinned or on the device - or a numpy array), idx the ascending host list of the frames to
     keep (encode.frame_indices; None: all) -> one [T, 3, R, R] tensor per tower on `device` (default: the frames' device, or
     the current one), bit for bit what process_images gives for the kept frames.
+    frames may also be a YuvFrames (4:2:0 planes): its kept frames are converted to RGB on the device,
+    slab by slab, in front of the same resize - the result is what the RGB frames the planes convert to give.
     The kept frames are resized in slabs of at most `slab` frames: one tdc_preprocess_frames call per slab and tower writes its
     slice of the output, and ONE scratch of tdc_preprocess_scratch_bytes(slab, H, W, R) bytes serves every slab and tower, so the
     scratch does not grow with the video.  Frames are resized independently: the result does not depend on `slab`.
     out: one preallocated contiguous [>= T, 3, R, R] tensor of `dtype` per tower - rows [0, T) are written, nothing else, and
     the views out[j][:T] are returned.  stats: a dict that receives frames_in, frames_resized and bytes_uploaded."""
+    if is_yuv_frames(frames):
+        return _preprocess_selected_yuv(frames, idx, towers, dtype, slab, device, out, stats)
     frames = check_frames(frames)
     idx = check_indices(idx, frames.shape[0])       # on the host, before anything is launched
-    if dtype not in (torch.float16, torch.bfloat16):
-        raise ValueError("preprocess_selected writes float16 or bfloat16 pixels, got %s" % (dtype,))
-    if isinstance(slab, bool) or not isinstance(slab, int) or not 1 <= slab <= 65535:
-        raise ValueError("slab must be a frame count in [1, 65535], got %r" % (slab,))
+    _check_dtype_slab(dtype, slab)
     if device is None:
         device = frames.device if frames.is_cuda else torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
@@ -166,16 +365,7 @@ def preprocess_selected(frames, idx, towers=(SIGLIP, DINOV2), dtype=torch.float1
     T = kept.shape[0]
     if stats is not None:
         stats.update(frames_in=T0, frames_resized=T, bytes_uploaded=uploaded)
-    if out is None:
-        out = [torch.empty(T, 3, t["R"], t["R"], device=device, dtype=dtype) for t in towers]
-    else:
-        out = list(out)
-        if len(out) != len(towers):
-            raise ValueError("out holds %d tensors for %d towers" % (len(out), len(towers)))
-        for o, t in zip(out, towers):
-            if not (torch.is_tensor(o) and o.device == device and o.dtype == dtype and o.is_contiguous() and o.dim() == 4
-                    and o.shape[0] >= T and tuple(o.shape[1:]) == (3, t["R"], t["R"])):
-                raise ValueError("out must be contiguous %s [>= %d, 3, %d, %d] tensors on %s" % (dtype, T, t["R"], t["R"], device))
+    out = _outputs(out, towers, T, dtype, device)
     lib = L.load()
     n0 = min(slab, T)
     nscr = max(lib.tdc_preprocess_scratch_bytes(n0, H, W, t["R"]) for t in towers)
