@@ -559,6 +559,45 @@ typedef struct { int y_off, cy, crv, cgu, cgv, cbu; } tdc_yuv_coef;      /* host
 int tdc_yuv420_to_rgb(const tdc_yuv420_planes* p, const tdc_yuv_coef* c, int T, int H, int W,
                       unsigned char* rgb /* [T, H, W, 3] contiguous */, void* stream);
 
+/* ---- YUV -> RGB at 8, 10 and 12 bits, 4:2:0 / 4:2:2 / 4:4:4 -----------------------------------
+ * The surfaces the entry above does not take: P010 / P012 / P016 (16-bit words, the sample in the high bits), planar or
+ * interleaved yuv4xxp10le / 12le (the sample in the low bits), 8-bit 4:2:2 and 4:4:4.  Same output, same replication, and at
+ * bits = 8, 4:2:0 the same bytes as the entry above.  With s = bits - 8:
+ *   sample   a byte at bits = 8, else a little-endian 16-bit word w taken as (w >> shift) & (2^bits - 1), shift = 16 - bits
+ *            when msb_aligned and 0 otherwise: the bits outside the sample are ignored, whatever they hold
+ *   chroma   pixel (y, x) takes (U, V)[y >> sub_y, x >> sub_x]; the chroma planes have Hc = (H + sub_y) >> sub_y rows of
+ *            Wc = (W + sub_x) >> sub_x samples; (sub_x, sub_y) is (1, 1) 4:2:0, (1, 0) 4:2:2 or (0, 0) 4:4:4
+ *   Y' = Y - y_off, Cb = U - 2^(bits-1), Cr = V - 2^(bits-1), in int32 (>> arithmetic, clip8 to [0, 255]):
+ *     R = clip8((cy*Y' + crv*Cr          + 2^(15+s)) >> (16+s))
+ *     G = clip8((cy*Y' - cgu*Cb - cgv*Cr + 2^(15+s)) >> (16+s))
+ *     B = clip8((cy*Y' + cbu*Cb          + 2^(15+s)) >> (16+s))
+ * The coefficients are the host's (preprocess.yuv_coefficients with its bits argument); y_off is 0 or 16 << s.  The transfer
+ * function is not touched: PQ or HLG samples come out as PQ or HLG bytes.
+ * A thread owns (1 + sub_y) rows, so a chroma sample is loaded once.  The host picks the 8-pixel vector form when W % 8 == 0
+ * and the pointers, the pitches and (T > 1) the frame strides are multiples of the access widths - luma 8 bytes (bits = 8) or
+ * 16 (words), rgb 8, chroma the 8 >> sub_x samples of one plane in one load, or that many pairs at the lower pointer when u
+ * and v are neighbours (32 bytes: aligned to 16) - and the form of one sample per load otherwise: same bytes.
+ * TDC_E_BADARG before any launch: what the entry above refuses (with the pitches and frame strides measured in bytes); bits
+ * not 8, 10 or 12; another (sub_x, sub_y); msb_aligned not 0 or 1, or 1 at bits = 8; c_step not one or two sample sizes;
+ * y_off not 0 or 16 << s; at 16-bit samples an odd pointer, pitch, frame stride or c_step; y_pitch below W samples, c_pitch
+ * below c_step * Wc; for T > 1 a frame stride that does not clear the plane's last row; a coefficient outside [0, 2^18], or
+ * cy * 2^bits + max(crv, cgu + cgv, cbu) * 2^(bits-1) + 2^(15+s) >= 2^31 (an accumulator could leave int32; coefficients
+ * inside [0, 2^18] stay below 2^30 + 2^29 + 2^19 at 12 bits, so the first check already implies this one).
+ * writes: rgb [T, H, W, 3] and nothing else.  reads: the W samples of each of the H luma rows and, of each of the Hc chroma
+ * rows, c_step * (Wc - 1) + sample size bytes from u and from v.  never read: pitch padding, the rows between a plane's end
+ * and the next frame. */
+typedef struct {
+    const unsigned char *y, *u, *v;   /* first byte of frame 0's planes; interleaved: u and v one sample apart, either order */
+    long long y_frame, c_frame;       /* bytes from one frame's plane to the next frame's (u and v share c_frame) */
+    int y_pitch, c_pitch;             /* bytes per plane row */
+    int c_step;                       /* bytes between chroma samples of a row: one sample size planar, two interleaved */
+    int bits;                         /* significant bits of a sample: 8 (bytes), 10 or 12 (16-bit words) */
+    int msb_aligned;                  /* 16-bit words: 1 = the sample is the word's high bits (P010), 0 = its low bits */
+    int sub_x, sub_y;                 /* chroma sub-sampling shifts */
+} tdc_yuv_planes;
+int tdc_yuv_to_rgb(const tdc_yuv_planes* p, const tdc_yuv_coef* c, int T, int H, int W,
+                   unsigned char* rgb /* [T, H, W, 3] contiguous */, void* stream);
+
 /* ---- BEATs audio front end --------------------------------------------------------------------------
  * kaldi fbank as BEATs.preprocess calls it (tdc/audio_models/beats/BEATs.py:115-129: torchaudio.compliance.kaldi.fbank,
  * 128 mel bins, 16 kHz, 25 ms / 10 ms, povey window, pre-emphasis 0.97, DC removal, dither 0, snip_edges) on B

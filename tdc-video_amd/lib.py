@@ -148,6 +148,12 @@ class Yuv420Planes(C.Structure):
                 ("y_pitch", C.c_int), ("c_pitch", C.c_int), ("c_step", C.c_int)]
 
 
+class YuvPlanes(C.Structure):
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("y_frame", C.c_longlong), ("c_frame", C.c_longlong),
+                ("y_pitch", C.c_int), ("c_pitch", C.c_int), ("c_step", C.c_int), ("bits", C.c_int), ("msb_aligned", C.c_int),
+                ("sub_x", C.c_int), ("sub_y", C.c_int)]
+
+
 class YuvCoef(C.Structure):
     _fields_ = [("y_off", C.c_int), ("cy", C.c_int), ("crv", C.c_int), ("cgu", C.c_int), ("cgv", C.c_int), ("cbu", C.c_int)]
 
@@ -213,6 +219,7 @@ SIGNATURES = {
                                         C.c_void_p]),
     "tdc_yuv420_to_rgb": (C.c_int, [C.POINTER(Yuv420Planes), C.POINTER(YuvCoef), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p]),
+    "tdc_yuv_to_rgb": (C.c_int, [C.POINTER(YuvPlanes), C.POINTER(YuvCoef), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdc_fbank_frames": (C.c_int, [C.c_longlong]),
     "tdc_fbank": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),

@@ -729,6 +729,38 @@ def yuv420_to_rgb(y, u, v, c_step, coef, H, W, out=None):
     return out
 
 
+YUV_SUBSAMPLING = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}     # name -> (sub_x, sub_y)
+
+
+def yuv_to_rgb(y, u, v, c_step, coef, H, W, bits=8, msb_aligned=False, subsampling="420", out=None):
+    """T frames of 8-, 10- or 12-bit YUV 4:2:0 / 4:2:2 / 4:4:4 -> rgb uint8 [T, H, W, 3] (tdc_yuv_to_rgb).
+    The views are yuv420_to_rgb's, counted in samples: uint8 at bits = 8, else 16-bit words (torch.int16 as a bit pattern, or
+    torch.uint16) whose high (msb_aligned, P010) or low `bits` bits are the sample.  y [T, >= H, >= W] and u, v
+    [T, >= Hc, >= c_step * (Wc - 1) + 1] with Hc = (H + sub_y) >> sub_y, Wc = (W + sub_x) >> sub_x; c_step 1: two planes;
+    c_step 2: interleaved samples, u and v views of one plane one sample apart.  coef = (y_off, cy, crv, cgu, cgv, cbu) of
+    this bit depth, e.g. preprocess.yuv_coefficients(matrix, full_range, bits)."""
+    assert subsampling in YUV_SUBSAMPLING, "subsampling must be one of %s" % sorted(YUV_SUBSAMPLING)
+    sub_x, sub_y = YUV_SUBSAMPLING[subsampling]
+    Hc, Wc = (H + sub_y) >> sub_y, (W + sub_x) >> sub_x
+    T = y.shape[0]
+    words = tuple(d for d in (torch.int16, getattr(torch, "uint16", None)) if d is not None)
+    for t, rows, cols, name in ((y, H, W, "y"), (u, Hc, c_step * (Wc - 1) + 1, "u"), (v, Hc, c_step * (Wc - 1) + 1, "v")):
+        assert t.is_cuda and t.dim() == 3 and t.stride(2) == 1 and (t.dtype == torch.uint8 if bits == 8 else t.dtype in words), \
+            "%s must be a [T, rows, samples] CUDA view of uint8 (bits = 8) or 16-bit words" % name
+        assert t.shape[0] == T and t.shape[1] >= rows and t.shape[2] >= cols, "%s %s is smaller than the frames" % (name, tuple(t.shape))
+    assert u.stride() == v.stride(), "u and v must share their strides"
+    if out is None:
+        out = torch.empty(T, H, W, 3, device=y.device, dtype=torch.uint8)
+    assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (T, H, W, 3) and out.is_contiguous()
+    b = y.element_size()
+    # torch leaves the stride of a size-1 dimension arbitrary: one frame has no frame stride, one row the dense pitch
+    p = L.YuvPlanes(y.data_ptr(), u.data_ptr(), v.data_ptr(), b * y.stride(0) if T > 1 else 0, b * u.stride(0) if T > 1 else 0,
+                    b * (y.stride(1) if y.shape[1] > 1 else W), b * (u.stride(1) if u.shape[1] > 1 else c_step * Wc), b * c_step,
+                    bits, int(msb_aligned), sub_x, sub_y)
+    L.check(L.load().tdc_yuv_to_rgb(C.byref(p), C.byref(L.YuvCoef(*coef)), T, H, W, _ptr(out), _stream()), "tdc_yuv_to_rgb")
+    return out
+
+
 def relpos_gate(q, rows, heads, head_dim, w2, b2, grep_a, out=None):
     """q: [rows, ld] 16-bit view (un-scaled q_proj output) -> gate fp32 [rows, heads]."""
     assert q.is_cuda and q.dim() == 2 and q.stride(1) == 1 and q.shape[0] >= rows and q.shape[1] >= heads * head_dim

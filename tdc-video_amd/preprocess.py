@@ -142,68 +142,97 @@ def selected_frames(frames, idx, device):
     return frames.to(device, non_blocking=True), frames.numel()
 
 
-# ---- YUV 4:2:0 frames ------------------------------------------------------------------------------
-YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}      # (Kr, Kb)
+# ---- YUV frames (DESIGN.md sections 19 and 20) ----------------------------------------------------------------------------
+YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020": (0.2627, 0.0593)}      # (Kr, Kb); bt2020: non-constant luminance
+YUV_BITS = (8, 10, 12)
 
 
-def yuv_coefficients(matrix="bt601", full_range=False):
-    """(y_off, cy, crv, cgu, cgv, cbu) of tdc_yuv420_to_rgb: floor(real * 65536 + 0.5) of the matrix's real coefficients, in
-    double precision.  Limited range: luma 16 .. 235, chroma 16 .. 240; full range: 0 .. 255 both."""
+def yuv_coefficients(matrix="bt601", full_range=False, bits=8):
+    """(y_off, cy, crv, cgu, cgv, cbu) of tdc_yuv420_to_rgb (bits = 8) and tdc_yuv_to_rgb: floor(real * 65536 + 0.5) of the
+    matrix's real coefficients, in double precision.  Limited range: luma 16 .. 235 and chroma 16 .. 240, times 2^(bits - 8) -
+    the scales 255/219 and 255/224 and so the coefficients are those of 8 bits at every depth, y_off is 16 << (bits - 8).
+    Full range: 0 .. 2^bits - 1 both, one scale 255 * 2^(bits - 8) / (2^bits - 1), which is 1 at 8 bits."""
     if matrix not in YUV_MATRICES:
         raise ValueError("matrix must be one of %s, got %r" % (sorted(YUV_MATRICES), matrix))
     if not isinstance(full_range, bool):
         raise ValueError("full_range must be True / False, got %r" % (full_range,))
+    if isinstance(bits, bool) or bits not in YUV_BITS:
+        raise ValueError("bits must be one of %s, got %r" % (YUV_BITS, bits))
+    s = bits - 8
     kr, kb = YUV_MATRICES[matrix]
     kg = 1.0 - kr - kb
-    ys, cs = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
+    full = 255.0 * (1 << s) / ((1 << bits) - 1)
+    ys, cs = (full, full) if full_range else (255.0 / 219.0, 255.0 / 224.0)
     real = (ys, 2 * (1 - kr) * cs, 2 * (1 - kb) * kb / kg * cs, 2 * (1 - kr) * kr / kg * cs, 2 * (1 - kb) * cs)
-    return (0 if full_range else 16,) + tuple(int(math.floor(r * 65536 + 0.5)) for r in real)
+    return (0 if full_range else 16 << s,) + tuple(int(math.floor(r * 65536 + 0.5)) for r in real)
 
 
-def _plane(p, name):
-    """one plane as a uint8 torch tensor [T0, rows, bytes] over the same memory, the last dimension dense"""
+def _plane(p, name, bits=8):
+    """one plane as a torch tensor [T0, rows, samples] over the same memory, the last dimension dense: uint8 at bits = 8;
+    16-bit words (numpy uint16, torch.uint16 or torch.int16) as torch.int16, a bit pattern the kernel masks its sample out of"""
+    kind = "uint8" if bits == 8 else "uint16 (or torch.int16 as a bit pattern)"
     if isinstance(p, np.ndarray):
-        if p.dtype != np.uint8:
-            raise ValueError("%s must be uint8, got %s" % (name, p.dtype))
+        if p.dtype != (np.uint8 if bits == 8 else np.uint16):
+            raise ValueError("%s must be %s at %d bits, got %s" % (name, kind, bits, p.dtype))
         if any(s < 0 for s in p.strides):
             raise ValueError("%s has a negative stride" % name)
-        p = torch.from_numpy(p)
+        p = torch.from_numpy(p if bits == 8 else p.view(np.int16))
     if not torch.is_tensor(p):
-        raise ValueError("%s must be a uint8 torch tensor or numpy array, got %s" % (name, type(p).__name__))
-    if p.dtype != torch.uint8 or p.dim() != 3 or 0 in p.shape:
-        raise ValueError("%s must be uint8 [T0, rows, bytes] with no empty dimension, got %s %s" % (name, p.dtype, tuple(p.shape)))
+        raise ValueError("%s must be a %s torch tensor or numpy array, got %s" % (name, kind, type(p).__name__))
+    if bits != 8 and p.dtype == getattr(torch, "uint16", None):
+        p = p.view(torch.int16)
+    if p.dtype != (torch.uint8 if bits == 8 else torch.int16) or p.dim() != 3 or 0 in p.shape:
+        raise ValueError("%s must be %s [T0, rows, samples] with no empty dimension at %d bits, got %s %s"
+                         % (name, kind, bits, p.dtype, tuple(p.shape)))
     if p.stride(2) != 1 and p.shape[2] > 1:
         raise ValueError("%s: the last dimension must be dense, got stride %d" % (name, p.stride(2)))
     return p
 
 
 class YuvFrames:
-    """T0 frames of 8-bit YUV 4:2:0 of one size, described and not copied: what a decoder hands over before any colour
-    conversion.  y is [T0, H, >= W]; the chroma planes have Hc = (H + 1) // 2 rows of Wc = (W + 1) // 2 samples -
-    interleaved uv [T0, Hc, >= 2 * Wc] bytes (nv12) or planar u, v [T0, Hc, >= Wc] with equal strides (i420).  Planes are
+    """T0 frames of YUV of one size, described and not copied: what a decoder hands over before any colour conversion.
+    y is [T0, H, >= W]; the chroma planes have Hc = (H + 1) // 2 rows of Wc = (W + 1) // 2 samples -
+    interleaved uv [T0, Hc, >= 2 * Wc] samples (nv12) or planar u, v [T0, Hc, >= Wc] with equal strides (i420).  Planes are
     uint8 torch tensors, all on the host or all on one device, or numpy arrays; row and frame strides may exceed the plane
     (a decoder surface with a pitch and an aligned height, taken as a view) and rows may be longer than `width` (default: the
-    luma row length).  matrix "bt601" / "bt709" and full_range choose the coefficients of the conversion (yuv_coefficients),
-    which is the stated formula of include/tdc_hip.h and no decoder library's.  .shape is (T0, H, W, 3), that of the RGB
-    frames the planes convert to; yuv[a:b] is a YuvFrames over the same memory."""
+    luma row length).  matrix "bt601" / "bt709" / "bt2020" and full_range choose the coefficients of the conversion
+    (yuv_coefficients), which is the stated formula of include/tdc_hip.h and no decoder library's; the transfer function is
+    not touched (PQ / HLG content stays PQ / HLG: no tone mapping).  .shape is (T0, H, W, 3), that of the RGB frames the
+    planes convert to; yuv[a:b] is a YuvFrames over the same memory.
+    Beyond 8-bit 4:2:0: bits 10 or 12 - the planes are 16-bit words (numpy uint16, torch.uint16 where
+    torch has it, or torch.int16 as a bit pattern; kept as torch.int16 views), the sample in their high bits (msb_aligned: P010,
+    P012, P016) or their low bits (yuv420p10le and its kin); whatever the other bits hold is ignored.  subsampling "422":
+    Hc = H, "444": Hc = H and Wc = W.  bt2020 is taken at 10 and 12 bits, the depths it is defined for."""
 
-    def __init__(self, y, chroma, c_step, width=None, matrix="bt601", full_range=False):
+    def __init__(self, y, chroma, c_step, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False,
+                 subsampling="420"):
         if c_step not in (1, 2):
             raise ValueError("c_step is 1 (planar u, v) or 2 (interleaved uv), got %r" % (c_step,))
         names = ("uv",) if c_step == 2 else ("u", "v")
         if len(chroma) != len(names):
             raise ValueError("c_step %r takes %d chroma plane(s), got %d" % (c_step, len(names), len(chroma)))
-        self.y = _plane(y, "y")
-        self.chroma = tuple(_plane(c, n) for c, n in zip(chroma, names))
+        if isinstance(bits, bool) or bits not in YUV_BITS:
+            raise ValueError("bits must be one of %s, got %r" % (YUV_BITS, bits))
+        if not isinstance(msb_aligned, bool) or (msb_aligned and bits == 8):
+            raise ValueError("msb_aligned must be True / False, and False at 8 bits, got %r at %d bits" % (msb_aligned, bits))
+        if subsampling not in ops.YUV_SUBSAMPLING:
+            raise ValueError("subsampling must be one of %s, got %r" % (sorted(ops.YUV_SUBSAMPLING), subsampling))
+        if matrix == "bt2020" and bits == 8:
+            raise ValueError("matrix bt2020 is taken at 10 and 12 bits, the depths it is defined for; 8-bit planes take %s"
+                             % sorted(m for m in YUV_MATRICES if m != "bt2020"))
+        self.y = _plane(y, "y", bits)
+        self.chroma = tuple(_plane(c, n, bits) for c, n in zip(chroma, names))
         self.c_step, self.matrix, self.full_range = c_step, matrix, full_range
-        self.coef = yuv_coefficients(matrix, full_range)
+        self.bits, self.msb_aligned, self.subsampling = bits, msb_aligned, subsampling
+        self.sub_x, self.sub_y = ops.YUV_SUBSAMPLING[subsampling]
+        self.coef = yuv_coefficients(matrix, full_range, bits)
         T0, H, pitch = self.y.shape
         W = pitch if width is None else int(width)
         if not 1 <= W <= pitch:
             raise ValueError("width must be in [1, %d] (the y rows), got %r" % (pitch, width))
         if T0 > 65535 or H > 65535 or W > 65535:
             raise ValueError("y %s: at most 65535 frames, rows and pixels per row" % (tuple(self.y.shape),))
-        Hc, Wc = (H + 1) // 2, (W + 1) // 2
+        Hc, Wc = (H + self.sub_y) >> self.sub_y, (W + self.sub_x) >> self.sub_x
         for c, n in zip(self.chroma, names):
             if c.shape[0] != T0 or c.shape[1] != Hc or c.shape[2] < c_step * Wc:
                 raise ValueError("%s must be [%d, %d, >= %d] for y %s and width %d, got %s"
@@ -215,12 +244,36 @@ class YuvFrames:
         self.shape = (T0, H, W, 3)
 
     @classmethod
-    def nv12(cls, y, uv, width=None, matrix="bt601", full_range=False):
-        return cls(y, (uv,), 2, width, matrix, full_range)
+    def nv12(cls, y, uv, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False, subsampling="420"):
+        """a luma plane and one plane of interleaved (u, v) samples: NV12, and NV16 / NV24 with subsampling "422" / "444" """
+        return cls(y, (uv,), 2, width, matrix, full_range, bits, msb_aligned, subsampling)
 
     @classmethod
-    def i420(cls, y, u, v, width=None, matrix="bt601", full_range=False):
-        return cls(y, (u, v), 1, width, matrix, full_range)
+    def i420(cls, y, u, v, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False, subsampling="420"):
+        """three planes: yuv420p, yuv422p, yuv444p and - bits 10 / 12 - their 10le / 12le forms"""
+        return cls(y, (u, v), 1, width, matrix, full_range, bits, msb_aligned, subsampling)
+
+    @classmethod
+    def p010(cls, y, uv, width=None, matrix="bt601", full_range=False):
+        """P010 as a hardware decoder writes it: 4:2:0, 16-bit words, the 10-bit sample in the high bits"""
+        return cls(y, (uv,), 2, width, matrix, full_range, 10, True, "420")
+
+    @classmethod
+    def p016(cls, y, uv, bits, width=None, matrix="bt601", full_range=False):
+        """a P016 surface holding `bits` (10 or 12) significant bits, MSB-aligned; the low bits are ignored"""
+        if isinstance(bits, bool) or bits not in (10, 12):
+            raise ValueError("bits of a P016 surface must be 10 or 12, got %r" % (bits,))
+        return cls(y, (uv,), 2, width, matrix, full_range, bits, True, "420")
+
+    @property
+    def sample_size(self):
+        """bytes per sample: 1 at 8 bits, 2 above"""
+        return self.y.element_size()
+
+    @property
+    def is_420_8bit(self):
+        """the kind tdc_yuv420_to_rgb takes (section 19); every other kind goes to tdc_yuv_to_rgb (section 20)"""
+        return self.bits == 8 and self.subsampling == "420"
 
     @property
     def is_cuda(self):
@@ -229,16 +282,26 @@ class YuvFrames:
     def __getitem__(self, s):
         if not isinstance(s, slice) or s.step not in (None, 1):
             raise TypeError("YuvFrames takes a slice of frames a:b, got %r" % (s,))
-        return YuvFrames(self.y[s], tuple(c[s] for c in self.chroma), self.c_step, self.shape[2], self.matrix, self.full_range)
+        return YuvFrames(self.y[s], tuple(c[s] for c in self.chroma), self.c_step, self.shape[2], self.matrix, self.full_range,
+                         self.bits, self.msb_aligned, self.subsampling)
 
     def planes(self):
         """the read set as views: (y [T0, H, W], one or two chroma planes [T0, Hc, c_step * Wc]) - the pitch padding cut off"""
         W = self.shape[2]
-        return (self.y[:, :, :W],) + tuple(c[:, :, :self.c_step * ((W + 1) // 2)] for c in self.chroma)
+        return (self.y[:, :, :W],) + tuple(c[:, :, :self.c_step * ((W + self.sub_x) >> self.sub_x)] for c in self.chroma)
 
     def kernel_views(self, planes):
-        """(y, u, v) as ops.yuv420_to_rgb takes them, from `planes` laid out like planes()"""
+        """(y, u, v) as ops.yuv420_to_rgb and ops.yuv_to_rgb take them, from `planes` laid out like planes()"""
         return (planes[0], planes[1], planes[1][:, :, 1:]) if self.c_step == 2 else tuple(planes)
+
+    def to_rgb(self, planes, out):
+        """ONE conversion launch: the frames of `planes` (device planes laid out like planes()) -> out uint8 [T, H, W, 3].
+        8-bit 4:2:0 issues tdc_yuv420_to_rgb as it always did; every other kind issues tdc_yuv_to_rgb."""
+        y, u, v = self.kernel_views(planes)
+        H, W = self.shape[1:3]
+        if self.is_420_8bit:
+            return ops.yuv420_to_rgb(y, u, v, self.c_step, self.coef, H, W, out=out)
+        return ops.yuv_to_rgb(y, u, v, self.c_step, self.coef, H, W, self.bits, self.msb_aligned, self.subsampling, out=out)
 
 
 def is_yuv_frames(x):
@@ -249,11 +312,12 @@ def is_yuv_frames(x):
 def gather_planes(yuv, idx, pin=True):
     """the frames idx (check_indices; not None) of host planes, gathered plane by plane with the pitch padding removed into
     ONE staging tensor (pinned when `pin`) -> (the staged planes as views of it laid out like yuv.planes(), the staging
-    tensor).  Frames outside idx and bytes outside planes() are never read.  The staging holds T * (H*W + 2*Hc*Wc) bytes."""
+    tensor).  Frames outside idx and bytes outside planes() are never read.  The staging holds T * (H*W + 2*Hc*Wc) samples
+    of the planes' type: that many bytes at 8 bits, twice as many at 10 and 12."""
     sel = torch.tensor(idx)
     src = yuv.planes()
     sizes = [len(idx) * p.shape[1] * p.shape[2] for p in src]
-    stage = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=pin)
+    stage = torch.empty(sum(sizes), dtype=src[0].dtype, pin_memory=pin)
     out, at = [], 0
     for p, n in zip(src, sizes):
         dst = stage[at:at + n].view(len(idx), p.shape[1], p.shape[2])
@@ -275,19 +339,19 @@ def selected_planes(yuv, idx, device):
             src = [torch.index_select(p, 0, sel) for p in src]
         return [p.to(device) for p in src], 0
     if idx is None and all(p.is_pinned() and p.is_contiguous() for p in src):
-        return [p.to(device, non_blocking=True) for p in src], sum(p.numel() for p in src)
+        return [p.to(device, non_blocking=True) for p in src], sum(p.numel() * p.element_size() for p in src)
     staged, stage = gather_planes(yuv, list(range(yuv.shape[0])) if idx is None else idx)
     dev = stage.to(device, non_blocking=True)
     out, at = [], 0
     for p in staged:
         out.append(dev[at:at + p.numel()].view(p.shape))
         at += p.numel()
-    return out, stage.numel()
+    return out, stage.numel() * stage.element_size()
 
 
 def _preprocess_selected_yuv(yuv, idx, towers, dtype, slab, device, out, stats):
-    """preprocess_selected for a YuvFrames: per slab of kept frames ONE tdc_yuv420_to_rgb launch into a [slab, H, W, 3] RGB
-    scratch, then tdc_preprocess_frames per tower on that scratch - the RGB path's launches on the frames the planes convert
+    """preprocess_selected for a YuvFrames: per slab of kept frames ONE conversion launch (YuvFrames.to_rgb: tdc_yuv420_to_rgb
+    for 8-bit 4:2:0, tdc_yuv_to_rgb for every other kind) into a [slab, H, W, 3] RGB scratch, then tdc_preprocess_frames per tower on that scratch - the RGB path's launches on the frames the planes convert
     to.  Both scratches are slab-sized and serve the whole video."""
     idx = check_indices(idx, yuv.shape[0])
     _check_dtype_slab(dtype, slab)
@@ -296,8 +360,7 @@ def _preprocess_selected_yuv(yuv, idx, towers, dtype, slab, device, out, stats):
     device = torch.device(device)
     T0, H, W, _ = yuv.shape
     planes, uploaded = selected_planes(yuv, idx, device)
-    y, u, v = yuv.kernel_views(planes)
-    T = y.shape[0]
+    T = planes[0].shape[0]
     if stats is not None:
         stats.update(frames_in=T0, frames_resized=T, bytes_uploaded=uploaded)
     out = _outputs(out, towers, T, dtype, device)
@@ -310,7 +373,7 @@ def _preprocess_selected_yuv(yuv, idx, towers, dtype, slab, device, out, stats):
     with torch.cuda.device(device):
         for s in range(0, T, slab):
             n = min(slab, T - s)
-            ops.yuv420_to_rgb(y[s:s + n], u[s:s + n], v[s:s + n], yuv.c_step, yuv.coef, H, W, out=rgb[:n])
+            yuv.to_rgb([p[s:s + n] for p in planes], rgb[:n])
             for t, o, (bounds, coeffs, lut) in zip(towers, out, tables):
                 pad = [int(x * 255) for x in t["mean"]]   # expand2square background (tdc/mm_datautils.py:302-304)
                 L.check(lib.tdc_preprocess_frames(ops._ptr(rgb), n, H, W, t["R"], ops._ptr(bounds), ops._ptr(coeffs),
@@ -345,7 +408,7 @@ def preprocess_selected(frames, idx, towers=(SIGLIP, DINOV2), dtype=torch.float1
     (a torch tensor - pageable, pinned or on the device - or a numpy array), idx the ascending host list of the frames to
     keep (encode.frame_indices; None: all) -> one [T, 3, R, R] tensor per tower on `device` (default: the frames' device, or
     the current one), bit for bit what process_images gives for the kept frames.
-    frames may also be a YuvFrames (4:2:0 planes): its kept frames are converted to RGB on the device,
+    frames may also be a YuvFrames (a decoder's planes, DESIGN.md sections 19 and 20): its kept frames are converted to RGB on the device,
     slab by slab, in front of the same resize - the result is what the RGB frames the planes convert to give.
     The kept frames are resized in slabs of at most `slab` frames: one tdc_preprocess_frames call per slab and tower writes its
     slice of the output, and ONE scratch of tdc_preprocess_scratch_bytes(slab, H, W, R) bytes serves every slab and tower, so the
