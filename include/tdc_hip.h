@@ -572,7 +572,7 @@ int tdc_yuv420_to_rgb(const tdc_yuv420_planes* p, const tdc_yuv_coef* c, int T, 
  *     G = clip8((cy*Y' - cgu*Cb - cgv*Cr + 2^(15+s)) >> (16+s))
  *     B = clip8((cy*Y' + cbu*Cb          + 2^(15+s)) >> (16+s))
  * The coefficients are the host's (preprocess.yuv_coefficients with its bits argument); y_off is 0 or 16 << s.  The transfer
- * function is not touched: PQ or HLG samples come out as PQ or HLG bytes.
+ * function is not touched: PQ or HLG samples come out as PQ or HLG bytes (tdc_yuv_hdr_to_rgb below tone-maps them).
  * A thread owns (1 + sub_y) rows, so a chroma sample is loaded once.  The host picks the 8-pixel vector form when W % 8 == 0
  * and the pointers, the pitches and (T > 1) the frame strides are multiples of the access widths - luma 8 bytes (bits = 8) or
  * 16 (words), rgb 8, chroma the 8 >> sub_x samples of one plane in one load, or that many pairs at the lower pointer when u
@@ -597,6 +597,45 @@ typedef struct {
 } tdc_yuv_planes;
 int tdc_yuv_to_rgb(const tdc_yuv_planes* p, const tdc_yuv_coef* c, int T, int H, int W,
                    unsigned char* rgb /* [T, H, W, 3] contiguous */, void* stream);
+
+/* ---- HDR YUV -> SDR RGB: PQ / HLG surfaces of 10 or 12 bits tone-mapped to sRGB bytes ------------
+ * The surfaces, the sample extraction, the sub-sampling, the replicated chroma, the thread ownership and the two kernel forms
+ * are those of the entry above; bits is 10 or 12.  The project's own stated formula, not claimed equal to any library's tone
+ * mapper.  s = bits - 8, N = 2^bits - 1.
+ * Stage A, int32, exact - YCbCr to non-linear R'G'B' codes at full depth, Y', Cb, Cr as above (clipN to [0, N], the clamp
+ * taken on the accumulator before the shift):
+ *     E_R = clipN((cy*Y' + crv*Cr          + 32768) >> 16)
+ *     E_G = clipN((cy*Y' - cgu*Cb - cgv*Cr + 32768) >> 16)
+ *     E_B = clipN((cy*Y' + cbu*Cb          + 32768) >> 16)
+ *   with the coefficients of preprocess.yuv_code_coefficients: floor(real * 65536 + 0.5) of the matrix factors times the luma
+ *   scale N / (219 << s) and the chroma scale N / (224 << s) (limited range; both 1 at full range).
+ * Stage B, float32 (defined in fp64 over the same float32 table):
+ *   1. l_c = lut[E_c].  PQ: lut[i] = 10000 * PQ_EOTF(i / N) / white (ST 2084; linear light in units of SDR white).
+ *      HLG: lut[i] = the BT.2100 inverse OETF of i / N (scene light in [0, 1]).
+ *   2. HLG only (ootf_exp != 0): Ys = luma . l;  g = ootf_scale * Ys^ootf_exp for Ys > 0 and g = 0 for Ys = 0;  l_c <- g * l_c
+ *      (the BT.2100 OOTF: ootf_scale = peak / white, ootf_exp = gamma - 1, gamma = 1.2 + 0.42 * log10(peak / 1000)).
+ *   3. m = max(l_R, l_G, l_B);  f = (1 + m * inv_p2) / (1 + m);  l_c <- f * l_c   (extended Reinhard on the largest channel,
+ *      inv_p2 = (white / peak)^2: slope 1 at black, monotone, m = peak / white goes to 1; the hue is kept).
+ *   4. x = gamut * l   (row-major 3 x 3: BT.2020 -> BT.709 primaries, or the identity).
+ *   5. x clipped to [0, 1];  v = 12.92 x for x <= 0.0031308, else 1.055 x^(1/2.4) - 0.055 (the sRGB OETF);  the byte is
+ *      floor(255 v + 0.5).
+ * Stage A is bit for bit the integer formula; every byte is within 1 of the definition (a float32 evaluation within 0.5 of
+ * the fp64 one on the 0 .. 255 scale moves the rounded byte by at most 1).  The powers are exp2(k * log2(x)) on the hardware
+ * instructions; both kernel forms run one device function per pixel and give the same bytes.
+ * TDC_E_BADARG before any launch: everything the entry above refuses; bits = 8; a null descriptor; lut null or not 4-byte
+ * aligned; a non-finite float in the descriptor; inv_p2 outside (0, 1]; ootf_exp outside [0, 1); ootf_scale <= 0 when
+ * ootf_exp != 0.
+ * writes: rgb [T, H, W, 3] and nothing else.  reads: what the entry above reads, plus exactly 2^bits floats at lut. */
+typedef struct {
+    const float* lut;       /* device: 2^bits entries, code -> light */
+    float ootf_scale;       /* HLG: peak / white */
+    float ootf_exp;         /* HLG: gamma - 1; 0: no OOTF (PQ) */
+    float luma[3];          /* the luminance weights of the OOTF */
+    float inv_p2;           /* (white / peak)^2 */
+    float gamut[9];         /* row-major 3 x 3, applied to linear light */
+} tdc_hdr_desc;             /* host struct, passed by value into the kernel */
+int tdc_yuv_hdr_to_rgb(const tdc_yuv_planes* p, const tdc_yuv_coef* c, const tdc_hdr_desc* h, int T, int H, int W,
+                       unsigned char* rgb /* [T, H, W, 3] contiguous */, void* stream);
 
 /* ---- BEATs audio front end --------------------------------------------------------------------------
  * kaldi fbank as BEATs.preprocess calls it (tdc/audio_models/beats/BEATs.py:115-129: torchaudio.compliance.kaldi.fbank,

@@ -158,6 +158,11 @@ class YuvCoef(C.Structure):
     _fields_ = [("y_off", C.c_int), ("cy", C.c_int), ("crv", C.c_int), ("cgu", C.c_int), ("cgv", C.c_int), ("cbu", C.c_int)]
 
 
+class HdrDesc(C.Structure):
+    _fields_ = [("lut", C.c_void_p), ("ootf_scale", C.c_float), ("ootf_exp", C.c_float), ("luma", C.c_float * 3),
+                ("inv_p2", C.c_float), ("gamut", C.c_float * 9)]
+
+
 class ProfRec(C.Structure):
     _fields_ = [("kind", C.c_int), ("tag", C.c_int), ("ms", C.c_float), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
                 ("act", C.c_int), ("res", C.c_int), ("out_f32", C.c_int), ("W", C.c_void_p), ("flops", C.c_double)]
@@ -220,6 +225,8 @@ SIGNATURES = {
     "tdc_yuv420_to_rgb": (C.c_int, [C.POINTER(Yuv420Planes), C.POINTER(YuvCoef), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p]),
     "tdc_yuv_to_rgb": (C.c_int, [C.POINTER(YuvPlanes), C.POINTER(YuvCoef), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "tdc_yuv_hdr_to_rgb": (C.c_int, [C.POINTER(YuvPlanes), C.POINTER(YuvCoef), C.POINTER(HdrDesc), C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_void_p]),
     "tdc_fbank_frames": (C.c_int, [C.c_longlong]),
     "tdc_fbank": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),

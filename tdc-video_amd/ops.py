@@ -739,6 +739,13 @@ def yuv_to_rgb(y, u, v, c_step, coef, H, W, bits=8, msb_aligned=False, subsampli
     [T, >= Hc, >= c_step * (Wc - 1) + 1] with Hc = (H + sub_y) >> sub_y, Wc = (W + sub_x) >> sub_x; c_step 1: two planes;
     c_step 2: interleaved samples, u and v views of one plane one sample apart.  coef = (y_off, cy, crv, cgu, cgv, cbu) of
     this bit depth, e.g. preprocess.yuv_coefficients(matrix, full_range, bits)."""
+    p, out = _yuv_planes(y, u, v, c_step, H, W, bits, msb_aligned, subsampling, out)
+    L.check(L.load().tdc_yuv_to_rgb(C.byref(p), C.byref(L.YuvCoef(*coef)), y.shape[0], H, W, _ptr(out), _stream()), "tdc_yuv_to_rgb")
+    return out
+
+
+def _yuv_planes(y, u, v, c_step, H, W, bits, msb_aligned, subsampling, out):
+    """the checked views of yuv_to_rgb / yuv_hdr_to_rgb -> (their tdc_yuv_planes, out allocated when None)"""
     assert subsampling in YUV_SUBSAMPLING, "subsampling must be one of %s" % sorted(YUV_SUBSAMPLING)
     sub_x, sub_y = YUV_SUBSAMPLING[subsampling]
     Hc, Wc = (H + sub_y) >> sub_y, (W + sub_x) >> sub_x
@@ -757,7 +764,23 @@ def yuv_to_rgb(y, u, v, c_step, coef, H, W, bits=8, msb_aligned=False, subsampli
     p = L.YuvPlanes(y.data_ptr(), u.data_ptr(), v.data_ptr(), b * y.stride(0) if T > 1 else 0, b * u.stride(0) if T > 1 else 0,
                     b * (y.stride(1) if y.shape[1] > 1 else W), b * (u.stride(1) if u.shape[1] > 1 else c_step * Wc), b * c_step,
                     bits, int(msb_aligned), sub_x, sub_y)
-    L.check(L.load().tdc_yuv_to_rgb(C.byref(p), C.byref(L.YuvCoef(*coef)), T, H, W, _ptr(out), _stream()), "tdc_yuv_to_rgb")
+    return p, out
+
+
+def yuv_hdr_to_rgb(y, u, v, c_step, coef, H, W, bits, msb_aligned, subsampling, hdr, out=None):
+    """T frames of 10- or 12-bit PQ / HLG YUV -> SDR rgb uint8 [T, H, W, 3] (tdc_yuv_hdr_to_rgb).  The
+    views are yuv_to_rgb's.  coef = (y_off, ky, krv, kgu, kgv, kbu) to codes at full depth, e.g.
+    preprocess.yuv_code_coefficients(matrix, full_range, bits).  hdr: the descriptor as a mapping - lut (float32 [2^bits] on
+    the planes' device, preprocess.hdr_table), ootf_scale, ootf_exp, luma (3), inv_p2, gamut (9, row-major)."""
+    lut = hdr["lut"]
+    assert lut.is_cuda and lut.dtype == torch.float32 and lut.dim() == 1 and lut.numel() == 1 << bits and lut.is_contiguous() \
+        and lut.device == y.device, "hdr['lut'] must be float32 [2^bits] on the planes' device"
+    assert len(hdr["luma"]) == 3 and len(hdr["gamut"]) == 9
+    p, out = _yuv_planes(y, u, v, c_step, H, W, bits, msb_aligned, subsampling, out)
+    h = L.HdrDesc(lut.data_ptr(), hdr["ootf_scale"], hdr["ootf_exp"], (C.c_float * 3)(*hdr["luma"]), hdr["inv_p2"],
+                  (C.c_float * 9)(*hdr["gamut"]))
+    L.check(L.load().tdc_yuv_hdr_to_rgb(C.byref(p), C.byref(L.YuvCoef(*coef)), C.byref(h), y.shape[0], H, W, _ptr(out), _stream()),
+            "tdc_yuv_hdr_to_rgb")
     return out
 
 

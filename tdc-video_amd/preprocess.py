@@ -152,19 +152,103 @@ def yuv_coefficients(matrix="bt601", full_range=False, bits=8):
     matrix's real coefficients, in double precision.  Limited range: luma 16 .. 235 and chroma 16 .. 240, times 2^(bits - 8) -
     the scales 255/219 and 255/224 and so the coefficients are those of 8 bits at every depth, y_off is 16 << (bits - 8).
     Full range: 0 .. 2^bits - 1 both, one scale 255 * 2^(bits - 8) / (2^bits - 1), which is 1 at 8 bits."""
+    _check_matrix_range_bits(matrix, full_range, bits)
+    s = bits - 8
+    kr, kb = YUV_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    full =255.0 * (1 << s) / ((1 << bits) - 1)
+    ys, cs = (full, full) if full_range else (255.0 / 219.0, 255.0 / 224.0)
+    real = (ys, 2 * (1 - kr) * cs, 2 * (1 - kb) * kb / kg * cs, 2 * (1 - kr) * kr / kg * cs, 2 * (1 - kb) * cs)
+    return (0 if full_range else 16 << s,) + tuple(int(math.floor(r * 65536 + 0.5)) for r in real)
+
+
+def _check_matrix_range_bits(matrix, full_range, bits):
     if matrix not in YUV_MATRICES:
         raise ValueError("matrix must be one of %s, got %r" % (sorted(YUV_MATRICES), matrix))
     if not isinstance(full_range, bool):
         raise ValueError("full_range must be True / False, got %r" % (full_range,))
     if isinstance(bits, bool) or bits not in YUV_BITS:
         raise ValueError("bits must be one of %s, got %r" % (YUV_BITS, bits))
-    s = bits - 8
+
+
+def yuv_code_coefficients(matrix="bt2020", full_range=False, bits=10):
+    """(y_off, ky, krv, kgu, kgv, kbu) of tdc_yuv_hdr_to_rgb's stage A: YCbCr to non-linear R'G'B' CODES
+    at the samples' depth, [0, N] with N = 2^bits - 1, instead of bytes.  floor(real * 65536 + 0.5) in double precision of the
+    matrix factors of yuv_coefficients times the luma scale N / (219 << s) and the chroma scale N / (224 << s) (limited range;
+    both 1 at full range), s = bits - 8."""
+    _check_matrix_range_bits(matrix, full_range, bits)
+    s, N = bits - 8, (1 << bits) - 1
     kr, kb = YUV_MATRICES[matrix]
     kg = 1.0 - kr - kb
-    full = 255.0 * (1 << s) / ((1 << bits) - 1)
-    ys, cs = (full, full) if full_range else (255.0 / 219.0, 255.0 / 224.0)
+    ys, cs = (1.0, 1.0) if full_range else (N / float(219 << s), N / float(224 << s))
     real = (ys, 2 * (1 - kr) * cs, 2 * (1 - kb) * kb / kg * cs, 2 * (1 - kr) * kr / kg * cs, 2 * (1 - kb) * cs)
     return (0 if full_range else 16 << s,) + tuple(int(math.floor(r * 65536 + 0.5)) for r in real)
+
+
+# ---- HDR transfer functions to SDR (DESIGN.md section 21) -----------------------------------------------------------------
+HDR_TRANSFERS = ("pq", "hlg")
+YUV_PRIMARIES = ("bt709", "bt2020")
+PQ_M1, PQ_M2 = 2610.0 / 16384.0, 2523.0 / 4096.0 * 128.0                              # SMPTE ST 2084
+PQ_C1, PQ_C2, PQ_C3 = 3424.0 / 4096.0, 2413.0 / 4096.0 * 32.0, 2392.0 / 4096.0 * 32.0
+HLG_A, HLG_B, HLG_C = 0.17883277, 0.28466892, 0.55991073                              # BT.2100
+BT2020_LUMA = (0.2627, 0.6780, 0.0593)
+# BT.2087 BT.2020 -> BT.709 primaries at four digits, each diagonal set so that its row sums to exactly 1 (grey stays grey)
+GAMUT_2020_TO_709 = (1.6604, -0.5876, -0.0728, -0.1246, 1.1329, -0.0083, -0.0182, -0.1006, 1.1188)
+GAMUT_IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)
+
+
+def _check_hdr(transfer, bits, peak_nits, sdr_white):
+    if transfer not in HDR_TRANSFERS:
+        raise ValueError("transfer must be 'sdr' or one of %s, got %r" % (HDR_TRANSFERS, transfer))
+    if isinstance(bits, bool) or bits not in (10, 12):
+        raise ValueError("transfer %r is taken at bits 10 and 12, got bits %r" % (transfer, bits))
+    _check_nits(peak_nits, sdr_white)
+    if transfer == "hlg" and not 0.0 < 0.2 + 0.42 * math.log10(peak_nits / 1000.0) < 1.0:
+        raise ValueError("peak_nits %r gives the HLG system gamma %.3f: hlg takes a peak whose gamma 1.2 + 0.42 log10(peak / 1000) "
+                         "is inside (1, 2), above 334.1 nits" % (peak_nits, 1.2 + 0.42 * math.log10(peak_nits / 1000.0)))
+
+
+def _check_nits(peak_nits, sdr_white):
+    for name, v in (("sdr_white", sdr_white), ("peak_nits", peak_nits)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError("%s must be a finite number of nits, got %r" % (name, v))
+    if not 0 < sdr_white:
+        raise ValueError("sdr_white must be above 0 nits, got %r" % (sdr_white,))
+    if not sdr_white <= peak_nits <= 10000:
+        raise ValueError("peak_nits must be in [sdr_white, 10000] = [%r, 10000] nits, got %r" % (sdr_white, peak_nits))
+
+
+def hdr_table(transfer, bits, peak_nits=1000.0, sdr_white=203.0):
+    """(table, scalars) of tdc_yuv_hdr_to_rgb's stage B.  table: numpy float32 [2^bits], code -> light, built in double
+    precision and rounded once - pq: 10000 * PQ_EOTF(i / N) / sdr_white, linear light in units of SDR white; hlg: the BT.2100
+    inverse OETF of i / N, scene light in [0, 1].  scalars: ootf_scale, ootf_exp (hlg: peak / white and gamma - 1 of the
+    BT.2100 OOTF with gamma = 1.2 + 0.42 log10(peak / 1000); pq: 1 and 0, no OOTF), luma, inv_p2 = (white / peak)^2."""
+    scalars = _hdr_scalars(transfer, bits, peak_nits, sdr_white)
+    e = np.arange(1 << bits, dtype=np.float64) / ((1 << bits) - 1)
+    if transfer == "pq":
+        ep = e ** (1.0 / PQ_M2)
+        table = 10000.0 * (np.maximum(ep - PQ_C1, 0.0) / (PQ_C2 - PQ_C3 * ep)) ** (1.0 / PQ_M1) / sdr_white
+    else:
+        table = np.where(e <= 0.5, e * e / 3.0, (np.exp((e - HLG_C) / HLG_A) + HLG_B) / 12.0)
+    return table.astype(np.float32), scalars
+
+
+def _hdr_scalars(transfer, bits, peak_nits, sdr_white):
+    _check_hdr(transfer, bits, peak_nits, sdr_white)
+    hlg = transfer == "hlg"
+    return dict(ootf_scale=peak_nits / sdr_white if hlg else 1.0, ootf_exp=0.2 + 0.42 * math.log10(peak_nits / 1000.0) if hlg else 0.0,
+                luma=BT2020_LUMA, inv_p2=(sdr_white / peak_nits) ** 2)
+
+
+_HDR_LUTS = {}      # (transfer, bits, peak_nits, sdr_white, device) -> the table on that device: made once, kept
+
+
+def hdr_lut(transfer, bits, peak_nits, sdr_white, device):
+    """hdr_table's table as a float32 tensor on `device`"""
+    key = (transfer, bits, float(peak_nits), float(sdr_white), str(torch.device(device)))
+    if key not in _HDR_LUTS:
+        _HDR_LUTS[key] = torch.from_numpy(hdr_table(transfer, bits, peak_nits, sdr_white)[0]).to(device)
+    return _HDR_LUTS[key]
 
 
 def _plane(p, name, bits=8):
@@ -196,16 +280,20 @@ class YuvFrames:
     uint8 torch tensors, all on the host or all on one device, or numpy arrays; row and frame strides may exceed the plane
     (a decoder surface with a pitch and an aligned height, taken as a view) and rows may be longer than `width` (default: the
     luma row length).  matrix "bt601" / "bt709" / "bt2020" and full_range choose the coefficients of the conversion
-    (yuv_coefficients), which is the stated formula of include/tdc_hip.h and no decoder library's; the transfer function is
-    not touched (PQ / HLG content stays PQ / HLG: no tone mapping).  .shape is (T0, H, W, 3), that of the RGB frames the
-    planes convert to; yuv[a:b] is a YuvFrames over the same memory.
+    (yuv_coefficients), which is the stated formula of include/tdc_hip.h and no decoder library's.  transfer "sdr" (the
+    default) leaves the transfer function alone; "pq" or "hlg" (HDR: 10 or 12 bits) converts to SDR sRGB bytes by the stated
+    tone mapping of DESIGN.md section 21 (tdc_yuv_hdr_to_rgb) - peak_nits is the mastering peak or MaxCLL (pq) or the nominal
+    display peak Lw (hlg, above 334.1 nits), sdr_white the luminance that maps to SDR's diffuse white (203 nits: BT.2408),
+    0 < sdr_white <= peak_nits <= 10000; primaries "bt2020" / "bt709" are the source's (None: bt2020 under the bt2020 matrix,
+    else bt709) and are converted to BT.709's.  .shape is (T0, H, W, 3), that of the RGB frames the planes convert to;
+    yuv[a:b] is a YuvFrames over the same memory.
     Beyond 8-bit 4:2:0: bits 10 or 12 - the planes are 16-bit words (numpy uint16, torch.uint16 where
     torch has it, or torch.int16 as a bit pattern; kept as torch.int16 views), the sample in their high bits (msb_aligned: P010,
     P012, P016) or their low bits (yuv420p10le and its kin); whatever the other bits hold is ignored.  subsampling "422":
     Hc = H, "444": Hc = H and Wc = W.  bt2020 is taken at 10 and 12 bits, the depths it is defined for."""
 
     def __init__(self, y, chroma, c_step, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False,
-                 subsampling="420"):
+                 subsampling="420", transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
         if c_step not in (1, 2):
             raise ValueError("c_step is 1 (planar u, v) or 2 (interleaved uv), got %r" % (c_step,))
         names = ("uv",) if c_step == 2 else ("u", "v")
@@ -225,7 +313,18 @@ class YuvFrames:
         self.c_step, self.matrix, self.full_range = c_step, matrix, full_range
         self.bits, self.msb_aligned, self.subsampling = bits, msb_aligned, subsampling
         self.sub_x, self.sub_y = ops.YUV_SUBSAMPLING[subsampling]
-        self.coef = yuv_coefficients(matrix, full_range, bits)
+        if primaries is None:
+            primaries = "bt2020" if matrix == "bt2020" else "bt709"
+        if primaries not in YUV_PRIMARIES:
+            raise ValueError("primaries must be None or one of %s, got %r" % (YUV_PRIMARIES, primaries))
+        self.transfer, self.peak_nits, self.sdr_white, self.primaries = transfer, peak_nits, sdr_white, primaries
+        if transfer == "sdr":
+            _check_nits(peak_nits, sdr_white)
+            self.coef, self.hdr = yuv_coefficients(matrix, full_range, bits), None
+        else:       # the descriptor of tdc_yuv_hdr_to_rgb but its table, which to_rgb takes from the planes' device
+            self.coef = yuv_code_coefficients(matrix, full_range, bits)
+            self.hdr = dict(_hdr_scalars(transfer, bits, peak_nits, sdr_white),
+                            gamut=GAMUT_2020_TO_709 if primaries == "bt2020" else GAMUT_IDENTITY)
         T0, H, pitch = self.y.shape
         W = pitch if width is None else int(width)
         if not 1 <= W <= pitch:
@@ -244,26 +343,30 @@ class YuvFrames:
         self.shape = (T0, H, W, 3)
 
     @classmethod
-    def nv12(cls, y, uv, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False, subsampling="420"):
+    def nv12(cls, y, uv, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False, subsampling="420",
+             transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
         """a luma plane and one plane of interleaved (u, v) samples: NV12, and NV16 / NV24 with subsampling "422" / "444" """
-        return cls(y, (uv,), 2, width, matrix, full_range, bits, msb_aligned, subsampling)
+        return cls(y, (uv,), 2, width, matrix, full_range, bits, msb_aligned, subsampling, transfer, peak_nits, sdr_white, primaries)
 
     @classmethod
-    def i420(cls, y, u, v, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False, subsampling="420"):
+    def i420(cls, y, u, v, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False, subsampling="420",
+             transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
         """three planes: yuv420p, yuv422p, yuv444p and - bits 10 / 12 - their 10le / 12le forms"""
-        return cls(y, (u, v), 1, width, matrix, full_range, bits, msb_aligned, subsampling)
+        return cls(y, (u, v), 1, width, matrix, full_range, bits, msb_aligned, subsampling, transfer, peak_nits, sdr_white, primaries)
 
     @classmethod
-    def p010(cls, y, uv, width=None, matrix="bt601", full_range=False):
+    def p010(cls, y, uv, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0,
+             primaries=None):
         """P010 as a hardware decoder writes it: 4:2:0, 16-bit words, the 10-bit sample in the high bits"""
-        return cls(y, (uv,), 2, width, matrix, full_range, 10, True, "420")
+        return cls(y, (uv,), 2, width, matrix, full_range, 10, True, "420", transfer, peak_nits, sdr_white, primaries)
 
     @classmethod
-    def p016(cls, y, uv, bits, width=None, matrix="bt601", full_range=False):
+    def p016(cls, y, uv, bits, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0,
+             primaries=None):
         """a P016 surface holding `bits` (10 or 12) significant bits, MSB-aligned; the low bits are ignored"""
         if isinstance(bits, bool) or bits not in (10, 12):
             raise ValueError("bits of a P016 surface must be 10 or 12, got %r" % (bits,))
-        return cls(y, (uv,), 2, width, matrix, full_range, bits, True, "420")
+        return cls(y, (uv,), 2, width, matrix, full_range, bits, True, "420", transfer, peak_nits, sdr_white, primaries)
 
     @property
     def sample_size(self):
@@ -283,7 +386,7 @@ class YuvFrames:
         if not isinstance(s, slice) or s.step not in (None, 1):
             raise TypeError("YuvFrames takes a slice of frames a:b, got %r" % (s,))
         return YuvFrames(self.y[s], tuple(c[s] for c in self.chroma), self.c_step, self.shape[2], self.matrix, self.full_range,
-                         self.bits, self.msb_aligned, self.subsampling)
+                         self.bits, self.msb_aligned, self.subsampling, self.transfer, self.peak_nits, self.sdr_white, self.primaries)
 
     def planes(self):
         """the read set as views: (y [T0, H, W], one or two chroma planes [T0, Hc, c_step * Wc]) - the pitch padding cut off"""
@@ -296,9 +399,13 @@ class YuvFrames:
 
     def to_rgb(self, planes, out):
         """ONE conversion launch: the frames of `planes` (device planes laid out like planes()) -> out uint8 [T, H, W, 3].
-        8-bit 4:2:0 issues tdc_yuv420_to_rgb as it always did; every other kind issues tdc_yuv_to_rgb."""
+        8-bit 4:2:0 issues tdc_yuv420_to_rgb as it always did; every other SDR kind issues tdc_yuv_to_rgb; transfer "pq" / "hlg"
+        issues tdc_yuv_hdr_to_rgb, its table taken from (and made once for) the planes' device."""
         y, u, v = self.kernel_views(planes)
         H, W = self.shape[1:3]
+        if self.hdr is not None:
+            hdr = dict(self.hdr, lut=hdr_lut(self.transfer, self.bits, self.peak_nits, self.sdr_white, y.device))
+            return ops.yuv_hdr_to_rgb(y, u, v, self.c_step, self.coef, H, W, self.bits, self.msb_aligned, self.subsampling, hdr, out=out)
         if self.is_420_8bit:
             return ops.yuv420_to_rgb(y, u, v, self.c_step, self.coef, H, W, out=out)
         return ops.yuv_to_rgb(y, u, v, self.c_step, self.coef, H, W, self.bits, self.msb_aligned, self.subsampling, out=out)
