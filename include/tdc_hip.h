@@ -657,6 +657,39 @@ int tdc_fbank(const void* wav, int wav_f32, long long n_samples, long long wav_b
 int tdc_relpos_gate(const void* q, int ldq, int rows, int heads, int head_dim, const float* w2, const float* b2,
                     const float* grep_a, float* gate, int ldg, int dtype, void* stream);
 
+/* ---- decoded PCM -> the mono 16 kHz waveform tdc_fbank takes -----------------------------------
+ * What a decoder hands over (interleaved s16, planar float32, any channel count, 8 .. 192 kHz) resampled to 16 kHz by the
+ * project's own stated formula, not claimed equal to librosa's, soxr's or any library's.  For an input rate sr (integer Hz):
+ * g = gcd(sr, 16000), L = 16000 / g, M = sr / g.  With rolloff = 0.9, Z = 32 zero crossings, Kaiser beta = 8.0:
+ *     c = rolloff * min(1, 16000 / sr)            cutoff, as a fraction of the input Nyquist
+ *     W = Z / c                                   half-width in input samples;  K = ceil(W)
+ *     h(tau) = c * sinc(c * tau) * I0(beta * sqrt(1 - (tau / W)^2)) / I0(beta)   for |tau| < W, else 0;  sinc(x) = sin(pi x) / (pi x)
+ *     table[p][j] = h(p / L - j),  j = -K+1 .. K (column j + K - 1),  p = 0 .. L-1
+ *     y[n] = sum_j table[(n M) mod L][j] * x[floor(n M / L) + j]
+ * Each row table[p] is divided by its own sum (DC gain exactly 1); the table is built in float64 and rounded once to float32
+ * (audio.resample_tables).  x is 0 outside [0, n_in); n M is computed in 64 bits.  Input sample: x = s / 32768 for int16
+ * (exact in fp32), a float32 as it is.  Channel: one index, or -1 = the fp32 mean of all channels (summed in ascending
+ * order, one division), taken before filtering.  L == M == 1 (sr = 16000) is a plain convert / select: no table is read.
+ * pcm: sample i of channel c is element i * sample_stride + c * channel_stride.  table: device, [L][2K] floats.  The call
+ * writes output samples out_lo .. out_lo + n_out - 1 of the track to out[0 .. n_out), fp32 or (out_f32 = 0) fp16 = round to
+ * nearest of the fp32 sum; outputs past ceil(n_in L / M) are those of the zero-padded track.  A lane runs the 2K taps of its
+ * row in ascending j as one fp32 FMA chain from 0, so every fp32 output is within (2K + 8) * 2^-24 * S * max|x| of the
+ * float64 definition, S = max_p sum_j |table[p][j]| (about 2.2), and the bits of output n depend only on n and the input -
+ * never on out_lo, n_out or the tile it lands in.  The host picks 16-byte loads for a dense channel (sample_stride = 1)
+ * whose 16-byte groups are aligned in every addressed channel, loads of one sample otherwise: same bits.
+ * TDC_E_BADARG before any launch: a null pointer; pcm not aligned to its sample, out to its element, table to 8 bytes; fmt
+ * outside {0, 1}; n_in < 1; channels outside [1, 65535]; channel < -1 or >= channels; sample_stride < 1; channel_stride < 0;
+ * K < 1; L outside [1, 640]; M outside [1, 2^20]; a negative out_lo / n_out, or out_lo + n_out (or n_in) above 2^40; a
+ * tile's span (255 M / L + 2K samples, plus the 2K taps at L == 1) beyond 64 KiB of LDS.
+ * writes: out[0 .. n_out) and nothing else.  reads: only samples [0, n_in) of the addressed channels (the one, or all for the
+ * mean), and L * 2K floats of the table (none at L == M == 1).  never read: the other channels, the padding between the
+ * samples of a strided view. */
+int tdc_pcm_resample(const void* pcm, int fmt /* 0 s16, 1 f32 */, long long n_in, int channels,
+                     long long sample_stride, long long channel_stride /* in elements */,
+                     int channel /* >= 0, or -1 = mean */, int L, int M,
+                     const float* table /* [L][2K] */, int K,
+                     long long out_lo, long long n_out, void* out, int out_f32, void* stream);
+
 /* ---- launch profiler -------------------------------------------------------------------------------------------------
  * Between tdc_profile_start and tdc_profile_stop every tdc_gemm / tdc_attention / tdc_layernorm / tdc_qformer_xattn launch -
  * called directly or from inside a composite (tdc_vit_fwd, tdc_connector_fwd, tdc_qformer_fwd) - is bracketed by two

@@ -27,8 +27,8 @@ import torch
 
 from . import segment as seg
 from .cache import fingerprint_rows_host
-from .encode import (cached_audio, emission_plan, encode_missing, frame_indices, join_side_tower, precise_features,
-                     sample_indicator, select_segments_with, start_side_tower, text_prompt, visual_budget)
+from .encode import (cached_audio, emission_plan, encode_missing, frame_indices, join_side_tower, normalize_audio,
+                     precise_features, sample_indicator, select_segments_with, start_side_tower, text_prompt, visual_budget)
 
 
 def owner_of(frame, ranges):
@@ -235,7 +235,9 @@ class ShardedVideoEncoder:
         with "audio_tokens" / "beats_windows" (all windows) / "audio_wav" (raw 16 kHz waveform: BEATs runs here, on this
         rank's windows only); sample_indices: frame_plan's per-second vector (all ones when a1 did not cap).
         cache: a FrameCache (new_cache) of this rank's own frames - the result is bit for bit that of cache=None
-        (_encode_cached); info then receives info["cache"].  cache=None: no collective besides those listed above."""
+        (_encode_cached); info then receives info["cache"].  cache=None: no collective besides those listed above.
+        {"audio_pcm": audio.PcmAudio} becomes the waveform here, on every rank (encode.normalize_audio)."""
+        audio = normalize_audio(self.e, audio)
         if cache is not None:
             return self._encode_cached(cache, px_siglip_local, px_dino_local_halo, T, image_size, n_text_tokens, prompt_ids,
                                        audio, sample_indices, recompute_halo, info)

@@ -13,6 +13,8 @@ The engine is pipeline.VideoEncoder on GPUs; the CPU tests plug in doubles.  The
   refinement selection_eps, selection_max_fraction, precise_dino(px), pair_sims(feats, pairs)
   frame cache fingerprint(px, rows), slot_sims(slab, pairs, defer), compact_rows(src, idx, cols), beats / beats_windows /
              audio_tokens (raw-waveform audio)
+  PCM audio   probed: resample_pcm(pcm) -> the track's fp32 16 kHz waveform [1, n] on the engine's device (normalize_audio;
+             audio.resample on an engine without the method)
   probed     mark / fetch / after (the host read beside the compute stream), two_streams / tower_stream (SigLIP on a side
              stream), emit_into, multi_prompt_ok, dev, side - absent on the doubles
   features   towers (what features.tower_signature fingerprints); probed: tower_width(name), feature_rows(x) (the tower
@@ -27,6 +29,31 @@ The engine is pipeline.VideoEncoder on GPUs; the CPU tests plug in doubles.  The
 import torch
 
 from . import segment as seg
+
+
+def normalize_audio(e, audio):
+    """the ONE place decoded PCM becomes a waveform: a dict with "audio_pcm" (audio.PcmAudio) comes back
+    as the same dict with "audio_wav" in its place - the whole track resampled to 16 kHz, fp32, on the engine's device
+    (engine.resample_pcm where the engine has it, audio.resample otherwise) - and everything below sees a waveform.  Called
+    where an audio dict first enters the orchestration (encode_source, encode_source_prompts, encode_batch_with,
+    same_source_key, audio_key, the sharded encode); any other audio comes back as the object it is, so such a call issues
+    the launches it always did.  "audio_pcm" beside "audio_wav", "beats_windows", "audio_tokens" or "audio_wav_mask" raises
+    ValueError (a PcmAudio has no padding, so no mask goes with it)."""
+    if not isinstance(audio, dict) or audio.get("audio_pcm") is None:
+        return audio
+    clash = [k for k in ("audio_wav", "beats_windows", "audio_tokens", "audio_wav_mask") if audio.get(k) is not None]
+    if clash:
+        raise ValueError("audio_pcm cannot be given together with %s" % ", ".join(clash))
+    from .audio import is_pcm_audio, resample
+    pcm = audio["audio_pcm"]
+    if not is_pcm_audio(pcm):
+        raise ValueError("audio_pcm must be an audio.PcmAudio, got %s" % type(pcm).__name__)
+    rs = getattr(e, "resample_pcm", None)
+    wav = rs(pcm) if rs is not None else resample(pcm, device=getattr(e, "dev", None))
+    out = {k: v for k, v in audio.items() if k != "audio_pcm" and v is not None}
+    out["audio_wav"] = wav
+    return out
+
 
 def visual_budget(cfg, n_text_tokens):
     """max_visual_len of a sample with n_text_tokens non-image tokens (tdc/cambrian_arch.py:1499-1505)"""
@@ -253,6 +280,7 @@ def encode_source_prompts(e, src, prompts, audio=None, frame_cap=224, video_inde
                           pad_fraction=0.25):
     """encode_video_prompts_with over any source (PixelSource, FrameSource, FeatureSource): a1 per prompt, here and nowhere
     below; the front of each distinct selection runs once (prompts_over_fronts)"""
+    audio = normalize_audio(e, audio)
     sels = [frame_indices(e.cfg, src.T0, pr["budget_text_len"], frame_cap) for pr in prompts]       # a1
     return prompts_over_fronts(e, sels, prompts, lambda idx, finfo: src.front(e, idx, audio, video_index, finfo), infos,
                                max_prompts, pad_fraction)
@@ -310,14 +338,14 @@ def audio_key(e, audio, T0, idx, video_index=None):
     the same-video keys and of the name of a kept K/V entry"""
     if audio is None:
         return None
-    return (content_key(e, audio), tuple(sample_indicator(T0, idx, video_index)))
+    return (content_key(e, normalize_audio(e, audio)), tuple(sample_indicator(T0, idx, video_index)))
 
 
 def same_source_key(e, src, budget_text_len, frame_cap, audio=None, video_index=None):
     """`config.tdc_batch_prompts`: what two samples of one call must share to be questions about the SAME video: the content
     of what a1 keeps of their source (PixelSource.same_key, FeatureSource.same_key) and their audio (audio_key)"""
     idx = frame_indices(e.cfg, src.T0, budget_text_len, frame_cap)                                  # a1
-    return src.same_key(e, idx, audio, video_index)
+    return src.same_key(e, idx, normalize_audio(e, audio), video_index)
 
 
 def same_video_key(e, px_siglip, px_dino, image_size, budget_text_len, frame_cap, audio=None, video_index=None):
@@ -528,6 +556,7 @@ def encode_source(e, src, budget_text_len, n_text_tokens, prompt_ids, audio=None
     aux = aux_kw(aux, getattr(src, "cache", None))
     if image:
         return src.image(e, info, **aux)[:, :e.H]
+    audio = normalize_audio(e, audio)
     idx = frame_indices(e.cfg, src.T0, budget_text_len, frame_cap)                                  # a1
     f = src.front(e, idx, audio, video_index, info, keep, **aux)
     return encode_front(e, f, n_text_tokens, prompt_ids, keep, splice, info)
@@ -638,7 +667,7 @@ def encode_batch_with(e, samples, frame_cap, infos=None):
             if info is not None:
                 info["final_size"] = fs
             continue
-        audio = s.get("audio")
+        audio = normalize_audio(e, s.get("audio"))
         if audio is not None:                                                                       # a20
             audio = e.local_audio(audio, sample_indicator(s["px_siglip"].shape[0], idx, s.get("video_index")), T, 0, T)
         out.append(compress_with(e, Xs, T, n // T, seg_idx[j], text_prompt(cfg, s["prompt_ids"]),   # a11-a19 (+a21)

@@ -232,6 +232,8 @@ SIGNATURES = {
                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
     "tdc_relpos_gate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "tdc_pcm_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_int,
+                                   C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p]),
     "tdc_profile_start": (C.c_int, [C.c_int]),
     "tdc_profile_stop": (C.c_int, [C.POINTER(ProfRec), C.c_int]),
     "tdc_profile_tag": (C.c_int, [C.c_int]),

@@ -23,7 +23,8 @@ import torch.nn as nn
 
 from . import lib as L
 from . import segment as seg
-from .encode import FeatureSource, FrameSource, PixelSource, batch_groups, encode_source, frame_indices, same_source_key
+from .encode import (FeatureSource, FrameSource, PixelSource, batch_groups, encode_source, frame_indices, normalize_audio,
+                     same_source_key)
 from .features import FeatureSet, is_feature_set
 from .pipeline import VideoEncoder
 
@@ -823,6 +824,11 @@ class CambrianMetaForCausalLM(ABC):
                 audio = audios[i]
                 if not isinstance(audio, dict):
                     audio = {"audio_tokens": audio.to(eng.dev)}
+                elif audio.get("audio_pcm") is not None:
+                    # a decoder's PCM track (audio.PcmAudio): resampled to the 16 kHz waveform once, here, so the same-video
+                    # grouping and every entry below see {"audio_wav": ...} (a clash with another key raises ValueError)
+                    audio = normalize_audio(eng, audio)
+                    eng.beats = model.tdc_beats()
                 elif audio.get("audio_wav") is not None and audio.get("beats_windows") is None \
                         and audio.get("audio_tokens") is None:
                     # the reference's own audio dict (cambrian_arch.py:1547): raw waveform -> BEATs on the device

@@ -708,6 +708,24 @@ def fbank(wav, tables, dtype, want_plain=False, mean=15.41663, std=6.55582):
     return patches, plain, m
 
 
+def pcm_resample(x, channel, Lp, M, table, K, out_lo, n_out, out=None, dtype=torch.float32):
+    """outputs out_lo .. out_lo + n_out - 1 of a PCM track at 16 kHz (tdc_pcm_resample).  x: the track
+    on the GPU as a view [n, C], int16 or float32, whose strides carry the layout (interleaved, planar, padded); channel: an
+    index, or -1 for the fp32 mean; Lp, M, table [Lp, 2K], K: audio.resample_tables of the track's rate.  -> out [n_out]
+    float32 or float16."""
+    assert x.is_cuda and x.dim() == 2 and x.dtype in (torch.int16, torch.float32), "x must be an int16 / float32 [n, C] CUDA view"
+    assert table.is_cuda and table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (Lp, 2 * K)
+    if out is None:
+        out = torch.empty(n_out, device=x.device, dtype=dtype)
+    assert out.is_cuda and out.dtype in (torch.float32, torch.float16) and out.dim() == 1 and out.numel() == n_out
+    assert n_out <= 1 or out.stride(0) == 1, "out must be dense"
+    with torch.cuda.device(x.device):
+        L.check(L.load().tdc_pcm_resample(_ptr(x), 1 if x.dtype == torch.float32 else 0, x.shape[0], x.shape[1],
+                                          x.stride(0) if x.shape[0] > 1 else 1, x.stride(1) if x.shape[1] > 1 else 0, channel, Lp, M, _ptr(table), K, out_lo, n_out, _ptr(out),
+                                          1 if out.dtype == torch.float32 else 0, _stream()), "tdc_pcm_resample")
+    return out
+
+
 def yuv420_to_rgb(y, u, v, c_step, coef, H, W, out=None):
     """T frames of 8-bit 4:2:0 -> rgb uint8 [T, H, W, 3] (tdc_yuv420_to_rgb).  y [T, >= H, >= W] and u, v
     [T, >= Hc, >= c_step * (Wc - 1) + 1] are uint8 views on the GPU with a dense last dimension whose strides carry the

@@ -910,6 +910,12 @@ class VideoEncoder:
             raise RuntimeError("raw audio given but no BEATs encoder is attached (VideoEncoder.beats)")
         return self.beats.window_features(wav, only=only, mask=mask)
 
+    def resample_pcm(self, pcm):
+        """a decoded track (audio.PcmAudio) -> its mono 16 kHz waveform [1, n] fp32 on this device (tdc_pcm_resample; DESIGN.md
+        section 22): what encode.normalize_audio puts in the place of audio={"audio_pcm": pcm}"""
+        from . import audio as pcm_audio
+        return pcm_audio.resample(pcm, device=self.dev)
+
     def local_audio(self, audio, sample_indices, T, lo=0, hi=None):
         """a20 for the frames [lo, hi) of the T kept frames: the caller's `audio` (None, a [T, 50, 768] token tensor, or
         the dict forms of prepare_inputs_labels_for_multimodal) -> [hi - lo, 50, 768] audio tokens (None without audio).
