@@ -637,6 +637,29 @@ typedef struct {
 int tdc_yuv_hdr_to_rgb(const tdc_yuv_planes* p, const tdc_yuv_coef* c, const tdc_hdr_desc* h, int T, int H, int W,
                        unsigned char* rgb /* [T, H, W, 3] contiguous */, void* stream);
 
+/* ---- display orientation of decoded RGB frames -------------------------------------------------
+ * A decoder writes the coded picture; the orientation travels beside it (the display matrix or `rotate` tag of MP4 / MOV,
+ * the EXIF orientation of a still).  src uint8 [T, H, W, 3] contiguous, the stored frames S -> dst uint8 [T, H', W', 3]
+ * contiguous, the upright frames O, what tdc_preprocess_frames takes.  quarters = the clockwise quarter turns that make
+ * the stored frame upright (rotate / 90), then hflip mirrors left-right:
+ *     quarters 0: O[y, x] = S[y, x]               (H', W') = (H, W)
+ *     quarters 1: O[y, x] = S[H-1-x, y]           (H', W') = (W, H)
+ *     quarters 2: O[y, x] = S[H-1-y, W-1-x]       (H', W') = (H, W)
+ *     quarters 3: O[y, x] = S[x, W-1-y]           (H', W') = (W, H)
+ *     hflip:      O'[y, x] = O[y, W'-1-x]
+ * the eight elements of the dihedral group; a vertical flip is (2, 1); (0, 0) is a plain copy.  A permutation of bytes:
+ * exact, the three bytes of a pixel stay in order.  quarters 1 and 3 move tiles of 64 x 64 pixels through LDS, read along
+ * source rows and written along destination rows; quarters 0 and 2 move rows, the pixel order reversed where needed.  The
+ * host picks 4-byte accesses where the pointer and the row length in bytes are multiples of 4 (the transposing cases:
+ * src and 3 W for the loads, dst and 3 H for the stores, each on its own; the others: src, dst and 3 W together), byte
+ * accesses otherwise: same bytes.  Every byte offset is 64-bit.
+ * TDC_E_BADARG before any launch: a null pointer; T, H or W outside [1, 65535]; quarters outside 0 .. 3; hflip outside
+ * {0, 1}; src [0, 3 T H W) and dst [0, 3 T H W) overlapping.
+ * writes: dst [0, 3 T H W) and nothing else.  reads: src [0, 3 T H W) and nothing else. */
+int tdc_orient_frames(const unsigned char* src /* [T, H, W, 3] contiguous */, int T, int H, int W,
+                      int quarters /* 0..3 clockwise */, int hflip /* 0 / 1 */,
+                      unsigned char* dst /* [T, H', W', 3] contiguous */, void* stream);
+
 /* ---- BEATs audio front end --------------------------------------------------------------------------
  * kaldi fbank as BEATs.preprocess calls it (tdc/audio_models/beats/BEATs.py:115-129: torchaudio.compliance.kaldi.fbank,
  * 128 mel bins, 16 kHz, 25 ms / 10 ms, povey window, pre-emphasis 0.97, DC removal, dither 0, snip_edges) on B

@@ -227,6 +227,7 @@ SIGNATURES = {
     "tdc_yuv_to_rgb": (C.c_int, [C.POINTER(YuvPlanes), C.POINTER(YuvCoef), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdc_yuv_hdr_to_rgb": (C.c_int, [C.POINTER(YuvPlanes), C.POINTER(YuvCoef), C.POINTER(HdrDesc), C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p]),
+    "tdc_orient_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdc_fbank_frames": (C.c_int, [C.c_longlong]),
     "tdc_fbank": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),

@@ -556,7 +556,9 @@ class CambrianMetaModel:
         """`config.tdc_frame_inputs`: True = `images` carries decoded uint8 frames instead of pixels.  Videos: images[0][i] is the
         uint8 [T, H, W, 3] tensor (or numpy array) of sample i, on the host or the device, and images[1] is ignored (None);
         single images: images[0] is uint8 [bsz, H, W, 3].  An entry images[0][i] (videos), or images[0] itself (single images),
-        may be a preprocess.YuvFrames - NV12 / I420 planes as the decoder wrote them.  Every sample runs through VideoEncoder.encode_frames: a1 first, then
+        may be a preprocess.YuvFrames - NV12 / I420 planes as the decoder wrote them - or a
+        preprocess.Oriented over either kind: stored frames plus their display rotation / mirror (image_sizes
+        is then the upright frames').  Every sample runs through VideoEncoder.encode_frames: a1 first, then
         only the kept frames are uploaded and resized - the 10-tuple is bit for bit the pixel call's on
         preprocess.process_images of the same frames.  Absent / False: pixels.  Composes with `config.tdc_video_cache_bytes`;
         set together with `config.tdc_feature_inputs`, `tdc_shard_frames`, `tdc_batch_frames`, `tdc_shard_cache_bytes` or

@@ -802,6 +802,22 @@ def yuv_hdr_to_rgb(y, u, v, c_step, coef, H, W, bits, msb_aligned, subsampling, 
     return out
 
 
+def orient_frames(frames, quarters, hflip, out=None):
+    """stored frames uint8 [T, H, W, 3] (contiguous, on the GPU) -> the upright frames uint8 [T, H', W', 3]: `quarters`
+    clockwise quarter turns, then a left-right mirror when `hflip` (tdc_orient_frames).  (H', W') is
+    (W, H) for quarters 1 and 3, else (H, W).  out: a contiguous uint8 tensor of that shape that shares no byte with frames."""
+    assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), \
+        "frames must be a contiguous uint8 [T, H, W, 3] CUDA tensor"
+    T, H, W, _ = frames.shape
+    shape = (T, W, H, 3) if quarters in (1, 3) else (T, H, W, 3)
+    if out is None:
+        out = torch.empty(shape, device=frames.device, dtype=torch.uint8)
+    assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous() and out.device == frames.device
+    with torch.cuda.device(frames.device):
+        L.check(L.load().tdc_orient_frames(_ptr(frames), T, H, W, int(quarters), int(hflip), _ptr(out), _stream()), "tdc_orient_frames")
+    return out
+
+
 def relpos_gate(q, rows, heads, head_dim, w2, b2, grep_a, out=None):
     """q: [rows, ld] 16-bit view (un-scaled q_proj output) -> gate fp32 [rows, heads]."""
     assert q.is_cuda and q.dim() == 2 and q.stride(1) == 1 and q.shape[0] >= rows and q.shape[1] >= heads * head_dim

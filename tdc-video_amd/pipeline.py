@@ -1265,7 +1265,9 @@ class VideoEncoder:
         `dtype`, bit for bit preprocess.process_images(frames[idx], dtype, frame_towers): the reference's process_images on the
         device.  Only the kept frames are uploaded and resized (preprocess.preprocess_selected).  frames may also be a
         preprocess.YuvFrames (NV12 / I420 planes): the kept frames' planes are uploaded and converted to
-        RGB on the device in front of the same resize, and `frames[idx]` above reads as the RGB frames they convert to."""
+        RGB on the device in front of the same resize, and `frames[idx]` above reads as the RGB frames they convert to.  Either
+        kind may be wrapped in a preprocess.Oriented (a display rotation / mirror): the kept frames are
+        turned upright on the device and `frames[idx]` reads as the upright frames."""
         if len(self.frame_towers) != 2:
             raise ValueError("frame_towers is a pair of {R, mean, std} dicts (SigLIP, DINOv2), got %d" % len(self.frame_towers))
         px_siglip, px_dino = preprocess.preprocess_selected(frames, idx, self.frame_towers, self.dtype, self.frame_slab,

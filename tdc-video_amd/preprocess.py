@@ -489,6 +489,111 @@ def _preprocess_selected_yuv(yuv, idx, towers, dtype, slab, device, out, stats):
     return [o[:T] for o in out]
 
 
+# ---- display orientation ---------------------------------------------------------------------------
+ROTATIONS = (0, 90, 180, 270)
+# EXIF orientation -> (rotate, hflip): the clockwise turn that makes the stored picture upright, then a left-right mirror
+EXIF_ORIENTATIONS = {1: (0, False), 2: (0, True), 3: (180, False), 4: (180, True),
+                     5: (90, True), 6: (90, False), 7: (270, True), 8: (270, False)}
+
+
+class Oriented:
+    """T0 stored frames and the display orientation that travels beside them, described and not copied: `frames` is what the
+    frames entries take - uint8 [T0, H, W, 3] (torch tensor or numpy array, host or device) or a YuvFrames of any kind -
+    as the decoder wrote it, `rotate` in {0, 90, 180, 270} the clockwise turn that makes a stored frame upright (the `rotate`
+    tag of MP4 / MOV), `hflip` a left-right mirror applied after the turn.  With S a stored frame [H, W, 3], the upright
+    frame O is
+        rotate   0: O[y, x] = S[y, x]                 rotate 180: O[y, x] = S[H-1-y, W-1-x]          both [H, W, 3]
+        rotate  90: O[y, x] = S[H-1-x, y]             rotate 270: O[y, x] = S[x, W-1-y]              both [W, H, 3]
+        hflip:      O'[y, x] = O[y, W'-1-x]
+    (np.rot90(S, -1) is rotate 90; a vertical flip is rotate 180 with hflip).  .shape is (T0, H', W', 3), that of the upright
+    frames; o[a:b] is an Oriented over the same memory.  The kept frames are turned on the device, in front of the resize
+    (tdc_orient_frames); everything behind sees the upright frames."""
+
+    def __init__(self, frames, rotate=0, hflip=False):
+        if isinstance(rotate, bool) or rotate not in ROTATIONS:
+            raise ValueError("rotate must be one of %s (clockwise degrees), got %r" % (ROTATIONS, rotate))
+        if not isinstance(hflip, bool):
+            raise ValueError("hflip must be True / False, got %r" % (hflip,))
+        if is_oriented(frames):
+            raise ValueError("frames is an Oriented already: compose the two orientations into one")
+        self.frames = frames if is_yuv_frames(frames) else check_frames(frames)
+        self.rotate, self.hflip, self.quarters = int(rotate), hflip, int(rotate) // 90
+        T0, H, W, _ = self.frames.shape
+        self.shape = (int(T0), int(W), int(H), 3) if self.quarters & 1 else (int(T0), int(H), int(W), 3)
+
+    @classmethod
+    def exif(cls, frames, orientation):
+        """from an EXIF orientation 1 .. 8 (EXIF_ORIENTATIONS)"""
+        if isinstance(orientation, bool) or orientation not in EXIF_ORIENTATIONS:
+            raise ValueError("an EXIF orientation is 1 .. 8, got %r" % (orientation,))
+        return cls(frames, *EXIF_ORIENTATIONS[orientation])
+
+    @property
+    def is_identity(self):
+        return self.quarters == 0 and not self.hflip
+
+    @property
+    def is_cuda(self):
+        return self.frames.is_cuda
+
+    def __getitem__(self, s):
+        if not isinstance(s, slice) or s.step not in (None, 1):
+            raise TypeError("Oriented takes a slice of frames a:b, got %r" % (s,))
+        return Oriented(self.frames[s], self.rotate, self.hflip)
+
+
+def is_oriented(x):
+    """an Oriented, recognised by its members (the package can be imported under two names: not by isinstance)"""
+    return all(hasattr(x, k) for k in ("frames", "rotate", "hflip", "quarters", "shape")) and not torch.is_tensor(x)
+
+
+def _preprocess_selected_oriented(o, idx, towers, dtype, slab, device, out, stats):
+    """preprocess_selected for an Oriented.  The identity issues exactly the launches of the wrapped frames.  Otherwise a1's
+    frames, or planes, are uploaded as the wrapped frames' are, and per slab of kept frames: YUV planes are converted by their
+    one launch into a [slab, H, W, 3] scratch, ONE tdc_orient_frames launch writes the upright frames into a [slab, H', W', 3]
+    scratch, and tdc_preprocess_frames runs per tower on that scratch - the RGB path's launches on the upright frames.  A slab
+    is turned once and both towers read it.  The scratches are slab-sized and serve the whole video."""
+    inner = o.frames
+    if o.is_identity:
+        return preprocess_selected(inner, idx, towers, dtype, slab, device, out, stats)
+    yuv = is_yuv_frames(inner)
+    idx = check_indices(idx, o.shape[0])
+    _check_dtype_slab(dtype, slab)
+    if device is None:
+        device = (inner.y.device if yuv else inner.device) if inner.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    T0, H, W, _ = inner.shape
+    Ho, Wo = o.shape[1:3]
+    if yuv:
+        planes, uploaded = selected_planes(inner, idx, device)
+        T = planes[0].shape[0]
+    else:
+        kept, uploaded = selected_frames(inner, idx, device)
+        T = kept.shape[0]
+    if stats is not None:
+        stats.update(frames_in=T0, frames_resized=T, bytes_uploaded=uploaded)
+    out = _outputs(out, towers, T, dtype, device)
+    lib = L.load()
+    n0 = min(slab, T)
+    nscr = max(lib.tdc_preprocess_scratch_bytes(n0, Ho, Wo, t["R"]) for t in towers)
+    scratch = torch.empty(max(nscr, 1), dtype=torch.uint8, device=device)
+    rgb = torch.empty((n0, H, W, 3), dtype=torch.uint8, device=device) if yuv else None
+    upright = torch.empty((n0, Ho, Wo, 3), dtype=torch.uint8, device=device)
+    tables = [_tables(max(Ho, Wo), t["R"], t["mean"], t["std"], device) for t in towers]
+    with torch.cuda.device(device):
+        for s in range(0, T, slab):
+            n = min(slab, T - s)
+            if yuv:
+                inner.to_rgb([p[s:s + n] for p in planes], rgb[:n])
+            ops.orient_frames(rgb[:n] if yuv else kept[s:s + n], o.quarters, o.hflip, out=upright[:n])
+            for t, dst, (bounds, coeffs, lut) in zip(towers, out, tables):
+                pad = [int(x * 255) for x in t["mean"]]   # expand2square background (tdc/mm_datautils.py:302-304)
+                L.check(lib.tdc_preprocess_frames(ops._ptr(upright), n, Ho, Wo, t["R"], ops._ptr(bounds), ops._ptr(coeffs),
+                                                  coeffs.shape[1], pad[0], pad[1], pad[2], ops._ptr(lut), ops._ptr(dst[s:s + n]), 0,
+                                                  ops._dtcode(dtype), ops._ptr(scratch), ops._stream()), "tdc_preprocess_frames")
+    return [dst[:T] for dst in out]
+
+
 def _check_dtype_slab(dtype, slab):
     if dtype not in (torch.float16, torch.bfloat16):
         raise ValueError("preprocess_selected writes float16 or bfloat16 pixels, got %s" % (dtype,))
@@ -521,7 +626,11 @@ def preprocess_selected(frames, idx, towers=(SIGLIP, DINOV2), dtype=torch.float1
     slice of the output, and ONE scratch of tdc_preprocess_scratch_bytes(slab, H, W, R) bytes serves every slab and tower, so the
     scratch does not grow with the video.  Frames are resized independently: the result does not depend on `slab`.
     out: one preallocated contiguous [>= T, 3, R, R] tensor of `dtype` per tower - rows [0, T) are written, nothing else, and
-    the views out[j][:T] are returned.  stats: a dict that receives frames_in, frames_resized and bytes_uploaded."""
+    the views out[j][:T] are returned.  stats: a dict that receives frames_in, frames_resized and bytes_uploaded.
+    frames may be an Oriented over either kind: the kept frames are turned upright on the device, one
+    launch per slab, in front of the same resize - the result is what the upright frames give."""
+    if is_oriented(frames):
+        return _preprocess_selected_oriented(frames, idx, towers, dtype, slab, device, out, stats)
     if is_yuv_frames(frames):
         return _preprocess_selected_yuv(frames, idx, towers, dtype, slab, device, out, stats)
     frames = check_frames(frames)
