@@ -660,6 +660,34 @@ int tdc_orient_frames(const unsigned char* src /* [T, H, W, 3] contiguous */, in
                       int quarters /* 0..3 clockwise */, int hflip /* 0 / 1 */,
                       unsigned char* dst /* [T, H', W', 3] contiguous */, void* stream);
 
+/* ---- channel-first, BGR, RGBA and gray frames to packed RGB ------------------------------------
+ * Decoded pictures in the layouts decoders, capture and image readers write, described by a base pointer, three byte
+ * strides (frame, row, pixel) and the byte offsets chan[0..2] of the R, G and B sample inside a pixel, all non-negative:
+ *     O[t, y, x, c] = src[t*frame_stride + y*row_stride + x*pixel_stride + chan[c]]     c = 0, 1, 2 (R, G, B)
+ * O uint8 [T, H, W, 3] contiguous, what tdc_preprocess_frames takes.  Channel-first [T, C, H, W]: pixel_stride 1, chan =
+ * the plane stride times the plane's number; BGRA: 4, (2, 1, 0); ARGB: 4, (1, 2, 3); BGR: 3, (2, 1, 0); gray: 1, (0, 0, 0);
+ * gray + alpha interleaved: 2, (0, 0, 0).  A row pitch, an aligned surface height and a crop are strides and a base.  An
+ * ignored channel (alpha, X) is no part of the result; alpha is dropped, not composited; gray is replicated.  Exact: every
+ * output byte is a copy of one input byte.  Forms, chosen on the host from the descriptor alone and moving the same bytes:
+ * four pixels per thread with 4-byte loads (pixel_stride 1: one per distinct channel offset; 3 and 4 with every chan <
+ * pixel_stride: the four pixels' 12 or 16 bytes, 16 as one load where aligned) and three 4-byte stores when W, dst, the
+ * source pointer (pixel_stride 1: plus each chan), row_stride and frame_stride are multiples of 4; one pixel per thread
+ * with byte accesses otherwise.  Every byte offset is 64-bit.
+ * TDC_E_BADARG before any launch: a null s, s->src or dst; T, H or W outside [1, 65535]; a stride or an offset that is
+ * negative or above 2^40; dst [0, 3 T H W) overlapping the source extent, which runs from src + min(chan) to the last
+ * byte of the last pixel's sample (of its group of pixel_stride bytes where pixel_stride is 3 or 4 and every chan <
+ * pixel_stride).
+ * writes: dst [0, 3 T H W) and nothing else.  reads: the three sample bytes of each pixel (t, y, x) of [0, T) x [0, H) x
+ * [0, W); where pixel_stride is 3 or 4 and every chan < pixel_stride, the pixel_stride bytes of that pixel's group (an
+ * ignored byte may be read; its value changes nothing); nothing else - no pitch padding, no other row or frame, no byte
+ * before a row's first group or after its last. */
+typedef struct {
+    const unsigned char* src;
+    long long frame_stride, row_stride, pixel_stride;     /* bytes */
+    long long chan[3];                                    /* byte offsets of R, G, B */
+} tdc_rgb_source;
+int tdc_pack_rgb(const tdc_rgb_source* s, int T, int H, int W, unsigned char* dst /* [T, H, W, 3] contiguous */, void* stream);
+
 /* ---- BEATs audio front end --------------------------------------------------------------------------
  * kaldi fbank as BEATs.preprocess calls it (tdc/audio_models/beats/BEATs.py:115-129: torchaudio.compliance.kaldi.fbank,
  * 128 mel bins, 16 kHz, 25 ms / 10 ms, povey window, pre-emphasis 0.97, DC removal, dither 0, snip_edges) on B

@@ -1075,7 +1075,9 @@ class FrameSource:
     image_size defaults to the frames' (H, W); frames of another shape raise here, before any engine call.  A
     preprocess.YuvFrames (4:2:0 planes; .shape is that of the RGB frames they convert to) is a source like any other: the
     engine converts what it keeps.  So is a preprocess.Oriented over either kind (.shape is that of
-    the upright frames, so image_size defaults to the upright (H', W'))."""
+    the upright frames, so image_size defaults to the upright (H', W')), and a preprocess.RgbFrames
+    (channel-first, B G R, 4-byte-pixel or gray pictures; .shape is that of the RGB frames it stands for; DESIGN.md section
+    24)."""
 
     def __init__(self, frames, image_size=None, cache=None):
         self.frames, self.cache = frames, cache

@@ -163,6 +163,11 @@ class HdrDesc(C.Structure):
                 ("inv_p2", C.c_float), ("gamut", C.c_float * 9)]
 
 
+class RgbSource(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("frame_stride", C.c_longlong), ("row_stride", C.c_longlong), ("pixel_stride", C.c_longlong),
+                ("chan", C.c_longlong * 3)]
+
+
 class ProfRec(C.Structure):
     _fields_ = [("kind", C.c_int), ("tag", C.c_int), ("ms", C.c_float), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
                 ("act", C.c_int), ("res", C.c_int), ("out_f32", C.c_int), ("W", C.c_void_p), ("flops", C.c_double)]
@@ -228,6 +233,7 @@ SIGNATURES = {
     "tdc_yuv_hdr_to_rgb": (C.c_int, [C.POINTER(YuvPlanes), C.POINTER(YuvCoef), C.POINTER(HdrDesc), C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p]),
     "tdc_orient_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "tdc_pack_rgb": (C.c_int, [C.POINTER(RgbSource), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdc_fbank_frames": (C.c_int, [C.c_longlong]),
     "tdc_fbank": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),

@@ -558,7 +558,8 @@ class CambrianMetaModel:
         single images: images[0] is uint8 [bsz, H, W, 3].  An entry images[0][i] (videos), or images[0] itself (single images),
         may be a preprocess.YuvFrames - NV12 / I420 planes as the decoder wrote them - or a
         preprocess.Oriented over either kind: stored frames plus their display rotation / mirror (image_sizes
-        is then the upright frames').  Every sample runs through VideoEncoder.encode_frames: a1 first, then
+        is then the upright frames') - or a preprocess.RgbFrames: channel-first [T, 3, H, W], B G R, RGBA / BGRA / ARGB or gray
+        pictures as their source wrote them, bare or inside an Oriented.  Every sample runs through VideoEncoder.encode_frames: a1 first, then
         only the kept frames are uploaded and resized - the 10-tuple is bit for bit the pixel call's on
         preprocess.process_images of the same frames.  Absent / False: pixels.  Composes with `config.tdc_video_cache_bytes`;
         set together with `config.tdc_feature_inputs`, `tdc_shard_frames`, `tdc_batch_frames`, `tdc_shard_cache_bytes` or

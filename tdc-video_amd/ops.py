@@ -818,6 +818,25 @@ def orient_frames(frames, quarters, hflip, out=None):
     return out
 
 
+def pack_rgb(src, frame_stride, row_stride, pixel_stride, chan, T, H, W, out=None):
+    """T pictures of H x W pixels described inside the uint8 GPU tensor `src` -> packed frames uint8 [T, H, W, 3]
+    (tdc_pack_rgb): out[t, y, x, c] is the byte frame_stride * t + row_stride * y + pixel_stride * x +
+    chan[c] past src's first element - byte strides and the byte offsets of the R, G and B sample, all non-negative
+    (preprocess.RgbFrames.descriptor() makes them).  The caller answers for the described bytes lying inside src's memory.
+    out: a contiguous uint8 [T, H, W, 3] tensor on src's device that shares no byte with the described source."""
+    assert src.is_cuda and src.dtype == torch.uint8, "src must be a uint8 CUDA tensor"
+    chan = tuple(int(c) for c in chan)
+    assert len(chan) == 3, "chan holds the byte offsets of R, G and B"
+    shape = (int(T), int(H), int(W), 3)
+    if out is None:
+        out = torch.empty(shape, device=src.device, dtype=torch.uint8)
+    assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous() and out.device == src.device
+    desc = L.RgbSource(src.data_ptr(), int(frame_stride), int(row_stride), int(pixel_stride), (C.c_longlong * 3)(*chan))
+    with torch.cuda.device(src.device):
+        L.check(L.load().tdc_pack_rgb(C.byref(desc), shape[0], shape[1], shape[2], _ptr(out), _stream()), "tdc_pack_rgb")
+    return out
+
+
 def relpos_gate(q, rows, heads, head_dim, w2, b2, grep_a, out=None):
     """q: [rows, ld] 16-bit view (un-scaled q_proj output) -> gate fp32 [rows, heads]."""
     assert q.is_cuda and q.dim() == 2 and q.stride(1) == 1 and q.shape[0] >= rows and q.shape[1] >= heads * head_dim

@@ -1267,7 +1267,9 @@ class VideoEncoder:
         preprocess.YuvFrames (NV12 / I420 planes): the kept frames' planes are uploaded and converted to
         RGB on the device in front of the same resize, and `frames[idx]` above reads as the RGB frames they convert to.  Either
         kind may be wrapped in a preprocess.Oriented (a display rotation / mirror): the kept frames are
-        turned upright on the device and `frames[idx]` reads as the upright frames."""
+        turned upright on the device and `frames[idx]` reads as the upright frames.  frames may also be a preprocess.RgbFrames
+        (channel-first, B G R, 4-byte-pixel or gray pictures, pitched or cropped), bare or inside an
+        Oriented: the kept frames are packed to R G B on the device and `frames[idx]` reads as the frames they stand for."""
         if len(self.frame_towers) != 2:
             raise ValueError("frame_towers is a pair of {R, mean, std} dicts (SigLIP, DINOv2), got %d" % len(self.frame_towers))
         px_siglip, px_dino = preprocess.preprocess_selected(frames, idx, self.frame_towers, self.dtype, self.frame_slab,
@@ -1282,7 +1284,10 @@ class VideoEncoder:
         arguments are encode_video's; image_size defaults to the frames' (H, W), what the reference's drivers pass.  info
         gains frames_in and frames_resized.  image=True: one frame as a single image - the towers and the connector only.
         aux: as encode_video's.  frames may be a preprocess.YuvFrames (4:2:0 planes as the decoder wrote them): the result is
-        that of the RGB frames the planes convert to."""
+        that of the RGB frames the planes convert to.  frames may be a preprocess.RgbFrames - [T0, 3, H, W]
+        as torchcodec / torchvision.io return it, B G R as OpenCV does, RGBA / BGRA / ARGB surfaces, a gray plane, any of them
+        pitched or cropped: the result is that of the [T0, H, W, 3] frames Pillow's .convert("RGB") makes of them (DESIGN.md
+        section 24)."""
         return encode_frames_with(self, frames, budget_text_len, n_text_tokens, prompt_ids, audio, frame_cap, splice,
                                   video_index, info, cache, image_size, image, aux)
 

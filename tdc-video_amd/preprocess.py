@@ -489,6 +489,211 @@ def _preprocess_selected_yuv(yuv, idx, towers, dtype, slab, device, out, stats):
     return [o[:T] for o in out]
 
 
+# ---- channel-first, BGR, RGBA and gray frames -------------------------------------------------------
+RGB_LAYOUTS = ("hwc", "chw")
+
+
+def channel_order(order, C):
+    """the stored channels (iR, iG, iB) an `order` string names among C stored channels: one letter per stored channel,
+    case-insensitive - each of r, g, b exactly once, or l (gray) exactly once and then iR = iG = iB, every other letter an
+    ignored a or x; anything else, or a length other than C, raises ValueError"""
+    if not isinstance(order, str):
+        raise ValueError("order must be a string with one letter per stored channel, got %r" % (order,))
+    o = order.lower()
+    if len(o) != C or not 1 <= C <= 4:
+        raise ValueError("order %r names %d channel(s), the data stores %d (1 to 4 are taken)" % (order, len(o), C))
+    if any(ch not in "rgblax" for ch in o):
+        raise ValueError("order %r: the letters are r, g, b, l (gray) and the ignored a, x" % (order,))
+    if "l" in o:
+        if o.count("l") != 1 or any(ch in o for ch in "rgb"):
+            raise ValueError("order %r: a gray order holds l exactly once beside ignored a / x" % (order,))
+        return (o.index("l"),) * 3
+    if any(o.count(ch) != 1 for ch in "rgb"):
+        raise ValueError("order %r: a colour order holds each of r, g, b exactly once beside ignored a / x" % (order,))
+    return tuple(o.index(ch) for ch in "rgb")
+
+
+class RgbFrames:
+    """T0 decoded pictures of one size in the layout their source writes, described and not copied: `data` is a uint8 torch
+    tensor or numpy array, on the host or the device, taken through its strides as it is - a row pitch, a crop or a slice of
+    frames is a valid source (a negative numpy stride raises ValueError).  layout "hwc": [T0, H, W, C], what OpenCV, Pillow
+    and hardware RGB surfaces write; "chw": [T0, C, H, W], what torchcodec and torchvision.io return; a 3-D [T0, H, W] is one
+    gray channel (order "l") under either.  `order` names the C stored channels, 1 to 4 of them, one letter each,
+    case-insensitive: r, g, b once each plus ignored a / x ("rgb", "bgr", "rgba", "bgra", "argb", "abgr", "rgbx", ...), or
+    l once plus ignored a / x ("l", "la", "al").  The RGB frames it stands for are what Pillow's .convert("RGB") gives:
+    alpha is dropped and not composited, gray is replicated into R, G and B.  .shape is (T0, H, W, 3), theirs; r[a:b] is an
+    RgbFrames over the same memory.  The kept frames are packed on the device, in front of the resize (tdc_pack_rgb);
+    layout "hwc" with order "rgb" is the frames entry's own form and issues no launch."""
+
+    def __init__(self, data, layout="hwc", order="rgb"):
+        if layout not in RGB_LAYOUTS:
+            raise ValueError("layout must be one of %s, got %r" % (RGB_LAYOUTS, layout))
+        if is_rgb_frames(data) or is_oriented(data) or is_yuv_frames(data):
+            raise ValueError("data must be a uint8 torch tensor or numpy array, got a %s: an RgbFrames describes memory (an "
+                             "Oriented goes around it, not inside)" % type(data).__name__)
+        if isinstance(data, np.ndarray):
+            if data.dtype != np.uint8:
+                raise ValueError("data must be uint8, got %s" % (data.dtype,))
+            if any(s < 0 for s in data.strides):
+                raise ValueError("data has a negative stride: a flipped view is not described here (preprocess.Oriented mirrors)")
+            data = torch.from_numpy(data)
+        if not torch.is_tensor(data):
+            raise ValueError("data must be a uint8 torch tensor or numpy array, got %s" % type(data).__name__)
+        if data.dtype != torch.uint8 or data.dim() not in (3, 4) or 0 in data.shape:
+            raise ValueError("data must be uint8 [T0, H, W, C], [T0, C, H, W] or [T0, H, W] with no empty dimension, got %s %s"
+                             % (data.dtype, tuple(data.shape)))
+        if data.dim() == 3:
+            data = data.unsqueeze(3 if layout == "hwc" else 1)
+        T0, H, W, C = (data.shape[i] for i in ((0, 1, 2, 3) if layout == "hwc" else (0, 2, 3, 1)))
+        self.index = channel_order(order, int(C))
+        if T0 > 65535 or H > 65535 or W > 65535:
+            raise ValueError("data %s: at most 65535 frames, rows and pixels per row" % (tuple(data.shape),))
+        self.data, self.layout, self.order = data, layout, order.lower()
+        self.shape = (int(T0), int(H), int(W), 3)
+
+    @classmethod
+    def chw(cls, data, order="rgb"):
+        """channel-first frames [T0, C, H, W]: a torchcodec / torchvision.io decoder's default"""
+        return cls(data, "chw", order)
+
+    @classmethod
+    def gray(cls, data):
+        """one gray plane per frame [T0, H, W], replicated into R, G and B"""
+        if not hasattr(data, "ndim") or data.ndim != 3:
+            raise ValueError("RgbFrames.gray takes [T0, H, W], got %s" % (tuple(getattr(data, "shape", ())),))
+        return cls(data, "hwc", "l")
+
+    @property
+    def is_identity(self):
+        """[T0, H, W, 3] in R, G, B order: what the frames entries take as it is"""
+        return self.layout == "hwc" and self.index == (0, 1, 2) and self.data.shape[3] == 3
+
+    @property
+    def is_cuda(self):
+        return self.data.is_cuda
+
+    @property
+    def device(self):
+        return self.data.device
+
+    @property
+    def is_gray(self):
+        return self.index[0] == self.index[1] == self.index[2]
+
+    def __getitem__(self, s):
+        if not isinstance(s, slice) or s.step not in (None, 1):
+            raise TypeError("RgbFrames takes a slice of frames a:b, got %r" % (s,))
+        return RgbFrames(self.data[s], self.layout, self.order)
+
+    def descriptor(self):
+        """(byte offset of the base inside data's storage, frame_stride, row_stride, pixel_stride, chan) as Python ints, from
+        the strides alone: the R, G, B sample of pixel (t, y, x) is the byte base + t * frame_stride + y * row_stride +
+        x * pixel_stride + chan[c] of the storage.  What tdc_pack_rgb takes, with data's first element as the base."""
+        st = self.data.stride()
+        fs, rs, ps, cs = (st[i] for i in ((0, 1, 2, 3) if self.layout == "hwc" else (0, 2, 3, 1)))
+        return int(self.data.storage_offset()), int(fs), int(rs), int(ps), tuple(int(i * cs) for i in self.index)
+
+    def pack(self, out):
+        """ONE tdc_pack_rgb launch: these frames (on the device) -> out uint8 [T, H, W, 3]"""
+        _, fs, rs, ps, chan = self.descriptor()
+        T, H, W, _ = self.shape
+        return ops.pack_rgb(self.data, fs, rs, ps, chan, T, H, W, out=out)
+
+    def dense_like(self, T, make):
+        """(staging tensor, RgbFrames over it) for T frames in this source's own layout, made dense: "hwc" [T, H, W, C], every
+        stored channel; "chw" only the planes that are used, in R, G, B order (gray: the one), each plane's T frames
+        together.  make(shape) allocates the uint8 staging tensor."""
+        _, H, W, _ = self.shape
+        if self.layout == "hwc":
+            stage = make((T, H, W, self.data.shape[3]))
+            return stage, RgbFrames(stage, "hwc", self.order)
+        stage = make((1 if self.is_gray else 3, T, H, W))
+        return stage, RgbFrames(stage.permute(1, 0, 2, 3), "chw", "l" if self.is_gray else "rgb")
+
+    def gather_into(self, staged, sel):
+        """the frames `sel` (an index tensor on data's device) -> the frames of `staged` (dense_like), by index_select on views:
+        only the kept frames' used bytes are read - no pitch padding, and of "chw" no plane that is ignored"""
+        if self.layout == "hwc":
+            torch.index_select(self.data, 0, sel, out=staged.data)
+        else:
+            for k, i in enumerate(self.index[:1] if self.is_gray else self.index):
+                torch.index_select(self.data[:, i], 0, sel, out=staged.data[:, k])
+        return staged
+
+    @property
+    def is_dense(self):
+        """contiguous, and every stored byte a used one or an interleaved neighbour of one: uploaded as it lies"""
+        return self.data.is_contiguous() and (self.layout == "hwc" or self.data.shape[1] == (1 if self.is_gray else 3))
+
+
+def is_rgb_frames(x):
+    """an RgbFrames, recognised by its members (the package can be imported under two names: not by isinstance)"""
+    return all(hasattr(x, k) for k in ("data", "layout", "order", "index", "descriptor", "shape")) and not torch.is_tensor(x)
+
+
+def gather_pixels(rgb, idx, pin=True):
+    """the frames idx (check_indices; not None) of a host RgbFrames, gathered into ONE dense staging tensor (pinned when
+    `pin`) in the source's own layout -> (an RgbFrames over the staging tensor, the staging tensor).  Frames outside idx,
+    pitch padding and ignored planes of a "chw" source are never read.  The staging holds T * H * W * C bytes for "hwc",
+    T * H * W * 3 for "chw" colour and T * H * W for gray."""
+    stage, staged = rgb.dense_like(len(idx), lambda shape: torch.empty(shape, dtype=torch.uint8, pin_memory=pin))
+    return rgb.gather_into(staged, torch.tensor(idx)), stage
+
+
+def selected_pixels(rgb, idx, device):
+    """the frames idx (check_indices) of an RgbFrames as an RgbFrames on `device` -> (it, bytes uploaded).  Host data: the kept
+    frames go through gather_pixels and one upload of exactly their bytes (dense pinned data with every frame kept is
+    uploaded from where it lies).  Device data: read in place through its strides when every frame is kept, gathered on the
+    device in its own layout otherwise."""
+    if rgb.is_cuda:
+        if idx is None:
+            return RgbFrames(rgb.data.to(device), rgb.layout, rgb.order), 0
+        _, staged = rgb.dense_like(len(idx), lambda shape: torch.empty(shape, dtype=torch.uint8, device=rgb.device))
+        rgb.gather_into(staged, torch.tensor(idx, device=rgb.device))
+        return RgbFrames(staged.data.to(device), staged.layout, staged.order), 0
+    if idx is None and rgb.data.is_pinned() and rgb.is_dense:
+        return RgbFrames(rgb.data.to(device, non_blocking=True), rgb.layout, rgb.order), rgb.data.numel()
+    staged, stage = gather_pixels(rgb, list(range(rgb.shape[0])) if idx is None else idx)
+    dev = stage.to(device, non_blocking=True)
+    return RgbFrames(dev if rgb.layout == "hwc" else dev.permute(1, 0, 2, 3), staged.layout, staged.order), stage.numel()
+
+
+def _preprocess_selected_rgb(rgb, idx, towers, dtype, slab, device, out, stats):
+    """preprocess_selected for an RgbFrames.  [T0, H, W, 3] in R, G, B order issues exactly the launches of the wrapped tensor.
+    Otherwise per slab of kept frames ONE tdc_pack_rgb launch into a [slab, H, W, 3] scratch, then tdc_preprocess_frames per
+    tower on that scratch - the RGB path's launches on the frames the source stands for.  A slab is packed once and both
+    towers read it.  Both scratches are slab-sized and serve the whole video."""
+    if rgb.is_identity:
+        return preprocess_selected(rgb.data, idx, towers, dtype, slab, device, out, stats)
+    idx = check_indices(idx, rgb.shape[0])
+    _check_dtype_slab(dtype, slab)
+    if device is None:
+        device = rgb.device if rgb.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    T0, H, W, _ = rgb.shape
+    kept, uploaded = selected_pixels(rgb, idx, device)
+    T = kept.shape[0]
+    if stats is not None:
+        stats.update(frames_in=T0, frames_resized=T, bytes_uploaded=uploaded)
+    out = _outputs(out, towers, T, dtype, device)
+    lib = L.load()
+    n0 = min(slab, T)
+    nscr = max(lib.tdc_preprocess_scratch_bytes(n0, H, W, t["R"]) for t in towers)
+    scratch = torch.empty(max(nscr, 1), dtype=torch.uint8, device=device)
+    packed = torch.empty((n0, H, W, 3), dtype=torch.uint8, device=device)
+    tables = [_tables(max(H, W), t["R"], t["mean"], t["std"], device) for t in towers]
+    with torch.cuda.device(device):
+        for s in range(0, T, slab):
+            n = min(slab, T - s)
+            kept[s:s + n].pack(packed[:n])
+            for t, o, (bounds, coeffs, lut) in zip(towers, out, tables):
+                pad = [int(x * 255) for x in t["mean"]]   # expand2square background (tdc/mm_datautils.py:302-304)
+                L.check(lib.tdc_preprocess_frames(ops._ptr(packed), n, H, W, t["R"], ops._ptr(bounds), ops._ptr(coeffs),
+                                                  coeffs.shape[1], pad[0], pad[1], pad[2], ops._ptr(lut), ops._ptr(o[s:s + n]), 0,
+                                                  ops._dtcode(dtype), ops._ptr(scratch), ops._stream()), "tdc_preprocess_frames")
+    return [o[:T] for o in out]
+
+
 # ---- display orientation (DESIGN.md section 23) ---------------------------------------------------------------------------
 ROTATIONS = (0, 90, 180, 270)
 # EXIF orientation -> (rotate, hflip): the clockwise turn that makes the stored picture upright, then a left-right mirror
@@ -498,8 +703,8 @@ EXIF_ORIENTATIONS = {1: (0, False), 2: (0, True), 3: (180, False), 4: (180, True
 
 class Oriented:
     """T0 stored frames and the display orientation that travels beside them, described and not copied: `frames` is what the
-    frames entries take - uint8 [T0, H, W, 3] (torch tensor or numpy array, host or device) or a YuvFrames of any kind -
-    as the decoder wrote it, `rotate` in {0, 90, 180, 270} the clockwise turn that makes a stored frame upright (the `rotate`
+    frames entries take - uint8 [T0, H, W, 3] (torch tensor or numpy array, host or device), a YuvFrames of any kind or an
+    RgbFrames - as the decoder wrote it, `rotate` in {0, 90, 180, 270} the clockwise turn that makes a stored frame upright (the `rotate`
     tag of MP4 / MOV), `hflip` a left-right mirror applied after the turn.  With S a stored frame [H, W, 3], the upright
     frame O is
         rotate   0: O[y, x] = S[y, x]                 rotate 180: O[y, x] = S[H-1-y, W-1-x]          both [H, W, 3]
@@ -516,7 +721,7 @@ class Oriented:
             raise ValueError("hflip must be True / False, got %r" % (hflip,))
         if is_oriented(frames):
             raise ValueError("frames is an Oriented already: compose the two orientations into one")
-        self.frames = frames if is_yuv_frames(frames) else check_frames(frames)
+        self.frames = frames if is_yuv_frames(frames) or is_rgb_frames(frames) else check_frames(frames)
         self.rotate, self.hflip, self.quarters = int(rotate), hflip, int(rotate) // 90
         T0, H, W, _ = self.frames.shape
         self.shape = (int(T0), int(W), int(H), 3) if self.quarters & 1 else (int(T0), int(H), int(W), 3)
@@ -549,14 +754,16 @@ def is_oriented(x):
 
 def _preprocess_selected_oriented(o, idx, towers, dtype, slab, device, out, stats):
     """preprocess_selected for an Oriented.  The identity issues exactly the launches of the wrapped frames.  Otherwise a1's
-    frames, or planes, are uploaded as the wrapped frames' are, and per slab of kept frames: YUV planes are converted by their
-    one launch into a [slab, H, W, 3] scratch, ONE tdc_orient_frames launch writes the upright frames into a [slab, H', W', 3]
+    frames, or planes, are uploaded as the wrapped frames' are, and per slab of kept frames: YUV planes are converted, and an
+    RgbFrames is packed, by their one launch into a [slab, H, W, 3] scratch, ONE tdc_orient_frames launch writes the upright frames into a [slab, H', W', 3]
     scratch, and tdc_preprocess_frames runs per tower on that scratch - the RGB path's launches on the upright frames.  A slab
     is turned once and both towers read it.  The scratches are slab-sized and serve the whole video."""
     inner = o.frames
     if o.is_identity:
         return preprocess_selected(inner, idx, towers, dtype, slab, device, out, stats)
-    yuv = is_yuv_frames(inner)
+    if is_rgb_frames(inner) and inner.is_identity:
+        inner = inner.data
+    yuv, packs = is_yuv_frames(inner), is_rgb_frames(inner)
     idx = check_indices(idx, o.shape[0])
     _check_dtype_slab(dtype, slab)
     if device is None:
@@ -567,6 +774,9 @@ def _preprocess_selected_oriented(o, idx, towers, dtype, slab, device, out, stat
     if yuv:
         planes, uploaded = selected_planes(inner, idx, device)
         T = planes[0].shape[0]
+    elif packs:
+        kept, uploaded = selected_pixels(inner, idx, device)
+        T = kept.shape[0]
     else:
         kept, uploaded = selected_frames(inner, idx, device)
         T = kept.shape[0]
@@ -577,7 +787,7 @@ def _preprocess_selected_oriented(o, idx, towers, dtype, slab, device, out, stat
     n0 = min(slab, T)
     nscr = max(lib.tdc_preprocess_scratch_bytes(n0, Ho, Wo, t["R"]) for t in towers)
     scratch = torch.empty(max(nscr, 1), dtype=torch.uint8, device=device)
-    rgb = torch.empty((n0, H, W, 3), dtype=torch.uint8, device=device) if yuv else None
+    rgb = torch.empty((n0, H, W, 3), dtype=torch.uint8, device=device) if yuv or packs else None
     upright = torch.empty((n0, Ho, Wo, 3), dtype=torch.uint8, device=device)
     tables = [_tables(max(Ho, Wo), t["R"], t["mean"], t["std"], device) for t in towers]
     with torch.cuda.device(device):
@@ -585,7 +795,9 @@ def _preprocess_selected_oriented(o, idx, towers, dtype, slab, device, out, stat
             n = min(slab, T - s)
             if yuv:
                 inner.to_rgb([p[s:s + n] for p in planes], rgb[:n])
-            ops.orient_frames(rgb[:n] if yuv else kept[s:s + n], o.quarters, o.hflip, out=upright[:n])
+            elif packs:
+                kept[s:s + n].pack(rgb[:n])
+            ops.orient_frames(rgb[:n] if yuv or packs else kept[s:s + n], o.quarters, o.hflip, out=upright[:n])
             for t, dst, (bounds, coeffs, lut) in zip(towers, out, tables):
                 pad = [int(x * 255) for x in t["mean"]]   # expand2square background (tdc/mm_datautils.py:302-304)
                 L.check(lib.tdc_preprocess_frames(ops._ptr(upright), n, Ho, Wo, t["R"], ops._ptr(bounds), ops._ptr(coeffs),
@@ -628,9 +840,14 @@ def preprocess_selected(frames, idx, towers=(SIGLIP, DINOV2), dtype=torch.float1
     out: one preallocated contiguous [>= T, 3, R, R] tensor of `dtype` per tower - rows [0, T) are written, nothing else, and
     the views out[j][:T] are returned.  stats: a dict that receives frames_in, frames_resized and bytes_uploaded.
     frames may be an Oriented over either kind: the kept frames are turned upright on the device, one
-    launch per slab, in front of the same resize - the result is what the upright frames give."""
+    launch per slab, in front of the same resize - the result is what the upright frames give.
+    frames may be an RgbFrames (an Oriented may hold one): channel-first, B G R, 4-byte-pixel or gray
+    pictures, pitched or cropped, packed to R G B on the device, one launch per slab, in front of the same resize - the result
+    is what the [T0, H, W, 3] frames Pillow's .convert("RGB") makes of them give."""
     if is_oriented(frames):
         return _preprocess_selected_oriented(frames, idx, towers, dtype, slab, device, out, stats)
+    if is_rgb_frames(frames):
+        return _preprocess_selected_rgb(frames, idx, towers, dtype, slab, device, out, stats)
     if is_yuv_frames(frames):
         return _preprocess_selected_yuv(frames, idx, towers, dtype, slab, device, out, stats)
     frames = check_frames(frames)
