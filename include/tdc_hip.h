@@ -637,6 +637,46 @@ typedef struct {
 int tdc_yuv_hdr_to_rgb(const tdc_yuv_planes* p, const tdc_yuv_coef* c, const tdc_hdr_desc* h, int T, int H, int W,
                        unsigned char* rgb /* [T, H, W, 3] contiguous */, void* stream);
 
+/* ---- packed YUV -> RGB: YUY2, UYVY, Y210, AYUV, Y410, Y416, v210 -------------------------------
+ * Surfaces in which luma and chroma share one row, little-endian.  A row is a run of groups; a group of P pixels is
+ *   TDC_YUVP_YUYV / YVYU / UYVY / VYUY   4 bytes, P = 2, in the order the name spells (YUYV = Y0 U Y1 V: YUY2)       bits 8
+ *   TDC_YUVP_Y210                        4 16-bit words Y0 U Y1 V, P = 2 (Y210, Y212, a Y216 container)               bits 10, 12
+ *   TDC_YUVP_VUYA / AYUV                 4 bytes, P = 1: V U Y A (Microsoft AYUV, VUYX) or A Y U V; A is ignored       bits 8
+ *   TDC_YUVP_Y410                        one 32-bit word, P = 1: U = bits 0-9, Y = 10-19, V = 20-29, 30-31 ignored     bits 10
+ *   TDC_YUVP_Y416                        4 16-bit words U Y V A, P = 1 (Y412, a Y416 container); A is ignored          bits 10, 12
+ *   TDC_YUVP_V210                        four 32-bit words, P = 6: w0 = Cb0 | Y0<<10 | Cr0<<20, w1 = Y1 | Cb1<<10 | Y2<<20,
+ *                                        w2 = Cr1 | Y3<<10 | Cb2<<20, w3 = Y4 | Cr2<<10 | Y5<<20; bits 30-31 ignored     bits 10
+ * A 16-bit word holds its sample as in tdc_yuv_planes: (w >> shift) & (2^bits - 1), shift = 16 - bits when msb_aligned, else 0.
+ * A row's read set is its ceil(W / P) whole groups.  Pixel (y, x) takes the luma of its position and the chroma pair of its
+ * group (4:2:2 and v210: pair x >> 1), replicated as in the entries above.
+ * h == NULL: the bytes are exactly those tdc_yuv_to_rgb writes for the same samples held in planes of `bits`, 4:2:2 or
+ * 4:4:4.  h != NULL (bits 10 or 12): exactly those of tdc_yuv_hdr_to_rgb.  The kernels run the same per-pixel device code.
+ * The host picks the form from alignment facts alone, same bytes: the group form (a thread owns one group of one row:
+ * byte, 16-bit or 32-bit loads, byte stores; any W, pitch, view and frame offset), or the vector form when W % 8 == 0 (v210:
+ * also W >= 24), base, pitch and (T > 1) frame stride are multiples of 16 and rgb of 8: eight pixels per thread (v210: 24) in
+ * 16-byte loads and 8-byte stores; what is left of a v210 row after its W / 24 such units (8 or 16 pixels) goes group by
+ * group, one 16-byte load each.
+ * TDC_E_BADARG before any launch: a null pointer (p, c, rgb, p->base); T, H or W outside [1, 65535]; an unknown format;
+ * bits the format does not take (above); msb_aligned not 0 or 1, or 1 for anything but Y210 / Y416; a base, pitch or frame
+ * stride that is not a multiple of the word size (2 for Y210 / Y416, 4 for Y410 / V210); pitch below the row's read set;
+ * for T > 1 a frame stride that does not clear the last row; the coefficient and y_off checks of tdc_yuv_to_rgb; with h:
+ * bits = 8 and everything tdc_yuv_hdr_to_rgb refuses about the descriptor.
+ * writes: rgb [T, H, W, 3] and nothing else.  reads: the ceil(W / P) groups of each of the H rows, plus - with h - exactly
+ * 2^bits floats at h->lut.  never read: pitch padding, the bytes between a frame's last row and the next frame.  read, but
+ * changing nothing: alpha, bits 30-31, the bits of a word outside the sample, the unused tail of a row's last group. */
+enum { TDC_YUVP_YUYV = 0, TDC_YUVP_YVYU = 1, TDC_YUVP_UYVY = 2, TDC_YUVP_VYUY = 3, TDC_YUVP_Y210 = 4, TDC_YUVP_VUYA = 5,
+       TDC_YUVP_AYUV = 6, TDC_YUVP_Y410 = 7, TDC_YUVP_Y416 = 8, TDC_YUVP_V210 = 9 };
+typedef struct {
+    const unsigned char* base;        /* first byte of frame 0 */
+    long long frame;                  /* bytes from frame to frame */
+    int pitch;                        /* bytes per row */
+    int format;                       /* TDC_YUVP_* */
+    int bits;                         /* significant bits of a sample */
+    int msb_aligned;                  /* 16-bit words: 1 = the sample is the word's high bits, 0 = its low bits */
+} tdc_yuv_packed;           /* host struct, passed by value into the kernel */
+int tdc_yuv_packed_to_rgb(const tdc_yuv_packed* p, const tdc_yuv_coef* c, const tdc_hdr_desc* h /* NULL: SDR */,
+                          int T, int H, int W, unsigned char* rgb /* [T, H, W, 3] contiguous */, void* stream);
+
 /* ---- display orientation of decoded RGB frames -------------------------------------------------
  * A decoder writes the coded picture; the orientation travels beside it (the display matrix or `rotate` tag of MP4 / MOV,
  * the EXIF orientation of a still).  src uint8 [T, H, W, 3] contiguous, the stored frames S -> dst uint8 [T, H', W', 3]

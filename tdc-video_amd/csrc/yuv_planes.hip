@@ -9,15 +9,9 @@
 //           samples in one load per plane - interleaved: the pairs from the lower of the two pointers, 32 bytes as two
 //           16-byte loads - and three 8-byte stores per row.
 // Bits of a word outside the sample are masked off before anything else sees them.  Both forms give the same bytes.
-#include "yuv_samples.h"
+#include "yuv_pixels.h"
 
 namespace {
-
-struct sdr_pixel {      // clip8 of each accumulator
-    __device__ __forceinline__ void operator()(const depth& d, int ar, int ag, int ab, unsigned& r, unsigned& g, unsigned& b) const {
-        r = clip_down(d, ar); g = clip_down(d, ag); b = clip_down(d, ab);
-    }
-};
 
 template <int BS, int SUBX, int FORM>
 __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(tdc_yuv_planes p, tdc_yuv_coef c, int T, int H, int W, int units_x,

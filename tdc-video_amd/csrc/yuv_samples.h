@@ -23,10 +23,11 @@ struct depth {
 };
 
 // out_bits: 8 (RGB bytes) or p.bits (codes at full depth)
-__device__ __forceinline__ depth depth_of(const tdc_yuv_planes& p, int out_bits) {
-    const int down = 16 + p.bits - out_bits;
-    return {p.msb_aligned ? 16 - p.bits : 0, (1u << p.bits) - 1u, 1 << (p.bits - 1), 1 << (down - 1), (1 << (16 + p.bits)) - 1, down};
+__device__ __forceinline__ depth depth_of(int bits, int msb_aligned, int out_bits) {
+    const int down = 16 + bits - out_bits;
+    return {msb_aligned ? 16 - bits : 0, (1u << bits) - 1u, 1 << (bits - 1), 1 << (down - 1), (1 << (16 + bits)) - 1, down};
 }
+__device__ __forceinline__ depth depth_of(const tdc_yuv_planes& p, int out_bits) { return depth_of(p.bits, p.msb_aligned, out_bits); }
 
 struct chroma_terms { int r, g, b; };   // the chroma part of each channel's accumulator, rounding term included
 
@@ -176,6 +177,20 @@ __device__ __forceinline__ void yuv_frames(const tdc_yuv_planes& p, const tdc_yu
 inline bool aligned(const void* p, unsigned a) { return ((unsigned long long)p & (a - 1)) == 0; }
 inline bool multiple(long long v, int a) { return v % a == 0; }
 
+// the coefficient and y_off checks of tdc_yuv_to_rgb at `bits`
+inline bool yuv_coef_ok(const tdc_yuv_coef* c, int bits) {
+    const int s = bits - 8;
+    if (c->y_off != 0 && c->y_off != 16 << s) return false;
+    const int coef[5] = {c->cy, c->crv, c->cgu, c->cgv, c->cbu};
+    for (int v : coef)
+        if (v < 0 || v > (1 << 18)) return false;
+    long long cmax = c->crv > c->cbu ? c->crv : c->cbu;
+    if ((long long)c->cgu + c->cgv > cmax) cmax = (long long)c->cgu + c->cgv;
+    // every accumulator stays inside int32 for every sample value
+    if (((long long)c->cy << bits) + (cmax << (bits - 1)) + (1ll << (15 + s)) >= (1ll << 31)) return false;
+    return true;
+}
+
 // everything tdc_yuv_to_rgb refuses, before any launch
 inline bool yuv_args_ok(const tdc_yuv_planes* p, const tdc_yuv_coef* c, int T, int H, int W, const unsigned char* rgb) {
     if (!p || !c || !rgb || !p->y || !p->u || !p->v) return false;
@@ -183,7 +198,7 @@ inline bool yuv_args_ok(const tdc_yuv_planes* p, const tdc_yuv_coef* c, int T, i
     if (p->bits != 8 && p->bits != 10 && p->bits != 12) return false;
     if (!((p->sub_x == 1 && p->sub_y == 1) || (p->sub_x == 1 && p->sub_y == 0) || (p->sub_x == 0 && p->sub_y == 0))) return false;
     if ((p->msb_aligned != 0 && p->msb_aligned != 1) || (p->msb_aligned && p->bits == 8)) return false;
-    const int bs = p->bits == 8 ? 1 : 2, s = p->bits - 8;       // bytes per sample
+    const int bs = p->bits == 8 ? 1 : 2;       // bytes per sample
     if (p->c_step != bs && p->c_step != 2 * bs) return false;
     if (bs == 2 && (!aligned(p->y, 2) || !aligned(p->u, 2) || !aligned(p->v, 2) || p->y_pitch % 2 || p->c_pitch % 2 ||
                     p->y_frame % 2 || p->c_frame % 2)) return false;
@@ -192,15 +207,7 @@ inline bool yuv_args_ok(const tdc_yuv_planes* p, const tdc_yuv_coef* c, int T, i
     // a frame stride must clear the plane's last row (it is used only between frames)
     if (T > 1 && (p->y_frame < (long long)(H - 1) * p->y_pitch + W * bs ||
                   p->c_frame < (long long)(Hc - 1) * p->c_pitch + p->c_step * (Wc - 1) + bs)) return false;
-    if (c->y_off != 0 && c->y_off != 16 << s) return false;
-    const int coef[5] = {c->cy, c->crv, c->cgu, c->cgv, c->cbu};
-    for (int v : coef)
-        if (v < 0 || v > (1 << 18)) return false;
-    long long cmax = c->crv > c->cbu ? c->crv : c->cbu;
-    if ((long long)c->cgu + c->cgv > cmax) cmax = (long long)c->cgu + c->cgv;
-    // every accumulator stays inside int32 for every sample value
-    if (((long long)c->cy << p->bits) + (cmax << (p->bits - 1)) + (1ll << (15 + s)) >= (1ll << 31)) return false;
-    return true;
+    return yuv_coef_ok(c, p->bits);
 }
 
 struct yuv_launch { int form, u_is_high, units_x; dim3 grid; };

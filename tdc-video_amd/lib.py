@@ -163,6 +163,15 @@ class HdrDesc(C.Structure):
                 ("inv_p2", C.c_float), ("gamut", C.c_float * 9)]
 
 
+class YuvPacked(C.Structure):
+    _fields_ = [("base", C.c_void_p), ("frame", C.c_longlong), ("pitch", C.c_int), ("format", C.c_int), ("bits", C.c_int),
+                ("msb_aligned", C.c_int)]
+
+
+# TDC_YUVP_* of include/tdc_hip.h
+YUV_PACKED_FORMATS = {"yuyv": 0, "yvyu": 1, "uyvy": 2, "vyuy": 3, "y210": 4, "vuya": 5, "ayuv": 6, "y410": 7, "y416": 8, "v210": 9}
+
+
 class RgbSource(C.Structure):
     _fields_ = [("src", C.c_void_p), ("frame_stride", C.c_longlong), ("row_stride", C.c_longlong), ("pixel_stride", C.c_longlong),
                 ("chan", C.c_longlong * 3)]
@@ -232,6 +241,8 @@ SIGNATURES = {
     "tdc_yuv_to_rgb": (C.c_int, [C.POINTER(YuvPlanes), C.POINTER(YuvCoef), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdc_yuv_hdr_to_rgb": (C.c_int, [C.POINTER(YuvPlanes), C.POINTER(YuvCoef), C.POINTER(HdrDesc), C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p]),
+    "tdc_yuv_packed_to_rgb": (C.c_int, [C.POINTER(YuvPacked), C.POINTER(YuvCoef), C.POINTER(HdrDesc), C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p]),
     "tdc_orient_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdc_pack_rgb": (C.c_int, [C.POINTER(RgbSource), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdc_fbank_frames": (C.c_int, [C.c_longlong]),

@@ -802,6 +802,53 @@ def yuv_hdr_to_rgb(y, u, v, c_step, coef, H, W, bits, msb_aligned, subsampling, 
     return out
 
 
+# packed YUV: name -> (bytes per word of the surface, words per group, pixels per group, bits taken)
+YUV_PACKED = {"yuyv": (1, 4, 2, (8,)), "yvyu": (1, 4, 2, (8,)), "uyvy": (1, 4, 2, (8,)), "vyuy": (1, 4, 2, (8,)),
+              "y210": (2, 4, 2, (10, 12)), "vuya": (1, 4, 1, (8,)), "ayuv": (1, 4, 1, (8,)), "y410": (4, 1, 1, (10,)),
+              "y416": (2, 4, 1, (10, 12)), "v210": (4, 4, 6, (10,))}
+
+
+def yuv_packed_words(fmt, W):
+    """the words (bytes, 16-bit or 32-bit words: YUV_PACKED) of a row's read set: its ceil(W / P) whole groups"""
+    _, per_group, P, _ = YUV_PACKED[fmt]
+    return (W + P - 1) // P * per_group
+
+
+def yuv_packed_to_rgb(surface, fmt, coef, H, W, bits, msb_aligned, hdr=None, out=None):
+    """T frames of packed YUV -> rgb uint8 [T, H, W, 3] (tdc_yuv_packed_to_rgb).  surface
+    [T, >= H, >= yuv_packed_words(fmt, W)] is a view on the GPU with a dense last dimension whose strides carry the pitch and the
+    frame stride: uint8 for the byte formats (yuyv, yvyu, uyvy, vyuy, vuya, ayuv), 16-bit words (torch.int16 as a bit pattern, or
+    torch.uint16) for y210 / y416, 32-bit words (torch.int32 as a bit pattern, or torch.uint32) for y410 / v210.  coef as
+    yuv_to_rgb takes it; with hdr (bits 10 or 12: the mapping yuv_hdr_to_rgb takes) as yuv_hdr_to_rgb takes it."""
+    assert fmt in YUV_PACKED, "fmt must be one of %s" % sorted(YUV_PACKED)
+    ws, _, _, depths = YUV_PACKED[fmt]
+    assert bits in depths, "fmt %s takes bits %s, got %r" % (fmt, depths, bits)
+    assert not msb_aligned or ws == 2, "msb_aligned is for the 16-bit-word formats"
+    words = {1: (torch.uint8,), 2: (torch.int16, getattr(torch, "uint16", None)), 4: (torch.int32, getattr(torch, "uint32", None))}[ws]
+    row = yuv_packed_words(fmt, W)
+    assert surface.is_cuda and surface.dim() == 3 and surface.stride(2) == 1 and surface.dtype in words, \
+        "surface must be a [T, rows, words] CUDA view of %d-byte words" % ws
+    T = surface.shape[0]
+    assert surface.shape[1] >= H and surface.shape[2] >= row, "surface %s is smaller than the frames" % (tuple(surface.shape),)
+    if out is None:
+        out = torch.empty(T, H, W, 3, device=surface.device, dtype=torch.uint8)
+    assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (T, H, W, 3) and out.is_contiguous()
+    # torch leaves the stride of a size-1 dimension arbitrary: one frame has no frame stride, one row the dense pitch
+    p = L.YuvPacked(surface.data_ptr(), ws * surface.stride(0) if T > 1 else 0, ws * (surface.stride(1) if surface.shape[1] > 1 else row),
+                    L.YUV_PACKED_FORMATS[fmt], bits, int(msb_aligned))
+    h = None
+    if hdr is not None:
+        lut = hdr["lut"]
+        assert lut.is_cuda and lut.dtype == torch.float32 and lut.dim() == 1 and lut.numel() == 1 << bits and lut.is_contiguous() \
+            and lut.device == surface.device, "hdr['lut'] must be float32 [2^bits] on the surface's device"
+        assert len(hdr["luma"]) == 3 and len(hdr["gamut"]) == 9
+        h = C.byref(L.HdrDesc(lut.data_ptr(), hdr["ootf_scale"], hdr["ootf_exp"], (C.c_float * 3)(*hdr["luma"]), hdr["inv_p2"],
+                              (C.c_float * 9)(*hdr["gamut"])))
+    L.check(L.load().tdc_yuv_packed_to_rgb(C.byref(p), C.byref(L.YuvCoef(*coef)), h, T, H, W, _ptr(out), _stream()),
+            "tdc_yuv_packed_to_rgb")
+    return out
+
+
 def orient_frames(frames, quarters, hflip, out=None):
     """stored frames uint8 [T, H, W, 3] (contiguous, on the GPU) -> the upright frames uint8 [T, H', W', 3]: `quarters`
     clockwise quarter turns, then a left-right mirror when `hflip` (tdc_orient_frames).  (H', W') is

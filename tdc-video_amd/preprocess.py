@@ -290,7 +290,9 @@ class YuvFrames:
     Beyond 8-bit 4:2:0: bits 10 or 12 - the planes are 16-bit words (numpy uint16, torch.uint16 where
     torch has it, or torch.int16 as a bit pattern; kept as torch.int16 views), the sample in their high bits (msb_aligned: P010,
     P012, P016) or their low bits (yuv420p10le and its kin); whatever the other bits hold is ignored.  subsampling "422":
-    Hc = H, "444": Hc = H and Wc = W.  bt2020 is taken at 10 and 12 bits, the depths it is defined for."""
+    Hc = H, "444": Hc = H and Wc = W.  bt2020 is taken at 10 and 12 bits, the depths it is defined for.
+    Packed surfaces - luma and chroma in one row: YUY2, UYVY, Y210, AYUV, Y410, Y416, v210 - are built by
+    YuvFrames.packed and its named forms and are PackedYuvFrames, which every consumer of a YuvFrames takes."""
 
     def __init__(self, y, chroma, c_step, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False,
                  subsampling="420", transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
@@ -368,6 +370,44 @@ class YuvFrames:
             raise ValueError("bits of a P016 surface must be 10 or 12, got %r" % (bits,))
         return cls(y, (uv,), 2, width, matrix, full_range, bits, True, "420", transfer, peak_nits, sdr_white, primaries)
 
+    @classmethod
+    def packed(cls, data, fmt, width=None, matrix="bt601", full_range=False, bits=None, msb_aligned=None, transfer="sdr",
+               peak_nits=1000.0, sdr_white=203.0, primaries=None):
+        """a packed surface, luma and chroma in one row: a PackedYuvFrames, which every consumer of a
+        YuvFrames takes.  fmt: one of YUV_PACKED_NAMES."""
+        return PackedYuvFrames(data, fmt, width, matrix, full_range, bits, msb_aligned, transfer, peak_nits, sdr_white, primaries)
+
+    @classmethod
+    def yuy2(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
+        """YUY2 / YUYV / ffmpeg yuyv422: bytes Y0 U Y1 V"""
+        return cls.packed(data, "yuyv", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries)
+
+    @classmethod
+    def uyvy(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
+        """UYVY / ffmpeg uyvy422: bytes U Y0 V Y1"""
+        return cls.packed(data, "uyvy", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries)
+
+    @classmethod
+    def y210(cls, data, width=None, matrix="bt601", full_range=False, bits=10, msb_aligned=True, transfer="sdr", peak_nits=1000.0,
+             sdr_white=203.0, primaries=None):
+        """Y210 / Y212 / a Y216 container (ffmpeg y210le, y212le): 16-bit words Y0 U Y1 V holding `bits` (10 or 12) bits"""
+        return cls.packed(data, "y210", width, matrix, full_range, bits, msb_aligned, transfer, peak_nits, sdr_white, primaries)
+
+    @classmethod
+    def ayuv(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
+        """Microsoft AYUV / VUYX / ffmpeg vuya, vuyx: bytes V U Y A (ffmpeg's `ayuv`, bytes A Y U V, is packed(data, "ayuv"))"""
+        return cls.packed(data, "vuya", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries)
+
+    @classmethod
+    def y410(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
+        """Y410 / ffmpeg xv30le: one 32-bit word per pixel, U = bits 0-9, Y = 10-19, V = 20-29"""
+        return cls.packed(data, "y410", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries)
+
+    @classmethod
+    def v210(cls, data, width, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
+        """v210: six pixels in four 32-bit words; `width` is required (a row holds whole blocks, often padded to 128 bytes)"""
+        return cls.packed(data, "v210", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries)
+
     @property
     def sample_size(self):
         """bytes per sample: 1 at 8 bits, 2 above"""
@@ -409,6 +449,120 @@ class YuvFrames:
         if self.is_420_8bit:
             return ops.yuv420_to_rgb(y, u, v, self.c_step, self.coef, H, W, out=out)
         return ops.yuv_to_rgb(y, u, v, self.c_step, self.coef, H, W, self.bits, self.msb_aligned, self.subsampling, out=out)
+
+
+# ---- packed YUV surfaces ----------------------------------------------------------------------------
+# name -> (the kernel's format, default bits, the depths the name takes)
+YUV_PACKED_NAMES = {"yuyv": ("yuyv", 8, (8,)), "yuy2": ("yuyv", 8, (8,)), "yvyu": ("yvyu", 8, (8,)), "uyvy": ("uyvy", 8, (8,)),
+                    "vyuy": ("vyuy", 8, (8,)), "y210": ("y210", 10, (10, 12)), "y212": ("y210", 12, (12,)), "y216": ("y210", None, (10, 12)),
+                    "vuya": ("vuya", 8, (8,)), "vuyx": ("vuya", 8, (8,)), "ayuv": ("ayuv", 8, (8,)), "y410": ("y410", 10, (10,)),
+                    "y412": ("y416", 12, (12,)), "y416": ("y416", None, (10, 12)), "v210": ("v210", 10, (10,))}
+
+
+def _packed_words(p, fmt, ws):
+    """a packed surface as a torch tensor [T0, H, words] over the same memory, the last dimension dense: uint8 for the byte
+    formats, 16-bit words as _plane keeps them (torch.int16), 32-bit words (numpy uint32, torch.uint32 or torch.int32) as
+    torch.int32 - bit patterns the kernel takes its samples out of"""
+    np_dt, t_dt, kind = {1: (np.uint8, torch.uint8, "uint8"), 2: (np.uint16, torch.int16, "uint16 (or torch.int16 as a bit pattern)"),
+                         4: (np.uint32, torch.int32, "uint32 (or torch.int32 as a bit pattern)")}[ws]
+    if isinstance(p, np.ndarray):
+        if p.dtype != np_dt:
+            raise ValueError("data must be %s for fmt %r, got %s" % (kind, fmt, p.dtype))
+        if any(s < 0 for s in p.strides):
+            raise ValueError("data has a negative stride")
+        p = torch.from_numpy(p if ws == 1 else p.view({2: np.int16, 4: np.int32}[ws]))
+    if not torch.is_tensor(p):
+        raise ValueError("data must be a %s torch tensor or numpy array for fmt %r, got %s" % (kind, fmt, type(p).__name__))
+    if ws != 1 and p.dtype == getattr(torch, "uint%d" % (8 * ws), None):
+        p = p.view(t_dt)
+    if p.dtype != t_dt or p.dim() != 3 or 0 in p.shape:
+        raise ValueError("data must be %s [T0, H, row] with no empty dimension for fmt %r, got %s %s" % (kind, fmt, p.dtype, tuple(p.shape)))
+    if p.stride(2) != 1 and p.shape[2] > 1:
+        raise ValueError("data: the last dimension must be dense, got stride %d" % p.stride(2))
+    return p
+
+
+class PackedYuvFrames(YuvFrames):
+    """T0 frames of packed YUV of one size, described and not copied (YuvFrames.packed and its named forms): ONE surface
+    `data` [T0, H, row] whose rows hold luma and chroma together - uint8 for the byte formats (yuyv / yuy2, yvyu, uyvy, vyuy:
+    4:2:2; vuya / vuyx, ayuv: 4:4:4), 16-bit words for y210 / y212 / y216 (4:2:2) and y412 / y416 (4:4:4), 32-bit words for
+    y410 and v210 - on the host or the device, with any row and frame stride.  A row holds ceil(width / P) whole groups of P
+    pixels; width defaults to the row's whole groups times P and is required for v210.  bits defaults to the name's (y216 and
+    y416 are containers: give 10 or 12), msb_aligned to True for the 16-bit-word formats.  Everything else is YuvFrames': the
+    matrix, the range, the transfer (pq / hlg at 10 and 12 bits), .shape, slicing, and the members its consumers use - .y is
+    the surface, planes() one view of it cut to the read set, to_rgb ONE tdc_yuv_packed_to_rgb launch."""
+
+    def __init__(self, data, fmt, width=None, matrix="bt601", full_range=False, bits=None, msb_aligned=None, transfer="sdr",
+                 peak_nits=1000.0, sdr_white=203.0, primaries=None):
+        if fmt not in YUV_PACKED_NAMES:
+            raise ValueError("fmt must be one of %s, got %r" % (sorted(YUV_PACKED_NAMES), fmt))
+        self.name = fmt
+        self.fmt, default_bits, depths = YUV_PACKED_NAMES[fmt]
+        ws, per_group, P, _ = ops.YUV_PACKED[self.fmt]
+        if bits is None:
+            bits = default_bits
+        if isinstance(bits, bool) or bits not in depths:
+            raise ValueError("bits of fmt %r must be %s, got %r" % (fmt, " or ".join(str(b) for b in depths), bits))
+        if msb_aligned is None:
+            msb_aligned = ws == 2
+        if not isinstance(msb_aligned, bool) or (msb_aligned and ws != 2):
+            raise ValueError("msb_aligned must be True / False, and False for fmt %r (it places a sample in a 16-bit word), got %r"
+                             % (fmt, msb_aligned))
+        if matrix == "bt2020" and bits == 8:
+            raise ValueError("matrix bt2020 is taken at 10 and 12 bits, the depths it is defined for; 8-bit surfaces take %s"
+                             % sorted(m for m in YUV_MATRICES if m != "bt2020"))
+        self.y = _packed_words(data, fmt, ws)
+        self.chroma, self.c_step = (), 0
+        self.matrix, self.full_range = matrix, full_range
+        self.bits, self.msb_aligned = bits, msb_aligned
+        self.subsampling = "422" if P != 1 else "444"
+        self.sub_x, self.sub_y = ops.YUV_SUBSAMPLING[self.subsampling]
+        if primaries is None:
+            primaries = "bt2020" if matrix == "bt2020" else "bt709"
+        if primaries not in YUV_PRIMARIES:
+            raise ValueError("primaries must be None or one of %s, got %r" % (YUV_PRIMARIES, primaries))
+        self.transfer, self.peak_nits, self.sdr_white, self.primaries = transfer, peak_nits, sdr_white, primaries
+        if transfer == "sdr":
+            _check_nits(peak_nits, sdr_white)
+            self.coef, self.hdr = yuv_coefficients(matrix, full_range, bits), None
+        else:
+            self.coef = yuv_code_coefficients(matrix, full_range, bits)
+            self.hdr = dict(_hdr_scalars(transfer, bits, peak_nits, sdr_white),
+                            gamut=GAMUT_2020_TO_709 if primaries == "bt2020" else GAMUT_IDENTITY)
+        T0, H, row = self.y.shape
+        if width is None:
+            if self.fmt == "v210":
+                raise ValueError("width is required for fmt 'v210': a row holds whole blocks of six pixels")
+            width = row // per_group * P
+        W = int(width)
+        if W < 1 or ops.yuv_packed_words(self.fmt, W) > row:
+            raise ValueError("width %r needs rows of %d words of %d byte(s) for fmt %r, data has %d"
+                             % (width, ops.yuv_packed_words(self.fmt, max(W, 1)), ws, fmt, row))
+        if T0 > 65535 or H > 65535 or W > 65535:
+            raise ValueError("data %s: at most 65535 frames, rows and pixels per row" % (tuple(self.y.shape),))
+        self.shape = (T0, H, W, 3)
+
+    def __getitem__(self, s):
+        if not isinstance(s, slice) or s.step not in (None, 1):
+            raise TypeError("YuvFrames takes a slice of frames a:b, got %r" % (s,))
+        return PackedYuvFrames(self.y[s], self.name, self.shape[2], self.matrix, self.full_range, self.bits, self.msb_aligned,
+                               self.transfer, self.peak_nits, self.sdr_white, self.primaries)
+
+    def planes(self):
+        """the read set as ONE view: data [T0, H, the words of ceil(W / P) groups] - the pitch padding cut off"""
+        return (self.y[:, :, :ops.yuv_packed_words(self.fmt, self.shape[2])],)
+
+    def kernel_views(self, planes):
+        return tuple(planes)
+
+    def to_rgb(self, planes, out):
+        """ONE tdc_yuv_packed_to_rgb launch: the frames of `planes` (the device surface laid out like planes()) -> out uint8
+        [T, H, W, 3]; transfer "pq" / "hlg" passes the descriptor, its table taken from (and made once for) the surface's device"""
+        H, W = self.shape[1:3]
+        hdr = None
+        if self.hdr is not None:
+            hdr = dict(self.hdr, lut=hdr_lut(self.transfer, self.bits, self.peak_nits, self.sdr_white, planes[0].device))
+        return ops.yuv_packed_to_rgb(planes[0], self.fmt, self.coef, H, W, self.bits, self.msb_aligned, hdr=hdr, out=out)
 
 
 def is_yuv_frames(x):
@@ -458,7 +612,7 @@ def selected_planes(yuv, idx, device):
 
 def _preprocess_selected_yuv(yuv, idx, towers, dtype, slab, device, out, stats):
     """preprocess_selected for a YuvFrames: per slab of kept frames ONE conversion launch (YuvFrames.to_rgb: tdc_yuv420_to_rgb
-    for 8-bit 4:2:0, tdc_yuv_to_rgb for every other kind) into a [slab, H, W, 3] RGB scratch, then tdc_preprocess_frames per tower on that scratch - the RGB path's launches on the frames the planes convert
+    for 8-bit 4:2:0, tdc_yuv_to_rgb for every other planar kind, tdc_yuv_packed_to_rgb for a packed surface) into a [slab, H, W, 3] RGB scratch, then tdc_preprocess_frames per tower on that scratch - the RGB path's launches on the frames the planes convert
     to.  Both scratches are slab-sized and serve the whole video."""
     idx = check_indices(idx, yuv.shape[0])
     _check_dtype_slab(dtype, slab)
