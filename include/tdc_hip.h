@@ -677,6 +677,42 @@ typedef struct {
 int tdc_yuv_packed_to_rgb(const tdc_yuv_packed* p, const tdc_yuv_coef* c, const tdc_hdr_desc* h /* NULL: SDR */,
                           int T, int H, int W, unsigned char* rgb /* [T, H, W, 3] contiguous */, void* stream);
 
+/* ---- YUV 4:2:0 / 4:2:2 -> RGB with interpolated chroma, sited ---------------------------------------
+ * The entries above rebuild full-resolution chroma by replication.  These two interpolate it linearly per axis, on the chroma
+ * SAMPLES, at the samples' depth and before anything else; the per-pixel formula of tdc_yuv_to_rgb (h == NULL) or stage A and
+ * B of tdc_yuv_hdr_to_rgb (h != NULL, bits 10 or 12) then runs unchanged on the result.  The project's own stated formula,
+ * not claimed equal to any library's scaler.
+ * Per axis that is sub-sampled by 2, position p has k = p >> 1 and n chroma samples on that axis (Wc = (W + 1) >> 1 across,
+ * Hc = (H + 1) >> 1 down); it takes two taps with weights in quarters, the indices clamped to [0, n - 1]:
+ *     siting of the axis                                              even p                    odd p
+ *     0 co-sited: sample k sits on luma 2k                            4 C[k]                    2 C[k] + 2 C[min(k+1, n-1)]
+ *     1 centred:  sample k sits midway between luma 2k and 2k + 1     3 C[k] + C[max(k-1, 0)]   3 C[k] + C[min(k+1, n-1)]
+ * An axis that is not sub-sampled (the rows of 4:2:2) has weight 4 on its own sample and its siting is ignored.  The 2-D
+ * weight is the product of the two axes' weights - four taps, in sixteenths, summing to 16 - and the sum is rounded once:
+ *     C'(y, x) = (sum w_ij * C_ij + 8) >> 4        in int32, for U and V alike
+ * C' takes the place of the replicated sample: the bytes are exactly those the replicate entries write for 4:4:4 planes
+ * holding C'.  (sit_x, sit_y) of ffmpeg's / H.273's chroma_sample_loc_type: left (0, 1) - MPEG-2, H.264, HEVC 4:2:0; center
+ * (1, 1) - JPEG, MPEG-1; topleft (0, 0) - BT.2020 UHD; top (1, 0).  4:2:2 from SDI is sit_x = 0.
+ * tdc_yuv_linear_to_rgb takes every tdc_yuv_planes the planar entries take at 4:2:0 or 4:2:2, 8-bit 4:2:0 included;
+ * tdc_yuv_packed_linear_to_rgb takes the 4:2:2 formats YUYV, YVYU, UYVY, VYUY, Y210 and V210.  Thread ownership, the forms and
+ * the alignment facts that choose between them are those of the replicate entry of the same surface; all forms give the same
+ * bytes.  A thread loads its own run of chroma samples in every chroma row it needs as the replicate kernel does, and the
+ * one sample left (centred) and right of the run as single-sample loads.
+ * TDC_E_BADARG before any launch: a null s; sit_x or sit_y not 0 or 1; a 4:4:4 surface (sub_x = 0; VUYA, AYUV, Y410, Y416);
+ * everything the replicate entry of the same surface refuses - tdc_yuv_to_rgb, tdc_yuv_packed_to_rgb - and, with h,
+ * bits = 8 and everything tdc_yuv_hdr_to_rgb refuses about the descriptor.
+ * writes: rgb [T, H, W, 3] and nothing else.  reads: EXACTLY the read set of the replicate entry of the same surface (plus,
+ * with h, the 2^bits floats at h->lut): every neighbour is clamped by index on the picture's own Wc and Hc.  never read: pitch
+ * padding, the bytes between a plane's or frame's end and the next frame, a neighbour from frame t - 1 or t + 1.  read, but
+ * changing nothing: the bits of a word outside the sample, the unused tail of a packed row's last group. */
+typedef struct { int sit_x, sit_y; } tdc_chroma_site;    /* 0 co-sited, 1 centred; host struct, passed by value into the kernel */
+int tdc_yuv_linear_to_rgb(const tdc_yuv_planes* p, const tdc_yuv_coef* c, const tdc_hdr_desc* h /* NULL: SDR */,
+                          const tdc_chroma_site* s, int T, int H, int W, unsigned char* rgb /* [T, H, W, 3] contiguous */,
+                          void* stream);
+int tdc_yuv_packed_linear_to_rgb(const tdc_yuv_packed* p, const tdc_yuv_coef* c, const tdc_hdr_desc* h /* NULL: SDR */,
+                                 const tdc_chroma_site* s, int T, int H, int W, unsigned char* rgb /* [T, H, W, 3] contiguous */,
+                                 void* stream);
+
 /* ---- display orientation of decoded RGB frames -------------------------------------------------
  * A decoder writes the coded picture; the orientation travels beside it (the display matrix or `rotate` tag of MP4 / MOV,
  * the EXIF orientation of a still).  src uint8 [T, H, W, 3] contiguous, the stored frames S -> dst uint8 [T, H', W', 3]

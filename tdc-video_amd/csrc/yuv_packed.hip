@@ -9,6 +9,9 @@
 //             a multiple of 8 but not of 24 ends in one or two units of one group (one 16-byte load, byte stores)
 // chosen on the host from alignment facts alone.  Bits outside a sample are masked off before anything else sees them; every
 // form gives the same bytes.
+// The linear kernels at the end (tdc_yuv_packed_linear_to_rgb) are the 4:2:2 families with interpolated
+// chroma: same units, same loads and stores, plus the chroma pair left (centred siting) and right of the unit's run.
+#include "yuv_linear.h"
 #include "yuv_pixels.h"
 
 namespace {
@@ -258,6 +261,163 @@ inline packed_launch packed_launch_of(const tdc_yuv_packed* p, int family, int T
     return {vec ? VEC : GROUP, units_x, units_vec, dim3(gx, gy)};
 }
 
+// ---- interpolated chroma: the 4:2:2 families ------------------------------------------------------
+// chroma pair k of a row, as single-sample loads (v210: the words that hold it; R = k % 3, its place in the group)
+template <int FAM, int R>
+__device__ __forceinline__ void pair_at(const unsigned char* srow, int k, const packed_lay& l, const depth& d, int& u, int& v) {
+    if constexpr (FAM == F422_8) {
+        const unsigned char* g = srow + 4ll * k;
+        u = (int)g[l.u]; v = (int)g[l.v];
+    } else if constexpr (FAM == F422_16) {
+        const unsigned char* g = srow + 8ll * k;
+        u = sample_at<2>(g + 2 * l.u, d); v = sample_at<2>(g + 2 * l.v, d);
+    } else {
+        const unsigned* g = reinterpret_cast<const unsigned*>(srow) + 4ll * (k / 3);
+        if constexpr (R == 0) { const unsigned w = g[0]; u = (int)(w & 1023u); v = (int)(w >> 20 & 1023u); }
+        else { u = (int)(g[2] >> 20 & 1023u); v = (int)(g[3] >> 10 & 1023u); }
+    }
+}
+
+// packed_unit with interpolated chroma: the unit's NG groups hold the pairs k0 .. k0 + NG * NC - 1 of the row at srow.  A
+// pair at or past Wc (the unused tail of the row's last group) is never used: the clamp is by index on the picture's Wc.
+template <int FAM, int NG, bool WIDE, class PX>
+__device__ __forceinline__ void packed_linear_unit(const unsigned char* srow, const unsigned char* src, unsigned char* orow, int x0,
+                                                   int W, const packed_lay& l, const tdc_yuv_coef& c, const depth& d, const PX& px,
+                                                   const axis_taps& wx) {
+    constexpr int P = fam_px(FAM), GW = fam_gw(FAM), NC = fam_nc(FAM);
+    constexpr int NPIX = NG * P, NCU = NG * NC;
+    static_assert(NPIX == 2 * NCU, "4:2:2: a chroma pair per two pixels");
+    constexpr bool PACK = NPIX % 8 == 0;
+    constexpr int CH = PACK ? 8 : NPIX;
+    unsigned all[NG * GW];
+    if constexpr (WIDE) {
+        load_words<NG * GW * 4>(src, all);
+    } else {
+        static_assert(NG == 1, "sample-sized loads take one group");
+        load_group<FAM>(src, all);
+    }
+    int ys[NPIX], su[NCU + 2], sv[NCU + 2];
+#pragma unroll
+    for (int gi = 0; gi < NG; ++gi) {
+        unsigned w[GW];
+#pragma unroll
+        for (int k = 0; k < GW; ++k) w[k] = all[gi * GW + k];
+        int y[P], u[NC], v[NC];
+        group_samples<FAM>(w, l, d, y, u, v);
+#pragma unroll
+        for (int j = 0; j < P; ++j) ys[gi * P + j] = y[j];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) { su[1 + gi * NC + k] = u[k]; sv[1 + gi * NC + k] = v[k]; }
+    }
+    const int k0 = x0 >> 1, Wc = (W + 1) >> 1;      // k0 < Wc: a unit starts below W
+    su[0] = su[1]; sv[0] = sv[1];
+    if (wx.eb && k0 > 0) pair_at<FAM, 2>(srow, k0 - 1, l, d, su[0], sv[0]);         // only the centred siting looks left
+#pragma unroll
+    for (int k = 1; k < NCU; ++k)                   // the tail of the row's last group takes the last live pair
+        if (k0 + k >= Wc) { su[1 + k] = su[k]; sv[1 + k] = sv[k]; }
+    su[NCU + 1] = su[NCU]; sv[NCU + 1] = sv[NCU];
+    if (k0 + NCU < Wc) pair_at<FAM, 0>(srow, k0 + NCU, l, d, su[NCU + 1], sv[NCU + 1]);
+    int hu[NPIX], hv[NPIX];
+    horizontal_sums<NCU>(su, wx, hu);
+    horizontal_sums<NCU>(sv, wx, hv);
+    unsigned r[NPIX / CH][CH], g[NPIX / CH][CH], b[NPIX / CH][CH];
+#pragma unroll
+    for (int q = 0; q < NPIX; ++q) {
+        const int yy = c.cy * (ys[q] - c.y_off);
+        const chroma_terms k = chroma(c, d, interpolated(4, hu[q], 0, 0), interpolated(4, hv[q], 0, 0));
+        px(d, yy + k.r, yy + k.g, yy + k.b, r[q / CH][q % CH], g[q / CH][q % CH], b[q / CH][q % CH]);
+    }
+    if constexpr (PACK) {
+        uint2* dst = reinterpret_cast<uint2*>(orow + (long long)x0 * 3);
+#pragma unroll
+        for (int k = 0; k < NPIX / 8; ++k) {
+            uint2 o[3];
+            pack_row8(r[k], g[k], b[k], o);
+            dst[3 * k] = o[0]; dst[3 * k + 1] = o[1]; dst[3 * k + 2] = o[2];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < NPIX; ++j) {
+            if (x0 + j < W) {       // the unused tail of a row's last group
+                unsigned char* o = orow + (long long)(x0 + j) * 3;
+                o[0] = (unsigned char)r[0][j]; o[1] = (unsigned char)g[0][j]; o[2] = (unsigned char)b[0][j];
+            }
+        }
+    }
+}
+
+// packed_frames with interpolated chroma: the same grid, units and order of units
+template <int FAM, int FORM, class PX>
+__device__ __forceinline__ void packed_linear_frames(const tdc_yuv_packed& p, const packed_lay& l, const tdc_yuv_coef& c, const depth& d,
+                                                     const PX& px, const tdc_chroma_site& s, int T, int H, int W, int units_x,
+                                                     int units_vec, unsigned char* rgb) {
+    constexpr int P = fam_px(FAM), GB = fam_gw(FAM) * 4;
+    constexpr int NG = FAM == FV210 ? 4 : 8 / P;          // groups per vector unit
+    const axis_taps wx = axis_taps_of(s.sit_x, 1);
+    const long long units = (long long)units_x * H;       // < 2^32: units_x and H are at most 65535
+    for (int t = blockIdx.y; t < T; t += gridDim.y) {
+        const unsigned char* sf = p.base + (long long)t * p.frame;
+        unsigned char* of = rgb + (long long)t * H * W * 3;
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < units; i += (long long)gridDim.x * 256) {
+            const bool tail = FAM == FV210 && FORM == VEC && i >= (long long)units_vec * H;
+            const unsigned per_row = FAM == FV210 && FORM == VEC ? (unsigned)(tail ? units_x - units_vec : units_vec) : (unsigned)units_x;
+            const unsigned j = (unsigned)(tail ? i - (long long)units_vec * H : i);     // i < 2^32: 32-bit divisions
+            const unsigned row_ = j / per_row;
+            const int row = (int)row_, xu = (int)(j - row_ * per_row);
+            const unsigned char* srow = sf + (long long)row * p.pitch;
+            unsigned char* orow = of + (long long)row * W * 3;
+            if constexpr (FORM == GROUP) {
+                packed_linear_unit<FAM, 1, false>(srow, srow + (long long)xu * GB, orow, xu * P, W, l, c, d, px, wx);
+            } else if constexpr (FAM == FV210) {
+                if (!tail) {
+                    packed_linear_unit<FAM, NG, true>(srow, srow + (long long)xu * (NG * GB), orow, xu * (NG * P), W, l, c, d, px, wx);
+                } else {
+                    const int gi = units_vec * NG + xu;
+                    packed_linear_unit<FAM, 1, true>(srow, srow + (long long)gi * GB, orow, gi * P, W, l, c, d, px, wx);
+                }
+            } else {
+                packed_linear_unit<FAM, NG, true>(srow, srow + (long long)xu * (NG * GB), orow, xu * (NG * P), W, l, c, d, px, wx);
+            }
+        }
+    }
+}
+
+template <int FAM, int FORM>
+__global__ __launch_bounds__(256) void yuv_packed_linear_to_rgb_kernel(tdc_yuv_packed p, packed_lay l, tdc_yuv_coef c, tdc_chroma_site s,
+                                                                       int T, int H, int W, int units_x, int units_vec, unsigned char* rgb) {
+    packed_linear_frames<FAM, FORM>(p, l, c, depth_of(p.bits, p.msb_aligned, 8), sdr_pixel(), s, T, H, W, units_x, units_vec, rgb);
+}
+
+template <int FAM, int FORM>
+__global__ __launch_bounds__(256) void yuv_packed_linear_hdr_to_rgb_kernel(tdc_yuv_packed p, packed_lay l, tdc_yuv_coef c, tdc_hdr_desc h,
+                                                                           tdc_chroma_site s, int T, int H, int W, int units_x,
+                                                                           int units_vec, unsigned char* rgb) {
+    extern __shared__ float lut[];      // 2^bits entries
+    stage_hdr_lut(lut, h, p.bits);
+    packed_linear_frames<FAM, FORM>(p, l, c, depth_of(p.bits, p.msb_aligned, p.bits), hdr_pixel{h, lut}, s, T, H, W, units_x, units_vec, rgb);
+}
+
+template <int FAM, int FORM>
+void launch_linear_form(const packed_launch& q, hipStream_t st, const tdc_yuv_packed& p, const packed_lay& l, const tdc_yuv_coef& c,
+                        const tdc_hdr_desc* h, const tdc_chroma_site& s, int T, int H, int W, unsigned char* rgb) {
+    const dim3 block(256);
+    if constexpr (FAM != F422_8) {
+        if (h) {
+            hipLaunchKernelGGL((yuv_packed_linear_hdr_to_rgb_kernel<FAM, FORM>), q.grid, block, sizeof(float) << p.bits, st, p, l, c, *h, s,
+                               T, H, W, q.units_x, q.units_vec, rgb);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((yuv_packed_linear_to_rgb_kernel<FAM, FORM>), q.grid, block, 0, st, p, l, c, s, T, H, W, q.units_x, q.units_vec, rgb);
+}
+
+template <int FAM>
+void launch_linear(const packed_launch& q, hipStream_t st, const tdc_yuv_packed& p, const packed_lay& l, const tdc_yuv_coef& c,
+                   const tdc_hdr_desc* h, const tdc_chroma_site& s, int T, int H, int W, unsigned char* rgb) {
+    if (q.form == VEC) return launch_linear_form<FAM, VEC>(q, st, p, l, c, h, s, T, H, W, rgb);
+    launch_linear_form<FAM, GROUP>(q, st, p, l, c, h, s, T, H, W, rgb);
+}
+
 }  // namespace
 
 extern "C" int tdc_yuv_packed_to_rgb(const tdc_yuv_packed* p, const tdc_yuv_coef* c, const tdc_hdr_desc* h, int T, int H, int W,
@@ -273,6 +433,21 @@ extern "C" int tdc_yuv_packed_to_rgb(const tdc_yuv_packed* p, const tdc_yuv_coef
         case F444_16: launch<F444_16>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
         case F410: launch<F410>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
         default: launch<FV210>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int tdc_yuv_packed_linear_to_rgb(const tdc_yuv_packed* p, const tdc_yuv_coef* c, const tdc_hdr_desc* h, const tdc_chroma_site* s,
+                                            int T, int H, int W, unsigned char* rgb, void* stream) {
+    packed_fmt f;
+    if (!chroma_site_ok(s) || !packed_args_ok(p, c, h, T, H, W, rgb, f)) return TDC_E_BADARG;
+    if (f.family != F422_8 && f.family != F422_16 && f.family != FV210) return TDC_E_BADARG;      // 4:4:4: nothing to interpolate
+    const packed_launch q = packed_launch_of(p, f.family, T, H, W, rgb);
+    hipStream_t st = (hipStream_t)stream;
+    switch (f.family) {
+        case F422_8: launch_linear<F422_8>(q, st, *p, f.lay, *c, h, *s, T, H, W, rgb); break;
+        case F422_16: launch_linear<F422_16>(q, st, *p, f.lay, *c, h, *s, T, H, W, rgb); break;
+        default: launch_linear<FV210>(q, st, *p, f.lay, *c, h, *s, T, H, W, rgb); break;
     }
     return (int)hipGetLastError();
 }

@@ -168,6 +168,10 @@ class YuvPacked(C.Structure):
                 ("msb_aligned", C.c_int)]
 
 
+class ChromaSite(C.Structure):
+    _fields_ = [("sit_x", C.c_int), ("sit_y", C.c_int)]
+
+
 # TDC_YUVP_* of include/tdc_hip.h
 YUV_PACKED_FORMATS = {"yuyv": 0, "yvyu": 1, "uyvy": 2, "vyuy": 3, "y210": 4, "vuya": 5, "ayuv": 6, "y410": 7, "y416": 8, "v210": 9}
 
@@ -243,6 +247,10 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p]),
     "tdc_yuv_packed_to_rgb": (C.c_int, [C.POINTER(YuvPacked), C.POINTER(YuvCoef), C.POINTER(HdrDesc), C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p]),
+    "tdc_yuv_linear_to_rgb": (C.c_int, [C.POINTER(YuvPlanes), C.POINTER(YuvCoef), C.POINTER(HdrDesc), C.POINTER(ChromaSite), C.c_int,
+                                        C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "tdc_yuv_packed_linear_to_rgb": (C.c_int, [C.POINTER(YuvPacked), C.POINTER(YuvCoef), C.POINTER(HdrDesc), C.POINTER(ChromaSite),
+                                               C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdc_orient_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdc_pack_rgb": (C.c_int, [C.POINTER(RgbSource), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdc_fbank_frames": (C.c_int, [C.c_longlong]),

@@ -802,6 +802,36 @@ def yuv_hdr_to_rgb(y, u, v, c_step, coef, H, W, bits, msb_aligned, subsampling, 
     return out
 
 
+def _hdr_desc(hdr, bits, device):
+    """the mapping yuv_hdr_to_rgb takes -> its tdc_hdr_desc"""
+    lut = hdr["lut"]
+    assert lut.is_cuda and lut.dtype == torch.float32 and lut.dim() == 1 and lut.numel() == 1 << bits and lut.is_contiguous() \
+        and lut.device == device, "hdr['lut'] must be float32 [2^bits] on the planes' device"
+    assert len(hdr["luma"]) == 3 and len(hdr["gamut"]) == 9
+    return L.HdrDesc(lut.data_ptr(), hdr["ootf_scale"], hdr["ootf_exp"], (C.c_float * 3)(*hdr["luma"]), hdr["inv_p2"],
+                     (C.c_float * 9)(*hdr["gamut"]))
+
+
+def _chroma_site(site):
+    assert len(site) == 2 and all(s in (0, 1) and not isinstance(s, bool) for s in site), \
+        "site must be (sit_x, sit_y), each 0 (co-sited) or 1 (centred), got %r" % (site,)
+    return L.ChromaSite(*site)
+
+
+def yuv_linear_to_rgb(y, u, v, c_step, coef, H, W, bits, msb_aligned, subsampling, site, hdr=None, out=None):
+    """T frames of 4:2:0 / 4:2:2 YUV -> rgb uint8 [T, H, W, 3] with interpolated chroma (tdc_yuv_linear_to_rgb; DESIGN.md section
+    26).  The views are yuv_to_rgb's, 8-bit 4:2:0 included.  site = (sit_x, sit_y): where the chroma samples sit on each axis,
+    0 co-sited with the even luma sample, 1 centred between two (preprocess.CHROMA_SITES).  hdr None: coef as yuv_to_rgb takes
+    it; with hdr (bits 10 or 12: the mapping yuv_hdr_to_rgb takes) as yuv_hdr_to_rgb takes it."""
+    assert subsampling in ("420", "422"), "interpolated chroma is for subsampling 420 and 422, got %r" % (subsampling,)
+    s = _chroma_site(site)
+    p, out = _yuv_planes(y, u, v, c_step, H, W, bits, msb_aligned, subsampling, out)
+    h = None if hdr is None else C.byref(_hdr_desc(hdr, bits, y.device))
+    L.check(L.load().tdc_yuv_linear_to_rgb(C.byref(p), C.byref(L.YuvCoef(*coef)), h, C.byref(s), y.shape[0], H, W, _ptr(out), _stream()),
+            "tdc_yuv_linear_to_rgb")
+    return out
+
+
 # packed YUV (DESIGN.md section 25): name -> (bytes per word of the surface, words per group, pixels per group, bits taken)
 YUV_PACKED = {"yuyv": (1, 4, 2, (8,)), "yvyu": (1, 4, 2, (8,)), "uyvy": (1, 4, 2, (8,)), "vyuy": (1, 4, 2, (8,)),
               "y210": (2, 4, 2, (10, 12)), "vuya": (1, 4, 1, (8,)), "ayuv": (1, 4, 1, (8,)), "y410": (4, 1, 1, (10,)),
@@ -820,6 +850,15 @@ def yuv_packed_to_rgb(surface, fmt, coef, H, W, bits, msb_aligned, hdr=None, out
     frame stride: uint8 for the byte formats (yuyv, yvyu, uyvy, vyuy, vuya, ayuv), 16-bit words (torch.int16 as a bit pattern, or
     torch.uint16) for y210 / y416, 32-bit words (torch.int32 as a bit pattern, or torch.uint32) for y410 / v210.  coef as
     yuv_to_rgb takes it; with hdr (bits 10 or 12: the mapping yuv_hdr_to_rgb takes) as yuv_hdr_to_rgb takes it."""
+    p, h, T, out = _yuv_packed(surface, fmt, H, W, bits, msb_aligned, hdr, out)
+    L.check(L.load().tdc_yuv_packed_to_rgb(C.byref(p), C.byref(L.YuvCoef(*coef)), h, T, H, W, _ptr(out), _stream()),
+            "tdc_yuv_packed_to_rgb")
+    return out
+
+
+def _yuv_packed(surface, fmt, H, W, bits, msb_aligned, hdr, out):
+    """the checked surface of yuv_packed_to_rgb / yuv_packed_linear_to_rgb -> (its tdc_yuv_packed, the descriptor by reference or
+    None, T, out allocated when None)"""
     assert fmt in YUV_PACKED, "fmt must be one of %s" % sorted(YUV_PACKED)
     ws, _, _, depths = YUV_PACKED[fmt]
     assert bits in depths, "fmt %s takes bits %s, got %r" % (fmt, depths, bits)
@@ -844,8 +883,18 @@ def yuv_packed_to_rgb(surface, fmt, coef, H, W, bits, msb_aligned, hdr=None, out
         assert len(hdr["luma"]) == 3 and len(hdr["gamut"]) == 9
         h = C.byref(L.HdrDesc(lut.data_ptr(), hdr["ootf_scale"], hdr["ootf_exp"], (C.c_float * 3)(*hdr["luma"]), hdr["inv_p2"],
                               (C.c_float * 9)(*hdr["gamut"])))
-    L.check(L.load().tdc_yuv_packed_to_rgb(C.byref(p), C.byref(L.YuvCoef(*coef)), h, T, H, W, _ptr(out), _stream()),
-            "tdc_yuv_packed_to_rgb")
+    return p, h, T, out
+
+
+def yuv_packed_linear_to_rgb(surface, fmt, coef, H, W, bits, msb_aligned, site, hdr=None, out=None):
+    """T frames of packed 4:2:2 YUV (yuyv, yvyu, uyvy, vyuy, y210, v210) -> rgb uint8 [T, H, W, 3] with interpolated chroma
+    (tdc_yuv_packed_linear_to_rgb).  The surface, coef and hdr are yuv_packed_to_rgb's; site = (sit_x,
+    sit_y) as yuv_linear_to_rgb takes it (only sit_x matters: the rows are not sub-sampled)."""
+    assert fmt in YUV_PACKED and YUV_PACKED[fmt][2] != 1, "interpolated chroma is for the 4:2:2 formats, got %r" % (fmt,)
+    s = _chroma_site(site)
+    p, h, T, out = _yuv_packed(surface, fmt, H, W, bits, msb_aligned, hdr, out)
+    L.check(L.load().tdc_yuv_packed_linear_to_rgb(C.byref(p), C.byref(L.YuvCoef(*coef)), h, C.byref(s), T, H, W, _ptr(out), _stream()),
+            "tdc_yuv_packed_linear_to_rgb")
     return out
 
 

@@ -273,6 +273,19 @@ def _plane(p, name, bits=8):
     return p
 
 
+# interpolated chroma: ffmpeg's / H.273's chroma_sample_loc_type -> (sit_x, sit_y), 0 co-sited, 1 centred
+CHROMA_UPSAMPLE = ("replicate", "linear")
+CHROMA_SITES = {"left": (0, 1), "center": (1, 1), "topleft": (0, 0), "top": (1, 0)}
+
+
+def _check_chroma(upsample, siting):
+    if upsample not in CHROMA_UPSAMPLE:
+        raise ValueError("upsample must be one of %s, got %r" % (CHROMA_UPSAMPLE, upsample))
+    if siting not in CHROMA_SITES:
+        raise ValueError("siting must be one of %s, got %r" % (sorted(CHROMA_SITES), siting))
+    return upsample, siting
+
+
 class YuvFrames:
     """T0 frames of YUV of one size, described and not copied: what a decoder hands over before any colour conversion.
     y is [T0, H, >= W]; the chroma planes have Hc = (H + 1) // 2 rows of Wc = (W + 1) // 2 samples -
@@ -292,10 +305,15 @@ class YuvFrames:
     P012, P016) or their low bits (yuv420p10le and its kin); whatever the other bits hold is ignored.  subsampling "422":
     Hc = H, "444": Hc = H and Wc = W.  bt2020 is taken at 10 and 12 bits, the depths it is defined for.
     Packed surfaces - luma and chroma in one row: YUY2, UYVY, Y210, AYUV, Y410, Y416, v210 - are built by
-    YuvFrames.packed and its named forms and are PackedYuvFrames, which every consumer of a YuvFrames takes."""
+    YuvFrames.packed and its named forms and are PackedYuvFrames, which every consumer of a YuvFrames takes.
+    upsample "replicate" (the default) gives pixel (y, x) the chroma sample (y >> sub_y, x >> sub_x); "linear" interpolates the
+    chroma samples per axis by where they sit: siting "left" (MPEG-2 / H.264 / HEVC 4:2:0, the default),
+    "center" (JPEG, MPEG-1), "topleft" (BT.2020 UHD / HDR10) or "top"; for 4:2:2 only the horizontal half of it matters, and
+    on a 4:4:4 surface there is nothing to interpolate.  The siting describes the stored picture and is ignored by "replicate"."""
 
     def __init__(self, y, chroma, c_step, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False,
-                 subsampling="420", transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
+                 subsampling="420", transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
+        self.upsample, self.siting = _check_chroma(upsample, siting)
         if c_step not in (1, 2):
             raise ValueError("c_step is 1 (planar u, v) or 2 (interleaved uv), got %r" % (c_step,))
         names = ("uv",) if c_step == 2 else ("u", "v")
@@ -346,67 +364,67 @@ class YuvFrames:
 
     @classmethod
     def nv12(cls, y, uv, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False, subsampling="420",
-             transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
+             transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """a luma plane and one plane of interleaved (u, v) samples: NV12, and NV16 / NV24 with subsampling "422" / "444" """
-        return cls(y, (uv,), 2, width, matrix, full_range, bits, msb_aligned, subsampling, transfer, peak_nits, sdr_white, primaries)
+        return cls(y, (uv,), 2, width, matrix, full_range, bits, msb_aligned, subsampling, transfer, peak_nits, sdr_white, primaries, upsample, siting)
 
     @classmethod
     def i420(cls, y, u, v, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False, subsampling="420",
-             transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
+             transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """three planes: yuv420p, yuv422p, yuv444p and - bits 10 / 12 - their 10le / 12le forms"""
-        return cls(y, (u, v), 1, width, matrix, full_range, bits, msb_aligned, subsampling, transfer, peak_nits, sdr_white, primaries)
+        return cls(y, (u, v), 1, width, matrix, full_range, bits, msb_aligned, subsampling, transfer, peak_nits, sdr_white, primaries, upsample, siting)
 
     @classmethod
     def p010(cls, y, uv, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0,
-             primaries=None):
+             primaries=None, upsample="replicate", siting="left"):
         """P010 as a hardware decoder writes it: 4:2:0, 16-bit words, the 10-bit sample in the high bits"""
-        return cls(y, (uv,), 2, width, matrix, full_range, 10, True, "420", transfer, peak_nits, sdr_white, primaries)
+        return cls(y, (uv,), 2, width, matrix, full_range, 10, True, "420", transfer, peak_nits, sdr_white, primaries, upsample, siting)
 
     @classmethod
     def p016(cls, y, uv, bits, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0,
-             primaries=None):
+             primaries=None, upsample="replicate", siting="left"):
         """a P016 surface holding `bits` (10 or 12) significant bits, MSB-aligned; the low bits are ignored"""
         if isinstance(bits, bool) or bits not in (10, 12):
             raise ValueError("bits of a P016 surface must be 10 or 12, got %r" % (bits,))
-        return cls(y, (uv,), 2, width, matrix, full_range, bits, True, "420", transfer, peak_nits, sdr_white, primaries)
+        return cls(y, (uv,), 2, width, matrix, full_range, bits, True, "420", transfer, peak_nits, sdr_white, primaries, upsample, siting)
 
     @classmethod
     def packed(cls, data, fmt, width=None, matrix="bt601", full_range=False, bits=None, msb_aligned=None, transfer="sdr",
-               peak_nits=1000.0, sdr_white=203.0, primaries=None):
+               peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """a packed surface, luma and chroma in one row: a PackedYuvFrames, which every consumer of a
         YuvFrames takes.  fmt: one of YUV_PACKED_NAMES."""
-        return PackedYuvFrames(data, fmt, width, matrix, full_range, bits, msb_aligned, transfer, peak_nits, sdr_white, primaries)
+        return PackedYuvFrames(data, fmt, width, matrix, full_range, bits, msb_aligned, transfer, peak_nits, sdr_white, primaries, upsample, siting)
 
     @classmethod
-    def yuy2(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
+    def yuy2(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """YUY2 / YUYV / ffmpeg yuyv422: bytes Y0 U Y1 V"""
-        return cls.packed(data, "yuyv", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries)
+        return cls.packed(data, "yuyv", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries, upsample, siting)
 
     @classmethod
-    def uyvy(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
+    def uyvy(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """UYVY / ffmpeg uyvy422: bytes U Y0 V Y1"""
-        return cls.packed(data, "uyvy", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries)
+        return cls.packed(data, "uyvy", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries, upsample, siting)
 
     @classmethod
     def y210(cls, data, width=None, matrix="bt601", full_range=False, bits=10, msb_aligned=True, transfer="sdr", peak_nits=1000.0,
-             sdr_white=203.0, primaries=None):
+             sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """Y210 / Y212 / a Y216 container (ffmpeg y210le, y212le): 16-bit words Y0 U Y1 V holding `bits` (10 or 12) bits"""
-        return cls.packed(data, "y210", width, matrix, full_range, bits, msb_aligned, transfer, peak_nits, sdr_white, primaries)
+        return cls.packed(data, "y210", width, matrix, full_range, bits, msb_aligned, transfer, peak_nits, sdr_white, primaries, upsample, siting)
 
     @classmethod
-    def ayuv(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
+    def ayuv(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """Microsoft AYUV / VUYX / ffmpeg vuya, vuyx: bytes V U Y A (ffmpeg's `ayuv`, bytes A Y U V, is packed(data, "ayuv"))"""
-        return cls.packed(data, "vuya", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries)
+        return cls.packed(data, "vuya", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries, upsample, siting)
 
     @classmethod
-    def y410(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
+    def y410(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """Y410 / ffmpeg xv30le: one 32-bit word per pixel, U = bits 0-9, Y = 10-19, V = 20-29"""
-        return cls.packed(data, "y410", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries)
+        return cls.packed(data, "y410", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries, upsample, siting)
 
     @classmethod
-    def v210(cls, data, width, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None):
+    def v210(cls, data, width, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """v210: six pixels in four 32-bit words; `width` is required (a row holds whole blocks, often padded to 128 bytes)"""
-        return cls.packed(data, "v210", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries)
+        return cls.packed(data, "v210", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries, upsample, siting)
 
     @property
     def sample_size(self):
@@ -422,11 +440,16 @@ class YuvFrames:
     def is_cuda(self):
         return self.y.is_cuda
 
+    @property
+    def interpolates(self):
+        """upsample "linear" on a surface whose chroma is sub-sampled: on 4:4:4 there is nothing to interpolate"""
+        return self.upsample == "linear" and self.sub_x == 1
+
     def __getitem__(self, s):
         if not isinstance(s, slice) or s.step not in (None, 1):
             raise TypeError("YuvFrames takes a slice of frames a:b, got %r" % (s,))
         return YuvFrames(self.y[s], tuple(c[s] for c in self.chroma), self.c_step, self.shape[2], self.matrix, self.full_range,
-                         self.bits, self.msb_aligned, self.subsampling, self.transfer, self.peak_nits, self.sdr_white, self.primaries)
+                         self.bits, self.msb_aligned, self.subsampling, self.transfer, self.peak_nits, self.sdr_white, self.primaries, self.upsample, self.siting)
 
     def planes(self):
         """the read set as views: (y [T0, H, W], one or two chroma planes [T0, Hc, c_step * Wc]) - the pitch padding cut off"""
@@ -440,9 +463,14 @@ class YuvFrames:
     def to_rgb(self, planes, out):
         """ONE conversion launch: the frames of `planes` (device planes laid out like planes()) -> out uint8 [T, H, W, 3].
         8-bit 4:2:0 issues tdc_yuv420_to_rgb as it always did; every other SDR kind issues tdc_yuv_to_rgb; transfer "pq" / "hlg"
-        issues tdc_yuv_hdr_to_rgb, its table taken from (and made once for) the planes' device."""
+        issues tdc_yuv_hdr_to_rgb, its table taken from (and made once for) the planes' device.  upsample "linear" on a 4:2:0 or
+        4:2:2 surface issues tdc_yuv_linear_to_rgb in their place."""
         y, u, v = self.kernel_views(planes)
         H, W = self.shape[1:3]
+        if self.interpolates:
+            hdr = self.hdr and dict(self.hdr, lut=hdr_lut(self.transfer, self.bits, self.peak_nits, self.sdr_white, y.device))
+            return ops.yuv_linear_to_rgb(y, u, v, self.c_step, self.coef, H, W, self.bits, self.msb_aligned, self.subsampling,
+                                         CHROMA_SITES[self.siting], hdr=hdr, out=out)
         if self.hdr is not None:
             hdr = dict(self.hdr, lut=hdr_lut(self.transfer, self.bits, self.peak_nits, self.sdr_white, y.device))
             return ops.yuv_hdr_to_rgb(y, u, v, self.c_step, self.coef, H, W, self.bits, self.msb_aligned, self.subsampling, hdr, out=out)
@@ -493,7 +521,8 @@ class PackedYuvFrames(YuvFrames):
     the surface, planes() one view of it cut to the read set, to_rgb ONE tdc_yuv_packed_to_rgb launch."""
 
     def __init__(self, data, fmt, width=None, matrix="bt601", full_range=False, bits=None, msb_aligned=None, transfer="sdr",
-                 peak_nits=1000.0, sdr_white=203.0, primaries=None):
+                 peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
+        self.upsample, self.siting = _check_chroma(upsample, siting)
         if fmt not in YUV_PACKED_NAMES:
             raise ValueError("fmt must be one of %s, got %r" % (sorted(YUV_PACKED_NAMES), fmt))
         self.name = fmt
@@ -546,7 +575,7 @@ class PackedYuvFrames(YuvFrames):
         if not isinstance(s, slice) or s.step not in (None, 1):
             raise TypeError("YuvFrames takes a slice of frames a:b, got %r" % (s,))
         return PackedYuvFrames(self.y[s], self.name, self.shape[2], self.matrix, self.full_range, self.bits, self.msb_aligned,
-                               self.transfer, self.peak_nits, self.sdr_white, self.primaries)
+                               self.transfer, self.peak_nits, self.sdr_white, self.primaries, self.upsample, self.siting)
 
     def planes(self):
         """the read set as ONE view: data [T0, H, the words of ceil(W / P) groups] - the pitch padding cut off"""
@@ -562,6 +591,9 @@ class PackedYuvFrames(YuvFrames):
         hdr = None
         if self.hdr is not None:
             hdr = dict(self.hdr, lut=hdr_lut(self.transfer, self.bits, self.peak_nits, self.sdr_white, planes[0].device))
+        if self.interpolates:       # ONE tdc_yuv_packed_linear_to_rgb launch in its place
+            return ops.yuv_packed_linear_to_rgb(planes[0], self.fmt, self.coef, H, W, self.bits, self.msb_aligned,
+                                                CHROMA_SITES[self.siting], hdr=hdr, out=out)
         return ops.yuv_packed_to_rgb(planes[0], self.fmt, self.coef, H, W, self.bits, self.msb_aligned, hdr=hdr, out=out)
 
 
@@ -612,7 +644,7 @@ def selected_planes(yuv, idx, device):
 
 def _preprocess_selected_yuv(yuv, idx, towers, dtype, slab, device, out, stats):
     """preprocess_selected for a YuvFrames: per slab of kept frames ONE conversion launch (YuvFrames.to_rgb: tdc_yuv420_to_rgb
-    for 8-bit 4:2:0, tdc_yuv_to_rgb for every other planar kind, tdc_yuv_packed_to_rgb for a packed surface) into a [slab, H, W, 3] RGB scratch, then tdc_preprocess_frames per tower on that scratch - the RGB path's launches on the frames the planes convert
+    for 8-bit 4:2:0, tdc_yuv_to_rgb for every other planar kind, tdc_yuv_packed_to_rgb for a packed surface; with upsample="linear" tdc_yuv_linear_to_rgb / tdc_yuv_packed_linear_to_rgb in their place) into a [slab, H, W, 3] RGB scratch, then tdc_preprocess_frames per tower on that scratch - the RGB path's launches on the frames the planes convert
     to.  Both scratches are slab-sized and serve the whole video."""
     idx = check_indices(idx, yuv.shape[0])
     _check_dtype_slab(dtype, slab)
