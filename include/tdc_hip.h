@@ -764,6 +764,34 @@ typedef struct {
 } tdc_rgb_source;
 int tdc_pack_rgb(const tdc_rgb_source* s, int T, int H, int W, unsigned char* dst /* [T, H, W, 3] contiguous */, void* stream);
 
+/* ---- one field of interlaced video rebuilt to a full-height frame ------------------------------
+ * An interlaced picture holds two fields taken at two moments; one of them, kept alone, is a half-height picture without
+ * the double image.  src: the kept field's RGB picture F, Hf rows of W pixels per frame, sample c of field pixel (t, k, x)
+ * at src + t * frame_stride + k * row_stride + 3 x + c (byte strides: 3 W for a dense field picture, 6 W for the field of
+ * an interleaved RGB frame read where it lies) -> dst uint8 [T, 2 Hf, W, 3] contiguous, the rebuilt frames O, what
+ * tdc_preprocess_frames takes.  parity = 0: the field is the even rows of the frame (the top field), 1: the odd rows.
+ * With cl(i) = min(max(i, 0), Hf - 1), per byte:
+ *     O[2k + parity]      = F[k]                                                        the kept rows: exact copies
+ *     O[2k + 1 - parity], with m = k - parity:
+ *         fill 0 (linear):  (F[cl(m)] + F[cl(m+1)] + 1) >> 1
+ *         fill 1 (cubic):   clip_0_255((9 * (F[cl(m)] + F[cl(m+1)]) - F[cl(m-1)] - F[cl(m+2)] + 8) >> 4)
+ * the two-tap mean and the (-1, 9, 9, -1) / 16 half-sample filter, both in integers; a constant column stays constant.
+ * The cubic sum lies in [-502, 4598]: every negative sum clips to 0 whichever way a shift of a negative number rounds, so
+ * that rounding is no part of the definition.  A stated formula, no library's deinterlacer.
+ * A thread owns a column of 16, 4 or 1 bytes of the row and walks a run of 16 field rows, the filter's window held in
+ * registers and slid down; the host picks the column width from the alignment of src, both strides, dst and 3 W alone
+ * (all multiples of 16: 16 bytes; of 4: 4 bytes; otherwise bytes; frame_stride at T = 1 and row_stride at Hf = 1 are never
+ * applied and are left out) and the forms produce the same bytes.  Every byte
+ * offset is 64-bit.
+ * TDC_E_BADARG before any launch: a null pointer; T or W outside [1, 65535]; Hf outside [1, 32767]; parity or fill
+ * outside {0, 1}; a stride that is negative or above 2^40; row_stride < 3 W; frame_stride < (Hf - 1) * row_stride + 3 W;
+ * dst [0, 6 T Hf W) overlapping the source extent [src, src + (T - 1) * frame_stride + (Hf - 1) * row_stride + 3 W).
+ * writes: dst [0, 6 T Hf W) and nothing else.  reads: the 3 W bytes of each of the Hf rows of each of the T frames and
+ * nothing else - never the gap between two rows, where the other field lies, nor the pitch padding, nor another frame. */
+int tdc_field_to_frame(const unsigned char* src, long long frame_stride, long long row_stride /* bytes */,
+                       int T, int Hf, int W, int parity /* 0: field on even rows, 1: odd */, int fill /* 0 linear, 1 cubic */,
+                       unsigned char* dst /* [T, 2 Hf, W, 3] contiguous */, void* stream);
+
 /* ---- BEATs audio front end --------------------------------------------------------------------------
  * kaldi fbank as BEATs.preprocess calls it (tdc/audio_models/beats/BEATs.py:115-129: torchaudio.compliance.kaldi.fbank,
  * 128 mel bins, 16 kHz, 25 ms / 10 ms, povey window, pre-emphasis 0.97, DC removal, dither 0, snip_edges) on B

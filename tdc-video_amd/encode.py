@@ -1077,7 +1077,8 @@ class FrameSource:
     engine converts what it keeps.  So is a preprocess.Oriented over either kind (.shape is that of
     the upright frames, so image_size defaults to the upright (H', W')), and a preprocess.RgbFrames
     (channel-first, B G R, 4-byte-pixel or gray pictures; .shape is that of the RGB frames it stands for; DESIGN.md section
-    24)."""
+    24), and a preprocess.Interlaced over any of these kinds but an Oriented, which goes around it (one field kept and rebuilt
+    to full height; .shape is that of the rebuilt frames)."""
 
     def __init__(self, frames, image_size=None, cache=None):
         self.frames, self.cache = frames, cache

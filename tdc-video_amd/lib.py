@@ -253,6 +253,8 @@ SIGNATURES = {
                                                C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdc_orient_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdc_pack_rgb": (C.c_int, [C.POINTER(RgbSource), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "tdc_field_to_frame": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_void_p]),
     "tdc_fbank_frames": (C.c_int, [C.c_longlong]),
     "tdc_fbank": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),

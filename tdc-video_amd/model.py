@@ -559,7 +559,9 @@ class CambrianMetaModel:
         may be a preprocess.YuvFrames - NV12 / I420 planes as the decoder wrote them - or a
         preprocess.Oriented over either kind: stored frames plus their display rotation / mirror (image_sizes
         is then the upright frames') - or a preprocess.RgbFrames: channel-first [T, 3, H, W], B G R, RGBA / BGRA / ARGB or gray
-        pictures as their source wrote them, bare or inside an Oriented.  Every sample runs through VideoEncoder.encode_frames: a1 first, then
+        pictures as their source wrote them, bare or inside an Oriented - or a preprocess.Interlaced over
+        any of these kinds (interlaced video, one field kept and rebuilt to full height), bare or inside an
+        Oriented.  Every sample runs through VideoEncoder.encode_frames: a1 first, then
         only the kept frames are uploaded and resized - the 10-tuple is bit for bit the pixel call's on
         preprocess.process_images of the same frames.  Absent / False: pixels.  Composes with `config.tdc_video_cache_bytes`;
         set together with `config.tdc_feature_inputs`, `tdc_shard_frames`, `tdc_batch_frames`, `tdc_shard_cache_bytes` or

@@ -933,6 +933,41 @@ def pack_rgb(src, frame_stride, row_stride, pixel_stride, chan, T, H, W, out=Non
     return out
 
 
+FIELD_FILLS = {"linear": 0, "cubic": 1}
+
+
+def field_pixels_dense(src):
+    """a [T, Hf, W, 3] view as tdc_field_to_frame addresses it: the three bytes of a pixel adjacent, the W pixels of a row adjacent
+    (the row and frame strides are free)"""
+    return src.stride(3) == 1 and (src.shape[2] == 1 or src.stride(2) == 3)
+
+
+def field_to_frame(src, parity, fill, out=None):
+    """the kept field of T interlaced frames, a uint8 [T, Hf, W, 3] view on the GPU whose pixels are dense (row and frame
+    strides free: the field of an interleaved frame read where it lies, or a dense field picture) -> the rebuilt frames uint8
+    [T, 2 Hf, W, 3] (tdc_field_to_frame).  parity 0: the field is the frame's even rows (top), 1: the
+    odd rows; fill "linear" / "cubic" (or 0 / 1): how the other rows are made.  out: a contiguous uint8 tensor of that
+    shape that shares no byte with the field's extent."""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and 0 not in src.shape, \
+        "src must be a uint8 [T, Hf, W, 3] CUDA view"
+    T, Hf, W, _ = src.shape
+    if not field_pixels_dense(src):      # not an assert: read as if dense, such a view would give wrong frames without a word
+        raise ValueError("src: the pixels of a row must be dense (strides (.., .., 3, 1)), got strides %s" % (tuple(src.stride()),))
+    # a dimension of one element has no stride to speak of: give it the least the entry takes (the entry leaves a stride it never
+    # applies out of its choice of form)
+    rs = src.stride(1) if Hf > 1 else 3 * W
+    fs = src.stride(0) if T > 1 else (Hf - 1) * rs + 3 * W
+    fill = FIELD_FILLS.get(fill, fill)
+    shape = (T, 2 * Hf, W, 3)
+    if out is None:
+        out = torch.empty(shape, device=src.device, dtype=torch.uint8)
+    assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous() and out.device == src.device
+    with torch.cuda.device(src.device):
+        L.check(L.load().tdc_field_to_frame(_ptr(src), int(fs), int(rs), T, Hf, W, int(parity), int(fill), _ptr(out), _stream()),
+                "tdc_field_to_frame")
+    return out
+
+
 def relpos_gate(q, rows, heads, head_dim, w2, b2, grep_a, out=None):
     """q: [rows, ld] 16-bit view (un-scaled q_proj output) -> gate fp32 [rows, heads]."""
     assert q.is_cuda and q.dim() == 2 and q.stride(1) == 1 and q.shape[0] >= rows and q.shape[1] >= heads * head_dim

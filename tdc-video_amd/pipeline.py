@@ -1269,7 +1269,10 @@ class VideoEncoder:
         kind may be wrapped in a preprocess.Oriented (a display rotation / mirror): the kept frames are
         turned upright on the device and `frames[idx]` reads as the upright frames.  frames may also be a preprocess.RgbFrames
         (channel-first, B G R, 4-byte-pixel or gray pictures, pitched or cropped), bare or inside an
-        Oriented: the kept frames are packed to R G B on the device and `frames[idx]` reads as the frames they stand for."""
+        Oriented: the kept frames are packed to R G B on the device and `frames[idx]` reads as the frames they stand for.
+        Any of these kinds may be wrapped in a preprocess.Interlaced, bare or inside an Oriented: only
+        the kept field of the kept frames is uploaded, the full-height frames are rebuilt from it on the device and
+        `frames[idx]` reads as the rebuilt frames."""
         if len(self.frame_towers) != 2:
             raise ValueError("frame_towers is a pair of {R, mean, std} dicts (SigLIP, DINOv2), got %d" % len(self.frame_towers))
         px_siglip, px_dino = preprocess.preprocess_selected(frames, idx, self.frame_towers, self.dtype, self.frame_slab,

@@ -451,6 +451,14 @@ class YuvFrames:
         return YuvFrames(self.y[s], tuple(c[s] for c in self.chroma), self.c_step, self.shape[2], self.matrix, self.full_range,
                          self.bits, self.msb_aligned, self.subsampling, self.transfer, self.peak_nits, self.sdr_white, self.primaries, self.upsample, self.siting)
 
+    def field(self, parity, layout="interleaved"):
+        """one field of interlaced frames: a YuvFrames over the same memory whose planes hold every
+        plane's rows of field `parity` (field_rows), every other parameter kept - a half-height picture of the same kind"""
+        return YuvFrames(self.y[:, field_rows(self.y.shape[1], parity, layout)],
+                         tuple(c[:, field_rows(c.shape[1], parity, layout)] for c in self.chroma), self.c_step, self.shape[2],
+                         self.matrix, self.full_range, self.bits, self.msb_aligned, self.subsampling, self.transfer, self.peak_nits,
+                         self.sdr_white, self.primaries, self.upsample, self.siting)
+
     def planes(self):
         """the read set as views: (y [T0, H, W], one or two chroma planes [T0, Hc, c_step * Wc]) - the pitch padding cut off"""
         W = self.shape[2]
@@ -576,6 +584,13 @@ class PackedYuvFrames(YuvFrames):
             raise TypeError("YuvFrames takes a slice of frames a:b, got %r" % (s,))
         return PackedYuvFrames(self.y[s], self.name, self.shape[2], self.matrix, self.full_range, self.bits, self.msb_aligned,
                                self.transfer, self.peak_nits, self.sdr_white, self.primaries, self.upsample, self.siting)
+
+    def field(self, parity, layout="interleaved"):
+        """one field of interlaced frames: a PackedYuvFrames over the surface's rows of field `parity`
+        (field_rows), every other parameter kept"""
+        return PackedYuvFrames(self.y[:, field_rows(self.y.shape[1], parity, layout)], self.name, self.shape[2], self.matrix,
+                               self.full_range, self.bits, self.msb_aligned, self.transfer, self.peak_nits, self.sdr_white,
+                               self.primaries, self.upsample, self.siting)
 
     def planes(self):
         """the read set as ONE view: data [T0, H, the words of ceil(W / P) groups] - the pitch padding cut off"""
@@ -771,6 +786,12 @@ class RgbFrames:
             raise TypeError("RgbFrames takes a slice of frames a:b, got %r" % (s,))
         return RgbFrames(self.data[s], self.layout, self.order)
 
+    def field(self, parity, layout="interleaved"):
+        """one field of interlaced frames: an RgbFrames over the same memory holding the pictures'
+        rows of field `parity` (field_rows), layout and order kept"""
+        rows = field_rows(self.shape[1], parity, layout)
+        return RgbFrames(self.data[:, rows] if self.layout == "hwc" else self.data[:, :, rows], self.layout, self.order)
+
     def descriptor(self):
         """(byte offset of the base inside data's storage, frame_stride, row_stride, pixel_stride, chan) as Python ints, from
         the strides alone: the R, G, B sample of pixel (t, y, x) is the byte base + t * frame_stride + y * row_stride +
@@ -898,7 +919,8 @@ class Oriented:
         hflip:      O'[y, x] = O[y, W'-1-x]
     (np.rot90(S, -1) is rotate 90; a vertical flip is rotate 180 with hflip).  .shape is (T0, H', W', 3), that of the upright
     frames; o[a:b] is an Oriented over the same memory.  The kept frames are turned on the device, in front of the resize
-    (tdc_orient_frames); everything behind sees the upright frames."""
+    (tdc_orient_frames); everything behind sees the upright frames.  `frames` may also be an Interlaced over any of these
+    kinds: the field is rebuilt to the stored frame first, then the frame is turned."""
 
     def __init__(self, frames, rotate=0, hflip=False):
         if isinstance(rotate, bool) or rotate not in ROTATIONS:
@@ -907,7 +929,7 @@ class Oriented:
             raise ValueError("hflip must be True / False, got %r" % (hflip,))
         if is_oriented(frames):
             raise ValueError("frames is an Oriented already: compose the two orientations into one")
-        self.frames = frames if is_yuv_frames(frames) or is_rgb_frames(frames) else check_frames(frames)
+        self.frames = frames if is_yuv_frames(frames) or is_rgb_frames(frames) or is_interlaced(frames) else check_frames(frames)
         self.rotate, self.hflip, self.quarters = int(rotate), hflip, int(rotate) // 90
         T0, H, W, _ = self.frames.shape
         self.shape = (int(T0), int(W), int(H), 3) if self.quarters & 1 else (int(T0), int(H), int(W), 3)
@@ -947,6 +969,8 @@ def _preprocess_selected_oriented(o, idx, towers, dtype, slab, device, out, stat
     inner = o.frames
     if o.is_identity:
         return preprocess_selected(inner, idx, towers, dtype, slab, device, out, stats)
+    if is_interlaced(inner):        # the field is rebuilt first, then the frame is turned
+        return _preprocess_selected_interlaced(inner, idx, towers, dtype, slab, device, out, stats, orient=o)
     if is_rgb_frames(inner) and inner.is_identity:
         inner = inner.data
     yuv, packs = is_yuv_frames(inner), is_rgb_frames(inner)
@@ -992,6 +1016,165 @@ def _preprocess_selected_oriented(o, idx, towers, dtype, slab, device, out, stat
     return [dst[:T] for dst in out]
 
 
+# ---- interlaced video: one field rebuilt to full height ---------------------------------------------
+FIELDS = ("top", "bottom")
+FIELD_LAYOUTS = ("interleaved", "sequential_tb", "sequential_bt")
+
+
+def field_rows(n, parity, layout="interleaved"):
+    """the rows of field `parity` (0 top, 1 bottom) among the n rows (n even) of one plane, as a slice: every second row from
+    row `parity` on ("interleaved"), or one half of the rows - the top field first ("sequential_tb", V4L2 FIELD_SEQ_TB) or the
+    bottom field first ("sequential_bt")"""
+    if layout == "interleaved":
+        return slice(parity, None, 2)
+    first = parity == (0 if layout == "sequential_tb" else 1)
+    return slice(0, n // 2) if first else slice(n // 2, n)
+
+
+class Interlaced:
+    """T0 interlaced frames and the field to keep of them, described and not copied: `frames` is what the frames entries take
+    except an Oriented or an Interlaced - uint8 [T0, H, W, 3] (torch tensor or numpy array, host or device), an RgbFrames, or a
+    YuvFrames, planar or packed, SDR or HDR - holding two fields per frame: layout "interleaved", field f (0 top, 1 bottom)
+    is rows f, f + 2, ... of every plane; "sequential_tb", the top field is rows [0, H / 2) of every plane and the bottom
+    field the rest (V4L2 FIELD_SEQ_TB); "sequential_bt", the reverse.  The chroma planes of a vertically sub-sampled surface
+    split the same way, plane by plane, so a field of a 4:2:0 surface is a half-height 4:2:0 picture with its own chroma rows.
+    `field` "top" / "bottom" is the field that is kept: it alone is uploaded, converted or packed, and its Hf = H / 2 rows
+    F[k] become the rows 2k + p of the frame (p = 0 top, 1 bottom).  `fill` makes the other rows, per byte of the RGB picture,
+    with m = k - p and cl(i) = min(max(i, 0), Hf - 1):
+        "linear":  O[2k + 1 - p] = (F[cl(m)] + F[cl(m+1)] + 1) >> 1
+        "cubic":   O[2k + 1 - p] = clip_0_255((9 * (F[cl(m)] + F[cl(m+1)]) - F[cl(m-1)] - F[cl(m+2)] + 8) >> 4)
+    (tdc_field_to_frame: a stated formula, no library's deinterlacer).  .shape is (T0, H, W, 3), that of the rebuilt frames;
+    x[a:b] is an Interlaced over the same memory.  An Oriented goes around an Interlaced, not inside: fields belong to the
+    coded picture, so the field is rebuilt first and the frame turned after.  ValueError: a bad field / fill / layout; H odd;
+    H % 4 != 0 on a surface with vertically sub-sampled chroma (its two chroma fields would differ in height); upsample
+    "linear" on such a surface (a field's chroma sits a quarter of a field row off the sitings of section 26)."""
+
+    def __init__(self, frames, field="top", fill="linear", layout="interleaved"):
+        if field not in FIELDS:
+            raise ValueError("field must be one of %s, got %r" % (FIELDS, field))
+        if fill not in ops.FIELD_FILLS:
+            raise ValueError("fill must be one of %s, got %r" % (sorted(ops.FIELD_FILLS), fill))
+        if layout not in FIELD_LAYOUTS:
+            raise ValueError("layout must be one of %s, got %r" % (FIELD_LAYOUTS, layout))
+        if is_oriented(frames):
+            raise ValueError("frames is an Oriented: fields belong to the coded picture, so the Oriented goes around the "
+                             "Interlaced - Oriented(Interlaced(frames, ...), rotate, hflip)")
+        if is_interlaced(frames):
+            raise ValueError("frames is an Interlaced already")
+        self.frames = frames if is_yuv_frames(frames) or is_rgb_frames(frames) else check_frames(frames)
+        self.field, self.fill, self.layout, self.parity = field, fill, layout, FIELDS.index(field)
+        T0, H, W, _ = self.frames.shape
+        if H % 2:
+            raise ValueError("interlaced frames hold two fields of equal height: H must be even, got %d" % H)
+        if is_yuv_frames(self.frames) and self.frames.sub_y:
+            if H % 4:
+                raise ValueError("a %s surface splits into fields whose chroma planes have H / 4 rows: H must be a multiple of 4, "
+                                 "got %d" % (self.frames.subsampling, H))
+            if self.frames.upsample == "linear":
+                raise ValueError("upsample 'linear' on a %s surface is not taken inside an Interlaced: a field's chroma rows sit a "
+                                 "quarter of a field row off the sitings that are interpolated; use 'replicate'" % self.frames.subsampling)
+        self.shape = (int(T0), int(H), int(W), 3)
+
+    @property
+    def is_cuda(self):
+        return self.frames.is_cuda
+
+    def __getitem__(self, s):
+        if not isinstance(s, slice) or s.step not in (None, 1):
+            raise TypeError("Interlaced takes a slice of frames a:b, got %r" % (s,))
+        return Interlaced(self.frames[s], self.field, self.fill, self.layout)
+
+    def field_frames(self):
+        """the kept field as a view of the wrapped kind: a uint8 [T0, H / 2, W, 3] tensor, an RgbFrames or a YuvFrames over the
+        same memory"""
+        if torch.is_tensor(self.frames):
+            return self.frames[:, field_rows(self.shape[1], self.parity, self.layout)]
+        return self.frames.field(self.parity, self.layout)
+
+
+def is_interlaced(x):
+    """an Interlaced, recognised by its members (the package can be imported under two names: not by isinstance)"""
+    return all(hasattr(x, k) for k in ("frames", "field", "fill", "layout", "parity", "shape")) and not torch.is_tensor(x)
+
+
+def selected_field(field, idx, device):
+    """the frames idx (check_indices) of a field view (uint8 [T0, Hf, W, 3], strided: Interlaced.field_frames) on `device` ->
+    (a [T, Hf, W, 3] tensor whose pixels are dense, bytes uploaded).  On the host the kept frames' field rows are gathered into
+    one pinned staging tensor and uploaded - a dropped frame and the other field are never read or copied; on the device the
+    view is read where it lies when every frame is kept and its pixels are dense (three adjacent bytes, W of them adjacent in a
+    row: what tdc_field_to_frame addresses), and the kept frames' field rows are gathered dense there otherwise - under a
+    selection, or for a view such as a permuted channel-first tensor or rgba[..., :3], which check_frames takes."""
+    if field.is_cuda:
+        if idx is not None:
+            field = torch.index_select(field, 0, torch.tensor(idx, device=field.device))
+        elif not ops.field_pixels_dense(field):
+            field = field.contiguous()
+        return field.to(device), 0
+    stage = torch.empty((field.shape[0] if idx is None else len(idx),) + tuple(field.shape[1:]), dtype=torch.uint8, pin_memory=True)
+    if idx is None:
+        stage.copy_(field)
+    else:
+        torch.index_select(field, 0, torch.tensor(idx), out=stage)
+    return stage.to(device, non_blocking=True), stage.numel()
+
+
+def _preprocess_selected_interlaced(it, idx, towers, dtype, slab, device, out, stats, orient=None):
+    """preprocess_selected for an Interlaced, bare or inside the non-identity Oriented `orient`.  a1's frames are uploaded as
+    the kept FIELD of the wrapped frames is - half the bytes - and per slab of kept frames: the field of YUV planes is
+    converted, and the field of an RgbFrames is packed, by their one launch (whatever launch that surface issues on a
+    half-height picture) into a [slab, H / 2, W, 3] scratch; plain uint8 frames' field is read where it lies.  ONE
+    tdc_field_to_frame launch then writes the rebuilt frames into a [slab, H, W, 3] scratch, tdc_orient_frames turns them when
+    `orient` is given, and tdc_preprocess_frames runs per tower on the result - the RGB path's launches on the rebuilt frames.
+    A slab is rebuilt once and both towers read it.  The scratches are slab-sized and serve the whole video."""
+    inner = it.field_frames()
+    if is_rgb_frames(inner) and inner.is_identity:
+        inner = inner.data
+    yuv, packs = is_yuv_frames(inner), is_rgb_frames(inner)
+    idx = check_indices(idx, it.shape[0])
+    _check_dtype_slab(dtype, slab)
+    if device is None:
+        device = (inner.y.device if yuv else inner.device) if inner.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    T0, H, W, _ = it.shape
+    Ho, Wo = (H, W) if orient is None else orient.shape[1:3]
+    if yuv:
+        planes, uploaded = selected_planes(inner, idx, device)
+        T = planes[0].shape[0]
+    elif packs:
+        kept, uploaded = selected_pixels(inner, idx, device)
+        T = kept.shape[0]
+    else:
+        kept, uploaded = selected_field(inner, idx, device)
+        T = kept.shape[0]
+    if stats is not None:
+        stats.update(frames_in=T0, frames_resized=T, bytes_uploaded=uploaded)
+    out = _outputs(out, towers, T, dtype, device)
+    lib = L.load()
+    n0 = min(slab, T)
+    nscr = max(lib.tdc_preprocess_scratch_bytes(n0, Ho, Wo, t["R"]) for t in towers)
+    scratch = torch.empty(max(nscr, 1), dtype=torch.uint8, device=device)
+    rgb = torch.empty((n0, H // 2, W, 3), dtype=torch.uint8, device=device) if yuv or packs else None
+    rebuilt = torch.empty((n0, H, W, 3), dtype=torch.uint8, device=device)
+    upright = torch.empty((n0, Ho, Wo, 3), dtype=torch.uint8, device=device) if orient is not None else rebuilt
+    tables = [_tables(max(Ho, Wo), t["R"], t["mean"], t["std"], device) for t in towers]
+    with torch.cuda.device(device):
+        for s in range(0, T, slab):
+            n = min(slab, T - s)
+            if yuv:
+                inner.to_rgb([p[s:s + n] for p in planes], rgb[:n])
+            elif packs:
+                kept[s:s + n].pack(rgb[:n])
+            ops.field_to_frame(rgb[:n] if yuv or packs else kept[s:s + n], it.parity, it.fill, out=rebuilt[:n])
+            if orient is not None:
+                ops.orient_frames(rebuilt[:n], orient.quarters, orient.hflip, out=upright[:n])
+            for t, dst, (bounds, coeffs, lut) in zip(towers, out, tables):
+                pad = [int(x * 255) for x in t["mean"]]   # expand2square background (tdc/mm_datautils.py:302-304)
+                L.check(lib.tdc_preprocess_frames(ops._ptr(upright), n, Ho, Wo, t["R"], ops._ptr(bounds), ops._ptr(coeffs),
+                                                  coeffs.shape[1], pad[0], pad[1], pad[2], ops._ptr(lut), ops._ptr(dst[s:s + n]), 0,
+                                                  ops._dtcode(dtype), ops._ptr(scratch), ops._stream()), "tdc_preprocess_frames")
+    return [dst[:T] for dst in out]
+
+
 def _check_dtype_slab(dtype, slab):
     if dtype not in (torch.float16, torch.bfloat16):
         raise ValueError("preprocess_selected writes float16 or bfloat16 pixels, got %s" % (dtype,))
@@ -1029,9 +1212,14 @@ def preprocess_selected(frames, idx, towers=(SIGLIP, DINOV2), dtype=torch.float1
     launch per slab, in front of the same resize - the result is what the upright frames give.
     frames may be an RgbFrames (an Oriented may hold one): channel-first, B G R, 4-byte-pixel or gray
     pictures, pitched or cropped, packed to R G B on the device, one launch per slab, in front of the same resize - the result
-    is what the [T0, H, W, 3] frames Pillow's .convert("RGB") makes of them give."""
+    is what the [T0, H, W, 3] frames Pillow's .convert("RGB") makes of them give.
+    frames may be an Interlaced over any of these kinds (an Oriented may hold one): only the kept field
+    is uploaded, converted or packed, and the full-height frames are rebuilt from it on the device, one tdc_field_to_frame
+    launch per slab, in front of the same resize - the result is what the frames a host rebuilds by the stated formula give."""
     if is_oriented(frames):
         return _preprocess_selected_oriented(frames, idx, towers, dtype, slab, device, out, stats)
+    if is_interlaced(frames):
+        return _preprocess_selected_interlaced(frames, idx, towers, dtype, slab, device, out, stats)
     if is_rgb_frames(frames):
         return _preprocess_selected_rgb(frames, idx, towers, dtype, slab, device, out, stats)
     if is_yuv_frames(frames):
