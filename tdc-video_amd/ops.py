@@ -790,13 +790,8 @@ def yuv_hdr_to_rgb(y, u, v, c_step, coef, H, W, bits, msb_aligned, subsampling, 
     views are yuv_to_rgb's.  coef = (y_off, ky, krv, kgu, kgv, kbu) to codes at full depth, e.g.
     preprocess.yuv_code_coefficients(matrix, full_range, bits).  hdr: the descriptor as a mapping - lut (float32 [2^bits] on
     the planes' device, preprocess.hdr_table), ootf_scale, ootf_exp, luma (3), inv_p2, gamut (9, row-major)."""
-    lut = hdr["lut"]
-    assert lut.is_cuda and lut.dtype == torch.float32 and lut.dim() == 1 and lut.numel() == 1 << bits and lut.is_contiguous() \
-        and lut.device == y.device, "hdr['lut'] must be float32 [2^bits] on the planes' device"
-    assert len(hdr["luma"]) == 3 and len(hdr["gamut"]) == 9
+    h = _hdr_desc(hdr, bits, y.device)
     p, out = _yuv_planes(y, u, v, c_step, H, W, bits, msb_aligned, subsampling, out)
-    h = L.HdrDesc(lut.data_ptr(), hdr["ootf_scale"], hdr["ootf_exp"], (C.c_float * 3)(*hdr["luma"]), hdr["inv_p2"],
-                  (C.c_float * 9)(*hdr["gamut"]))
     L.check(L.load().tdc_yuv_hdr_to_rgb(C.byref(p), C.byref(L.YuvCoef(*coef)), C.byref(h), y.shape[0], H, W, _ptr(out), _stream()),
             "tdc_yuv_hdr_to_rgb")
     return out
@@ -875,15 +870,7 @@ def _yuv_packed(surface, fmt, H, W, bits, msb_aligned, hdr, out):
     # torch leaves the stride of a size-1 dimension arbitrary: one frame has no frame stride, one row the dense pitch
     p = L.YuvPacked(surface.data_ptr(), ws * surface.stride(0) if T > 1 else 0, ws * (surface.stride(1) if surface.shape[1] > 1 else row),
                     L.YUV_PACKED_FORMATS[fmt], bits, int(msb_aligned))
-    h = None
-    if hdr is not None:
-        lut = hdr["lut"]
-        assert lut.is_cuda and lut.dtype == torch.float32 and lut.dim() == 1 and lut.numel() == 1 << bits and lut.is_contiguous() \
-            and lut.device == surface.device, "hdr['lut'] must be float32 [2^bits] on the surface's device"
-        assert len(hdr["luma"]) == 3 and len(hdr["gamut"]) == 9
-        h = C.byref(L.HdrDesc(lut.data_ptr(), hdr["ootf_scale"], hdr["ootf_exp"], (C.c_float * 3)(*hdr["luma"]), hdr["inv_p2"],
-                              (C.c_float * 9)(*hdr["gamut"])))
-    return p, h, T, out
+    return p, None if hdr is None else C.byref(_hdr_desc(hdr, bits, surface.device)), T, out
 
 
 def yuv_packed_linear_to_rgb(surface, fmt, coef, H, W, bits, msb_aligned, site, hdr=None, out=None):

@@ -80,11 +80,18 @@ def preprocess_frames(frames, R, mean, std, dtype=torch.float16, out_f32=False):
     out = torch.empty(T, 3, R, R, device=frames.device, dtype=torch.float32 if out_f32 else dtype)
     nscr = lib.tdc_preprocess_scratch_bytes(T, H, W, R)
     scratch = torch.empty(max(nscr, 1), dtype=torch.uint8, device=frames.device)
-    pad = [int(x * 255) for x in mean]        # expand2square background (tdc/mm_datautils.py:302-304)
-    L.check(lib.tdc_preprocess_frames(ops._ptr(frames), T, H, W, R, ops._ptr(bounds), ops._ptr(coeffs), coeffs.shape[1],
-                                      pad[0], pad[1], pad[2], ops._ptr(lut), ops._ptr(out), int(out_f32),
-                                      ops._dtcode(dtype), ops._ptr(scratch), ops._stream()), "tdc_preprocess_frames")
+    _resize(frames, T, H, W, dict(R=R, mean=mean), (bounds, coeffs, lut), out, dtype, scratch, out_f32)
     return out
+
+
+def _resize(frames, n, H, W, tower, tables, out, dtype, scratch, out_f32=False):
+    """ONE tdc_preprocess_frames launch: n contiguous uint8 [H, W, 3] frames on the GPU -> out [n, 3, R, R] of one tower
+    (`tables`: its _tables for max(H, W); `scratch`: tdc_preprocess_scratch_bytes(>= n, H, W, R) bytes)"""
+    bounds, coeffs, lut = tables
+    pad = [int(x * 255) for x in tower["mean"]]        # expand2square background (tdc/mm_datautils.py:302-304)
+    L.check(L.load().tdc_preprocess_frames(ops._ptr(frames), n, H, W, tower["R"], ops._ptr(bounds), ops._ptr(coeffs), coeffs.shape[1],
+                                           pad[0], pad[1], pad[2], ops._ptr(lut), ops._ptr(out), int(out_f32),
+                                           ops._dtcode(dtype), ops._ptr(scratch), ops._stream()), "tdc_preprocess_frames")
 
 
 def process_images(frames, dtype=torch.float16, towers=(SIGLIP, DINOV2)):
@@ -313,7 +320,6 @@ class YuvFrames:
 
     def __init__(self, y, chroma, c_step, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False,
                  subsampling="420", transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
-        self.upsample, self.siting = _check_chroma(upsample, siting)
         if c_step not in (1, 2):
             raise ValueError("c_step is 1 (planar u, v) or 2 (interleaved uv), got %r" % (c_step,))
         names = ("uv",) if c_step == 2 else ("u", "v")
@@ -325,26 +331,12 @@ class YuvFrames:
             raise ValueError("msb_aligned must be True / False, and False at 8 bits, got %r at %d bits" % (msb_aligned, bits))
         if subsampling not in ops.YUV_SUBSAMPLING:
             raise ValueError("subsampling must be one of %s, got %r" % (sorted(ops.YUV_SUBSAMPLING), subsampling))
-        if matrix == "bt2020" and bits == 8:
-            raise ValueError("matrix bt2020 is taken at 10 and 12 bits, the depths it is defined for; 8-bit planes take %s"
-                             % sorted(m for m in YUV_MATRICES if m != "bt2020"))
+        self._colour("planes", matrix=matrix, full_range=full_range, bits=bits, msb_aligned=msb_aligned, transfer=transfer,
+                     peak_nits=peak_nits, sdr_white=sdr_white, primaries=primaries, upsample=upsample, siting=siting)
         self.y = _plane(y, "y", bits)
         self.chroma = tuple(_plane(c, n, bits) for c, n in zip(chroma, names))
-        self.c_step, self.matrix, self.full_range = c_step, matrix, full_range
-        self.bits, self.msb_aligned, self.subsampling = bits, msb_aligned, subsampling
+        self.c_step, self.subsampling = c_step, subsampling
         self.sub_x, self.sub_y = ops.YUV_SUBSAMPLING[subsampling]
-        if primaries is None:
-            primaries = "bt2020" if matrix == "bt2020" else "bt709"
-        if primaries not in YUV_PRIMARIES:
-            raise ValueError("primaries must be None or one of %s, got %r" % (YUV_PRIMARIES, primaries))
-        self.transfer, self.peak_nits, self.sdr_white, self.primaries = transfer, peak_nits, sdr_white, primaries
-        if transfer == "sdr":
-            _check_nits(peak_nits, sdr_white)
-            self.coef, self.hdr = yuv_coefficients(matrix, full_range, bits), None
-        else:       # the descriptor of tdc_yuv_hdr_to_rgb but its table, which to_rgb takes from the planes' device
-            self.coef = yuv_code_coefficients(matrix, full_range, bits)
-            self.hdr = dict(_hdr_scalars(transfer, bits, peak_nits, sdr_white),
-                            gamut=GAMUT_2020_TO_709 if primaries == "bt2020" else GAMUT_IDENTITY)
         T0, H, pitch = self.y.shape
         W = pitch if width is None else int(width)
         if not 1 <= W <= pitch:
@@ -362,23 +354,57 @@ class YuvFrames:
             raise ValueError("u and v must have equal strides, got %s and %s" % (self.chroma[0].stride(), self.chroma[1].stride()))
         self.shape = (T0, H, W, 3)
 
+    def _colour(self, what, matrix, full_range, bits, msb_aligned, transfer, peak_nits, sdr_white, primaries, upsample, siting):
+        """the colour half of a constructor, the same for planar and packed surfaces (`what`: "planes" or "surfaces"; bits and
+        msb_aligned as the constructor settled them): checks the ten colour parameters, keeps them, and makes .coef and .hdr"""
+        self.upsample, self.siting = _check_chroma(upsample, siting)
+        if matrix == "bt2020" and bits == 8:
+            raise ValueError("matrix bt2020 is taken at 10 and 12 bits, the depths it is defined for; 8-bit %s take %s"
+                             % (what, sorted(m for m in YUV_MATRICES if m != "bt2020")))
+        if primaries is None:
+            primaries = "bt2020" if matrix == "bt2020" else "bt709"
+        if primaries not in YUV_PRIMARIES:
+            raise ValueError("primaries must be None or one of %s, got %r" % (YUV_PRIMARIES, primaries))
+        self.matrix, self.full_range, self.bits, self.msb_aligned = matrix, full_range, bits, msb_aligned
+        self.transfer, self.peak_nits, self.sdr_white, self.primaries = transfer, peak_nits, sdr_white, primaries
+        if transfer == "sdr":
+            _check_nits(peak_nits, sdr_white)
+            self.coef, self.hdr = yuv_coefficients(matrix, full_range, bits), None
+        else:       # the descriptor of tdc_yuv_hdr_to_rgb but its table, which hdr_on takes from the planes' device
+            self.coef = yuv_code_coefficients(matrix, full_range, bits)
+            self.hdr = dict(_hdr_scalars(transfer, bits, peak_nits, sdr_white),
+                            gamut=GAMUT_2020_TO_709 if primaries == "bt2020" else GAMUT_IDENTITY)
+
+    def colour(self):
+        """the ten colour parameters by name, as every constructor takes them"""
+        return dict(matrix=self.matrix, full_range=self.full_range, bits=self.bits, msb_aligned=self.msb_aligned,
+                    transfer=self.transfer, peak_nits=self.peak_nits, sdr_white=self.sdr_white, primaries=self.primaries,
+                    upsample=self.upsample, siting=self.siting)
+
+    def hdr_on(self, device):
+        """.hdr with the table of `device` (made once for it) attached, as ops takes the descriptor; None under transfer "sdr" """
+        return self.hdr and dict(self.hdr, lut=hdr_lut(self.transfer, self.bits, self.peak_nits, self.sdr_white, device))
+
     @classmethod
     def nv12(cls, y, uv, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False, subsampling="420",
              transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """a luma plane and one plane of interleaved (u, v) samples: NV12, and NV16 / NV24 with subsampling "422" / "444" """
-        return cls(y, (uv,), 2, width, matrix, full_range, bits, msb_aligned, subsampling, transfer, peak_nits, sdr_white, primaries, upsample, siting)
+        return cls(y, (uv,), 2, width, matrix=matrix, full_range=full_range, bits=bits, msb_aligned=msb_aligned, subsampling=subsampling,
+                   transfer=transfer, peak_nits=peak_nits, sdr_white=sdr_white, primaries=primaries, upsample=upsample, siting=siting)
 
     @classmethod
     def i420(cls, y, u, v, width=None, matrix="bt601", full_range=False, bits=8, msb_aligned=False, subsampling="420",
              transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """three planes: yuv420p, yuv422p, yuv444p and - bits 10 / 12 - their 10le / 12le forms"""
-        return cls(y, (u, v), 1, width, matrix, full_range, bits, msb_aligned, subsampling, transfer, peak_nits, sdr_white, primaries, upsample, siting)
+        return cls(y, (u, v), 1, width, matrix=matrix, full_range=full_range, bits=bits, msb_aligned=msb_aligned, subsampling=subsampling,
+                   transfer=transfer, peak_nits=peak_nits, sdr_white=sdr_white, primaries=primaries, upsample=upsample, siting=siting)
 
     @classmethod
     def p010(cls, y, uv, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0,
              primaries=None, upsample="replicate", siting="left"):
         """P010 as a hardware decoder writes it: 4:2:0, 16-bit words, the 10-bit sample in the high bits"""
-        return cls(y, (uv,), 2, width, matrix, full_range, 10, True, "420", transfer, peak_nits, sdr_white, primaries, upsample, siting)
+        return cls(y, (uv,), 2, width, matrix=matrix, full_range=full_range, bits=10, msb_aligned=True, subsampling="420",
+                   transfer=transfer, peak_nits=peak_nits, sdr_white=sdr_white, primaries=primaries, upsample=upsample, siting=siting)
 
     @classmethod
     def p016(cls, y, uv, bits, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0,
@@ -386,45 +412,53 @@ class YuvFrames:
         """a P016 surface holding `bits` (10 or 12) significant bits, MSB-aligned; the low bits are ignored"""
         if isinstance(bits, bool) or bits not in (10, 12):
             raise ValueError("bits of a P016 surface must be 10 or 12, got %r" % (bits,))
-        return cls(y, (uv,), 2, width, matrix, full_range, bits, True, "420", transfer, peak_nits, sdr_white, primaries, upsample, siting)
+        return cls(y, (uv,), 2, width, matrix=matrix, full_range=full_range, bits=bits, msb_aligned=True, subsampling="420",
+                   transfer=transfer, peak_nits=peak_nits, sdr_white=sdr_white, primaries=primaries, upsample=upsample, siting=siting)
 
     @classmethod
     def packed(cls, data, fmt, width=None, matrix="bt601", full_range=False, bits=None, msb_aligned=None, transfer="sdr",
                peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """a packed surface, luma and chroma in one row: a PackedYuvFrames, which every consumer of a
         YuvFrames takes.  fmt: one of YUV_PACKED_NAMES."""
-        return PackedYuvFrames(data, fmt, width, matrix, full_range, bits, msb_aligned, transfer, peak_nits, sdr_white, primaries, upsample, siting)
+        return PackedYuvFrames(data, fmt, width, matrix=matrix, full_range=full_range, bits=bits, msb_aligned=msb_aligned, transfer=transfer,
+                               peak_nits=peak_nits, sdr_white=sdr_white, primaries=primaries, upsample=upsample, siting=siting)
 
     @classmethod
     def yuy2(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """YUY2 / YUYV / ffmpeg yuyv422: bytes Y0 U Y1 V"""
-        return cls.packed(data, "yuyv", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries, upsample, siting)
+        return cls.packed(data, "yuyv", width, matrix=matrix, full_range=full_range, transfer=transfer, peak_nits=peak_nits,
+                          sdr_white=sdr_white, primaries=primaries, upsample=upsample, siting=siting)
 
     @classmethod
     def uyvy(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """UYVY / ffmpeg uyvy422: bytes U Y0 V Y1"""
-        return cls.packed(data, "uyvy", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries, upsample, siting)
+        return cls.packed(data, "uyvy", width, matrix=matrix, full_range=full_range, transfer=transfer, peak_nits=peak_nits,
+                          sdr_white=sdr_white, primaries=primaries, upsample=upsample, siting=siting)
 
     @classmethod
     def y210(cls, data, width=None, matrix="bt601", full_range=False, bits=10, msb_aligned=True, transfer="sdr", peak_nits=1000.0,
              sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """Y210 / Y212 / a Y216 container (ffmpeg y210le, y212le): 16-bit words Y0 U Y1 V holding `bits` (10 or 12) bits"""
-        return cls.packed(data, "y210", width, matrix, full_range, bits, msb_aligned, transfer, peak_nits, sdr_white, primaries, upsample, siting)
+        return cls.packed(data, "y210", width, matrix=matrix, full_range=full_range, bits=bits, msb_aligned=msb_aligned, transfer=transfer,
+                          peak_nits=peak_nits, sdr_white=sdr_white, primaries=primaries, upsample=upsample, siting=siting)
 
     @classmethod
     def ayuv(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """Microsoft AYUV / VUYX / ffmpeg vuya, vuyx: bytes V U Y A (ffmpeg's `ayuv`, bytes A Y U V, is packed(data, "ayuv"))"""
-        return cls.packed(data, "vuya", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries, upsample, siting)
+        return cls.packed(data, "vuya", width, matrix=matrix, full_range=full_range, transfer=transfer, peak_nits=peak_nits,
+                          sdr_white=sdr_white, primaries=primaries, upsample=upsample, siting=siting)
 
     @classmethod
     def y410(cls, data, width=None, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """Y410 / ffmpeg xv30le: one 32-bit word per pixel, U = bits 0-9, Y = 10-19, V = 20-29"""
-        return cls.packed(data, "y410", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries, upsample, siting)
+        return cls.packed(data, "y410", width, matrix=matrix, full_range=full_range, transfer=transfer, peak_nits=peak_nits,
+                          sdr_white=sdr_white, primaries=primaries, upsample=upsample, siting=siting)
 
     @classmethod
     def v210(cls, data, width, matrix="bt601", full_range=False, transfer="sdr", peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
         """v210: six pixels in four 32-bit words; `width` is required (a row holds whole blocks, often padded to 128 bytes)"""
-        return cls.packed(data, "v210", width, matrix, full_range, None, None, transfer, peak_nits, sdr_white, primaries, upsample, siting)
+        return cls.packed(data, "v210", width, matrix=matrix, full_range=full_range, transfer=transfer, peak_nits=peak_nits,
+                          sdr_white=sdr_white, primaries=primaries, upsample=upsample, siting=siting)
 
     @property
     def sample_size(self):
@@ -441,23 +475,30 @@ class YuvFrames:
         return self.y.is_cuda
 
     @property
+    def device(self):
+        return self.y.device
+
+    @property
     def interpolates(self):
         """upsample "linear" on a surface whose chroma is sub-sampled: on 4:4:4 there is nothing to interpolate"""
         return self.upsample == "linear" and self.sub_x == 1
 
+    def _over(self, cut):
+        """a YuvFrames of this kind over cut(plane) of every plane, every other parameter kept: rebuilt through the constructor,
+        which checks the view as it checks any planes"""
+        return YuvFrames(cut(self.y), tuple(cut(c) for c in self.chroma), self.c_step, self.shape[2], subsampling=self.subsampling,
+                         **self.colour())
+
     def __getitem__(self, s):
         if not isinstance(s, slice) or s.step not in (None, 1):
             raise TypeError("YuvFrames takes a slice of frames a:b, got %r" % (s,))
-        return YuvFrames(self.y[s], tuple(c[s] for c in self.chroma), self.c_step, self.shape[2], self.matrix, self.full_range,
-                         self.bits, self.msb_aligned, self.subsampling, self.transfer, self.peak_nits, self.sdr_white, self.primaries, self.upsample, self.siting)
+        return self._over(lambda p: p[s])
 
     def field(self, parity, layout="interleaved"):
-        """one field of interlaced frames: a YuvFrames over the same memory whose planes hold every
-        plane's rows of field `parity` (field_rows), every other parameter kept - a half-height picture of the same kind"""
-        return YuvFrames(self.y[:, field_rows(self.y.shape[1], parity, layout)],
-                         tuple(c[:, field_rows(c.shape[1], parity, layout)] for c in self.chroma), self.c_step, self.shape[2],
-                         self.matrix, self.full_range, self.bits, self.msb_aligned, self.subsampling, self.transfer, self.peak_nits,
-                         self.sdr_white, self.primaries, self.upsample, self.siting)
+        """one field of interlaced frames: a YuvFrames (packed: a PackedYuvFrames) over the same memory
+        whose planes hold every plane's rows of field `parity` (field_rows), every other parameter kept - a half-height picture
+        of the same kind"""
+        return self._over(lambda p: p[:, field_rows(p.shape[1], parity, layout)])
 
     def planes(self):
         """the read set as views: (y [T0, H, W], one or two chroma planes [T0, Hc, c_step * Wc]) - the pitch padding cut off"""
@@ -475,12 +516,11 @@ class YuvFrames:
         4:2:2 surface issues tdc_yuv_linear_to_rgb in their place."""
         y, u, v = self.kernel_views(planes)
         H, W = self.shape[1:3]
+        hdr = self.hdr_on(y.device)
         if self.interpolates:
-            hdr = self.hdr and dict(self.hdr, lut=hdr_lut(self.transfer, self.bits, self.peak_nits, self.sdr_white, y.device))
             return ops.yuv_linear_to_rgb(y, u, v, self.c_step, self.coef, H, W, self.bits, self.msb_aligned, self.subsampling,
                                          CHROMA_SITES[self.siting], hdr=hdr, out=out)
-        if self.hdr is not None:
-            hdr = dict(self.hdr, lut=hdr_lut(self.transfer, self.bits, self.peak_nits, self.sdr_white, y.device))
+        if hdr is not None:
             return ops.yuv_hdr_to_rgb(y, u, v, self.c_step, self.coef, H, W, self.bits, self.msb_aligned, self.subsampling, hdr, out=out)
         if self.is_420_8bit:
             return ops.yuv420_to_rgb(y, u, v, self.c_step, self.coef, H, W, out=out)
@@ -530,7 +570,6 @@ class PackedYuvFrames(YuvFrames):
 
     def __init__(self, data, fmt, width=None, matrix="bt601", full_range=False, bits=None, msb_aligned=None, transfer="sdr",
                  peak_nits=1000.0, sdr_white=203.0, primaries=None, upsample="replicate", siting="left"):
-        self.upsample, self.siting = _check_chroma(upsample, siting)
         if fmt not in YUV_PACKED_NAMES:
             raise ValueError("fmt must be one of %s, got %r" % (sorted(YUV_PACKED_NAMES), fmt))
         self.name = fmt
@@ -545,27 +584,12 @@ class PackedYuvFrames(YuvFrames):
         if not isinstance(msb_aligned, bool) or (msb_aligned and ws != 2):
             raise ValueError("msb_aligned must be True / False, and False for fmt %r (it places a sample in a 16-bit word), got %r"
                              % (fmt, msb_aligned))
-        if matrix == "bt2020" and bits == 8:
-            raise ValueError("matrix bt2020 is taken at 10 and 12 bits, the depths it is defined for; 8-bit surfaces take %s"
-                             % sorted(m for m in YUV_MATRICES if m != "bt2020"))
+        self._colour("surfaces", matrix=matrix, full_range=full_range, bits=bits, msb_aligned=msb_aligned, transfer=transfer,
+                     peak_nits=peak_nits, sdr_white=sdr_white, primaries=primaries, upsample=upsample, siting=siting)
         self.y = _packed_words(data, fmt, ws)
         self.chroma, self.c_step = (), 0
-        self.matrix, self.full_range = matrix, full_range
-        self.bits, self.msb_aligned = bits, msb_aligned
         self.subsampling = "422" if P != 1 else "444"
         self.sub_x, self.sub_y = ops.YUV_SUBSAMPLING[self.subsampling]
-        if primaries is None:
-            primaries = "bt2020" if matrix == "bt2020" else "bt709"
-        if primaries not in YUV_PRIMARIES:
-            raise ValueError("primaries must be None or one of %s, got %r" % (YUV_PRIMARIES, primaries))
-        self.transfer, self.peak_nits, self.sdr_white, self.primaries = transfer, peak_nits, sdr_white, primaries
-        if transfer == "sdr":
-            _check_nits(peak_nits, sdr_white)
-            self.coef, self.hdr = yuv_coefficients(matrix, full_range, bits), None
-        else:
-            self.coef = yuv_code_coefficients(matrix, full_range, bits)
-            self.hdr = dict(_hdr_scalars(transfer, bits, peak_nits, sdr_white),
-                            gamut=GAMUT_2020_TO_709 if primaries == "bt2020" else GAMUT_IDENTITY)
         T0, H, row = self.y.shape
         if width is None:
             if self.fmt == "v210":
@@ -579,18 +603,8 @@ class PackedYuvFrames(YuvFrames):
             raise ValueError("data %s: at most 65535 frames, rows and pixels per row" % (tuple(self.y.shape),))
         self.shape = (T0, H, W, 3)
 
-    def __getitem__(self, s):
-        if not isinstance(s, slice) or s.step not in (None, 1):
-            raise TypeError("YuvFrames takes a slice of frames a:b, got %r" % (s,))
-        return PackedYuvFrames(self.y[s], self.name, self.shape[2], self.matrix, self.full_range, self.bits, self.msb_aligned,
-                               self.transfer, self.peak_nits, self.sdr_white, self.primaries, self.upsample, self.siting)
-
-    def field(self, parity, layout="interleaved"):
-        """one field of interlaced frames: a PackedYuvFrames over the surface's rows of field `parity`
-        (field_rows), every other parameter kept"""
-        return PackedYuvFrames(self.y[:, field_rows(self.y.shape[1], parity, layout)], self.name, self.shape[2], self.matrix,
-                               self.full_range, self.bits, self.msb_aligned, self.transfer, self.peak_nits, self.sdr_white,
-                               self.primaries, self.upsample, self.siting)
+    def _over(self, cut):
+        return PackedYuvFrames(cut(self.y), self.name, self.shape[2], **self.colour())
 
     def planes(self):
         """the read set as ONE view: data [T0, H, the words of ceil(W / P) groups] - the pitch padding cut off"""
@@ -603,9 +617,7 @@ class PackedYuvFrames(YuvFrames):
         """ONE tdc_yuv_packed_to_rgb launch: the frames of `planes` (the device surface laid out like planes()) -> out uint8
         [T, H, W, 3]; transfer "pq" / "hlg" passes the descriptor, its table taken from (and made once for) the surface's device"""
         H, W = self.shape[1:3]
-        hdr = None
-        if self.hdr is not None:
-            hdr = dict(self.hdr, lut=hdr_lut(self.transfer, self.bits, self.peak_nits, self.sdr_white, planes[0].device))
+        hdr = self.hdr_on(planes[0].device)
         if self.interpolates:       # ONE tdc_yuv_packed_linear_to_rgb launch in its place (DESIGN.md section 26)
             return ops.yuv_packed_linear_to_rgb(planes[0], self.fmt, self.coef, H, W, self.bits, self.msb_aligned,
                                                 CHROMA_SITES[self.siting], hdr=hdr, out=out)
@@ -655,39 +667,6 @@ def selected_planes(yuv, idx, device):
         out.append(dev[at:at + p.numel()].view(p.shape))
         at += p.numel()
     return out, stage.numel() * stage.element_size()
-
-
-def _preprocess_selected_yuv(yuv, idx, towers, dtype, slab, device, out, stats):
-    """preprocess_selected for a YuvFrames: per slab of kept frames ONE conversion launch (YuvFrames.to_rgb: tdc_yuv420_to_rgb
-    for 8-bit 4:2:0, tdc_yuv_to_rgb for every other planar kind, tdc_yuv_packed_to_rgb for a packed surface; with upsample="linear" tdc_yuv_linear_to_rgb / tdc_yuv_packed_linear_to_rgb in their place) into a [slab, H, W, 3] RGB scratch, then tdc_preprocess_frames per tower on that scratch - the RGB path's launches on the frames the planes convert
-    to.  Both scratches are slab-sized and serve the whole video."""
-    idx = check_indices(idx, yuv.shape[0])
-    _check_dtype_slab(dtype, slab)
-    if device is None:
-        device = yuv.y.device if yuv.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    T0, H, W, _ = yuv.shape
-    planes, uploaded = selected_planes(yuv, idx, device)
-    T = planes[0].shape[0]
-    if stats is not None:
-        stats.update(frames_in=T0, frames_resized=T, bytes_uploaded=uploaded)
-    out = _outputs(out, towers, T, dtype, device)
-    lib = L.load()
-    n0 = min(slab, T)
-    nscr = max(lib.tdc_preprocess_scratch_bytes(n0, H, W, t["R"]) for t in towers)
-    scratch = torch.empty(max(nscr, 1), dtype=torch.uint8, device=device)
-    rgb = torch.empty((n0, H, W, 3), dtype=torch.uint8, device=device)
-    tables = [_tables(max(H, W), t["R"], t["mean"], t["std"], device) for t in towers]
-    with torch.cuda.device(device):
-        for s in range(0, T, slab):
-            n = min(slab, T - s)
-            yuv.to_rgb([p[s:s + n] for p in planes], rgb[:n])
-            for t, o, (bounds, coeffs, lut) in zip(towers, out, tables):
-                pad = [int(x * 255) for x in t["mean"]]   # expand2square background (tdc/mm_datautils.py:302-304)
-                L.check(lib.tdc_preprocess_frames(ops._ptr(rgb), n, H, W, t["R"], ops._ptr(bounds), ops._ptr(coeffs),
-                                                  coeffs.shape[1], pad[0], pad[1], pad[2], ops._ptr(lut), ops._ptr(o[s:s + n]), 0,
-                                                  ops._dtcode(dtype), ops._ptr(scratch), ops._stream()), "tdc_preprocess_frames")
-    return [o[:T] for o in out]
 
 
 # ---- channel-first, BGR, RGBA and gray frames (DESIGN.md section 24) -------------------------------------------------------
@@ -865,42 +844,6 @@ def selected_pixels(rgb, idx, device):
     return RgbFrames(dev if rgb.layout == "hwc" else dev.permute(1, 0, 2, 3), staged.layout, staged.order), stage.numel()
 
 
-def _preprocess_selected_rgb(rgb, idx, towers, dtype, slab, device, out, stats):
-    """preprocess_selected for an RgbFrames.  [T0, H, W, 3] in R, G, B order issues exactly the launches of the wrapped tensor.
-    Otherwise per slab of kept frames ONE tdc_pack_rgb launch into a [slab, H, W, 3] scratch, then tdc_preprocess_frames per
-    tower on that scratch - the RGB path's launches on the frames the source stands for.  A slab is packed once and both
-    towers read it.  Both scratches are slab-sized and serve the whole video."""
-    if rgb.is_identity:
-        return preprocess_selected(rgb.data, idx, towers, dtype, slab, device, out, stats)
-    idx = check_indices(idx, rgb.shape[0])
-    _check_dtype_slab(dtype, slab)
-    if device is None:
-        device = rgb.device if rgb.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    T0, H, W, _ = rgb.shape
-    kept, uploaded = selected_pixels(rgb, idx, device)
-    T = kept.shape[0]
-    if stats is not None:
-        stats.update(frames_in=T0, frames_resized=T, bytes_uploaded=uploaded)
-    out = _outputs(out, towers, T, dtype, device)
-    lib = L.load()
-    n0 = min(slab, T)
-    nscr = max(lib.tdc_preprocess_scratch_bytes(n0, H, W, t["R"]) for t in towers)
-    scratch = torch.empty(max(nscr, 1), dtype=torch.uint8, device=device)
-    packed = torch.empty((n0, H, W, 3), dtype=torch.uint8, device=device)
-    tables = [_tables(max(H, W), t["R"], t["mean"], t["std"], device) for t in towers]
-    with torch.cuda.device(device):
-        for s in range(0, T, slab):
-            n = min(slab, T - s)
-            kept[s:s + n].pack(packed[:n])
-            for t, o, (bounds, coeffs, lut) in zip(towers, out, tables):
-                pad = [int(x * 255) for x in t["mean"]]   # expand2square background (tdc/mm_datautils.py:302-304)
-                L.check(lib.tdc_preprocess_frames(ops._ptr(packed), n, H, W, t["R"], ops._ptr(bounds), ops._ptr(coeffs),
-                                                  coeffs.shape[1], pad[0], pad[1], pad[2], ops._ptr(lut), ops._ptr(o[s:s + n]), 0,
-                                                  ops._dtcode(dtype), ops._ptr(scratch), ops._stream()), "tdc_preprocess_frames")
-    return [o[:T] for o in out]
-
-
 # ---- display orientation (DESIGN.md section 23) ---------------------------------------------------------------------------
 ROTATIONS = (0, 90, 180, 270)
 # EXIF orientation -> (rotate, hflip): the clockwise turn that makes the stored picture upright, then a left-right mirror
@@ -958,62 +901,6 @@ class Oriented:
 def is_oriented(x):
     """an Oriented, recognised by its members (the package can be imported under two names: not by isinstance)"""
     return all(hasattr(x, k) for k in ("frames", "rotate", "hflip", "quarters", "shape")) and not torch.is_tensor(x)
-
-
-def _preprocess_selected_oriented(o, idx, towers, dtype, slab, device, out, stats):
-    """preprocess_selected for an Oriented.  The identity issues exactly the launches of the wrapped frames.  Otherwise a1's
-    frames, or planes, are uploaded as the wrapped frames' are, and per slab of kept frames: YUV planes are converted, and an
-    RgbFrames is packed, by their one launch into a [slab, H, W, 3] scratch, ONE tdc_orient_frames launch writes the upright frames into a [slab, H', W', 3]
-    scratch, and tdc_preprocess_frames runs per tower on that scratch - the RGB path's launches on the upright frames.  A slab
-    is turned once and both towers read it.  The scratches are slab-sized and serve the whole video."""
-    inner = o.frames
-    if o.is_identity:
-        return preprocess_selected(inner, idx, towers, dtype, slab, device, out, stats)
-    if is_interlaced(inner):        # the field is rebuilt first, then the frame is turned (DESIGN.md section 27)
-        return _preprocess_selected_interlaced(inner, idx, towers, dtype, slab, device, out, stats, orient=o)
-    if is_rgb_frames(inner) and inner.is_identity:
-        inner = inner.data
-    yuv, packs = is_yuv_frames(inner), is_rgb_frames(inner)
-    idx = check_indices(idx, o.shape[0])
-    _check_dtype_slab(dtype, slab)
-    if device is None:
-        device = (inner.y.device if yuv else inner.device) if inner.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    T0, H, W, _ = inner.shape
-    Ho, Wo = o.shape[1:3]
-    if yuv:
-        planes, uploaded = selected_planes(inner, idx, device)
-        T = planes[0].shape[0]
-    elif packs:
-        kept, uploaded = selected_pixels(inner, idx, device)
-        T = kept.shape[0]
-    else:
-        kept, uploaded = selected_frames(inner, idx, device)
-        T = kept.shape[0]
-    if stats is not None:
-        stats.update(frames_in=T0, frames_resized=T, bytes_uploaded=uploaded)
-    out = _outputs(out, towers, T, dtype, device)
-    lib = L.load()
-    n0 = min(slab, T)
-    nscr = max(lib.tdc_preprocess_scratch_bytes(n0, Ho, Wo, t["R"]) for t in towers)
-    scratch = torch.empty(max(nscr, 1), dtype=torch.uint8, device=device)
-    rgb = torch.empty((n0, H, W, 3), dtype=torch.uint8, device=device) if yuv or packs else None
-    upright = torch.empty((n0, Ho, Wo, 3), dtype=torch.uint8, device=device)
-    tables = [_tables(max(Ho, Wo), t["R"], t["mean"], t["std"], device) for t in towers]
-    with torch.cuda.device(device):
-        for s in range(0, T, slab):
-            n = min(slab, T - s)
-            if yuv:
-                inner.to_rgb([p[s:s + n] for p in planes], rgb[:n])
-            elif packs:
-                kept[s:s + n].pack(rgb[:n])
-            ops.orient_frames(rgb[:n] if yuv or packs else kept[s:s + n], o.quarters, o.hflip, out=upright[:n])
-            for t, dst, (bounds, coeffs, lut) in zip(towers, out, tables):
-                pad = [int(x * 255) for x in t["mean"]]   # expand2square background (tdc/mm_datautils.py:302-304)
-                L.check(lib.tdc_preprocess_frames(ops._ptr(upright), n, Ho, Wo, t["R"], ops._ptr(bounds), ops._ptr(coeffs),
-                                                  coeffs.shape[1], pad[0], pad[1], pad[2], ops._ptr(lut), ops._ptr(dst[s:s + n]), 0,
-                                                  ops._dtcode(dtype), ops._ptr(scratch), ops._stream()), "tdc_preprocess_frames")
-    return [dst[:T] for dst in out]
 
 
 # ---- interlaced video: one field rebuilt to full height (DESIGN.md section 27) ---------------------------------------------
@@ -1118,63 +1005,6 @@ def selected_field(field, idx, device):
     return stage.to(device, non_blocking=True), stage.numel()
 
 
-def _preprocess_selected_interlaced(it, idx, towers, dtype, slab, device, out, stats, orient=None):
-    """preprocess_selected for an Interlaced, bare or inside the non-identity Oriented `orient`.  a1's frames are uploaded as
-    the kept FIELD of the wrapped frames is - half the bytes - and per slab of kept frames: the field of YUV planes is
-    converted, and the field of an RgbFrames is packed, by their one launch (whatever launch that surface issues on a
-    half-height picture) into a [slab, H / 2, W, 3] scratch; plain uint8 frames' field is read where it lies.  ONE
-    tdc_field_to_frame launch then writes the rebuilt frames into a [slab, H, W, 3] scratch, tdc_orient_frames turns them when
-    `orient` is given, and tdc_preprocess_frames runs per tower on the result - the RGB path's launches on the rebuilt frames.
-    A slab is rebuilt once and both towers read it.  The scratches are slab-sized and serve the whole video."""
-    inner = it.field_frames()
-    if is_rgb_frames(inner) and inner.is_identity:
-        inner = inner.data
-    yuv, packs = is_yuv_frames(inner), is_rgb_frames(inner)
-    idx = check_indices(idx, it.shape[0])
-    _check_dtype_slab(dtype, slab)
-    if device is None:
-        device = (inner.y.device if yuv else inner.device) if inner.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    T0, H, W, _ = it.shape
-    Ho, Wo = (H, W) if orient is None else orient.shape[1:3]
-    if yuv:
-        planes, uploaded = selected_planes(inner, idx, device)
-        T = planes[0].shape[0]
-    elif packs:
-        kept, uploaded = selected_pixels(inner, idx, device)
-        T = kept.shape[0]
-    else:
-        kept, uploaded = selected_field(inner, idx, device)
-        T = kept.shape[0]
-    if stats is not None:
-        stats.update(frames_in=T0, frames_resized=T, bytes_uploaded=uploaded)
-    out = _outputs(out, towers, T, dtype, device)
-    lib = L.load()
-    n0 = min(slab, T)
-    nscr = max(lib.tdc_preprocess_scratch_bytes(n0, Ho, Wo, t["R"]) for t in towers)
-    scratch = torch.empty(max(nscr, 1), dtype=torch.uint8, device=device)
-    rgb = torch.empty((n0, H // 2, W, 3), dtype=torch.uint8, device=device) if yuv or packs else None
-    rebuilt = torch.empty((n0, H, W, 3), dtype=torch.uint8, device=device)
-    upright = torch.empty((n0, Ho, Wo, 3), dtype=torch.uint8, device=device) if orient is not None else rebuilt
-    tables = [_tables(max(Ho, Wo), t["R"], t["mean"], t["std"], device) for t in towers]
-    with torch.cuda.device(device):
-        for s in range(0, T, slab):
-            n = min(slab, T - s)
-            if yuv:
-                inner.to_rgb([p[s:s + n] for p in planes], rgb[:n])
-            elif packs:
-                kept[s:s + n].pack(rgb[:n])
-            ops.field_to_frame(rgb[:n] if yuv or packs else kept[s:s + n], it.parity, it.fill, out=rebuilt[:n])
-            if orient is not None:
-                ops.orient_frames(rebuilt[:n], orient.quarters, orient.hflip, out=upright[:n])
-            for t, dst, (bounds, coeffs, lut) in zip(towers, out, tables):
-                pad = [int(x * 255) for x in t["mean"]]   # expand2square background (tdc/mm_datautils.py:302-304)
-                L.check(lib.tdc_preprocess_frames(ops._ptr(upright), n, Ho, Wo, t["R"], ops._ptr(bounds), ops._ptr(coeffs),
-                                                  coeffs.shape[1], pad[0], pad[1], pad[2], ops._ptr(lut), ops._ptr(dst[s:s + n]), 0,
-                                                  ops._dtcode(dtype), ops._ptr(scratch), ops._stream()), "tdc_preprocess_frames")
-    return [dst[:T] for dst in out]
-
-
 def _check_dtype_slab(dtype, slab):
     if dtype not in (torch.float16, torch.bfloat16):
         raise ValueError("preprocess_selected writes float16 or bfloat16 pixels, got %s" % (dtype,))
@@ -1215,39 +1045,86 @@ def preprocess_selected(frames, idx, towers=(SIGLIP, DINOV2), dtype=torch.float1
     is what the [T0, H, W, 3] frames Pillow's .convert("RGB") makes of them give.
     frames may be an Interlaced over any of these kinds (an Oriented may hold one): only the kept field
     is uploaded, converted or packed, and the full-height frames are rebuilt from it on the device, one tdc_field_to_frame
-    launch per slab, in front of the same resize - the result is what the frames a host rebuilds by the stated formula give."""
-    if is_oriented(frames):
-        return _preprocess_selected_oriented(frames, idx, towers, dtype, slab, device, out, stats)
-    if is_interlaced(frames):
-        return _preprocess_selected_interlaced(frames, idx, towers, dtype, slab, device, out, stats)
-    if is_rgb_frames(frames):
-        return _preprocess_selected_rgb(frames, idx, towers, dtype, slab, device, out, stats)
-    if is_yuv_frames(frames):
-        return _preprocess_selected_yuv(frames, idx, towers, dtype, slab, device, out, stats)
-    frames = check_frames(frames)
-    idx = check_indices(idx, frames.shape[0])       # on the host, before anything is launched
+    launch per slab, in front of the same resize - the result is what the frames a host rebuilds by the stated formula give.
+    The launches, for every kind (_plan): the kept frames - of an Interlaced only their kept field, half the bytes - are uploaded
+    as their innermost kind is, and per slab of kept frames the stages that apply run in the order
+        convert or pack -> rebuild -> turn -> resize
+    each ONE launch into a slab-sized uint8 [slab, H, W, 3] scratch of its own that serves the whole video: YuvFrames.to_rgb
+    (tdc_yuv420_to_rgb for 8-bit 4:2:0, tdc_yuv_to_rgb for every other planar kind, tdc_yuv_hdr_to_rgb under pq / hlg,
+    tdc_yuv_packed_to_rgb for a packed surface; with upsample "linear" tdc_yuv_linear_to_rgb / tdc_yuv_packed_linear_to_rgb in
+    their place) or RgbFrames.pack (tdc_pack_rgb) at the stored size, of a field at H / 2; tdc_field_to_frame to [H, W];
+    tdc_orient_frames to the upright [H', W']; then tdc_preprocess_frames per tower on the last scratch - the RGB path's
+    launches on the frames the source stands for.  A slab is made once and every tower reads it.  Plain uint8 frames, an RgbFrames
+    that is [T0, H, W, 3] in R, G, B order and an identity Oriented over either have no stage and issue exactly the launches of
+    the tensor; the kept field of such frames is read where it lies by tdc_field_to_frame."""
+    source, upload, stages = _plan(frames)
+    T0 = source.shape[0]                            # a wrapper keeps every frame of what it wraps
+    idx = check_indices(idx, T0)                    # on the host, before anything is uploaded or launched
     _check_dtype_slab(dtype, slab)
     if device is None:
-        device = frames.device if frames.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        device = source.device if source.is_cuda else torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
-    T0, H, W, _ = frames.shape
-    kept, uploaded = selected_frames(frames, idx, device)
-    T = kept.shape[0]
+    kept, uploaded = upload(source, idx, device)
+    planar = isinstance(kept, list)                 # selected_planes: the planes of the kept frames, each [T, rows, samples]
+    T = (kept[0] if planar else kept).shape[0]
     if stats is not None:
         stats.update(frames_in=T0, frames_resized=T, bytes_uploaded=uploaded)
     out = _outputs(out, towers, T, dtype, device)
     lib = L.load()
     n0 = min(slab, T)
-    nscr = max(lib.tdc_preprocess_scratch_bytes(n0, H, W, t["R"]) for t in towers)
+    Ho, Wo = stages[-1][0] if stages else source.shape[1:3]
+    nscr = max(lib.tdc_preprocess_scratch_bytes(n0, Ho, Wo, t["R"]) for t in towers)
     scratch = torch.empty(max(nscr, 1), dtype=torch.uint8, device=device)
+    made = [torch.empty((n0, H, W, 3), dtype=torch.uint8, device=device) for (H, W), _ in stages]
+    tables = [_tables(max(Ho, Wo), t["R"], t["mean"], t["std"], device) for t in towers]
+    slabs = [(s, min(slab, T - s)) for s in range(0, T, slab)]
     with torch.cuda.device(device):
-        for t, o in zip(towers, out):
-            R = t["R"]
-            bounds, coeffs, lut = _tables(max(H, W), R, t["mean"], t["std"], device)
-            pad = [int(x * 255) for x in t["mean"]]   # expand2square background (tdc/mm_datautils.py:302-304)
-            for s in range(0, T, slab):
-                n = min(slab, T - s)
-                L.check(lib.tdc_preprocess_frames(ops._ptr(kept[s:s + n]), n, H, W, R, ops._ptr(bounds), ops._ptr(coeffs),
-                                                  coeffs.shape[1], pad[0], pad[1], pad[2], ops._ptr(lut), ops._ptr(o[s:s + n]), 0,
-                                                  ops._dtcode(dtype), ops._ptr(scratch), ops._stream()), "tdc_preprocess_frames")
+        if not stages:
+            # nothing to make per slab, so the frames are resized where the upload left them, tower by tower: all slabs of the
+            # first tower, then all of the next.  With stages a slab is made once and every tower reads it before the next slab
+            # overwrites the scratches, so the loop is slab by slab (tests/test_hip_orient_inputs.py holds both orders).
+            for t, o, tab in zip(towers, out, tables):
+                for s, n in slabs:
+                    _resize(kept[s:s + n], n, Ho, Wo, t, tab, o[s:s + n], dtype, scratch)
+        else:
+            for s, n in slabs:
+                x = [p[s:s + n] for p in kept] if planar else kept[s:s + n]
+                for (_, run), buf in zip(stages, made):
+                    run(x, buf[:n])
+                    x = buf[:n]
+                for t, o, tab in zip(towers, out, tables):
+                    _resize(x, n, Ho, Wo, t, tab, o[s:s + n], dtype, scratch)
     return [o[:T] for o in out]
+
+
+def _plan(frames):
+    """what preprocess_selected does for `frames`, found once -> (source, upload, stages).  The wrappers are peeled in their one
+    nesting order, Oriented(Interlaced(kind)): an Oriented that turns or mirrors gives the turn stage (the identity gives
+    none), an Interlaced replaces the kind by the view of its kept field and gives the rebuild stage, and an RgbFrames that is
+    [T0, H, W, 3] in R, G, B order already stands for its tensor.  `source` is the innermost kind and upload(source, idx,
+    device) its kept frames on the device: selected_frames for a tensor (selected_field for the kept field of one),
+    selected_planes for a YuvFrames, planar or packed, whose front stage is its to_rgb, selected_pixels for any other
+    RgbFrames, whose front stage is its pack.  A stage is ((H, W), run): run(x, made) issues ONE launch from x, the slab the
+    stage before it made or the slab of the upload, into made, a uint8 [n, H, W, 3] scratch."""
+    turn = rebuild = None
+    if is_oriented(frames):
+        turn, frames = (None if frames.is_identity else frames), frames.frames
+    if is_interlaced(frames):
+        rebuild, frames = frames, frames.field_frames()
+    if is_rgb_frames(frames) and frames.is_identity:
+        frames = frames.data
+    stages = []
+    if is_yuv_frames(frames):
+        upload = selected_planes
+        stages.append((frames.shape[1:3], frames.to_rgb))
+    elif is_rgb_frames(frames):
+        upload = selected_pixels
+        stages.append((frames.shape[1:3], lambda kept, made: kept.pack(made)))
+    else:
+        frames = check_frames(frames)
+        upload = selected_frames if rebuild is None else selected_field
+    if rebuild is not None:
+        stages.append((rebuild.shape[1:3], lambda x, made: ops.field_to_frame(x, rebuild.parity, rebuild.fill, out=made)))
+    if turn is not None:
+        stages.append((turn.shape[1:3], lambda x, made: ops.orient_frames(x, turn.quarters, turn.hflip, out=made)))
+    return frames, upload, stages
