@@ -540,6 +540,8 @@ int tdc_preprocess_frames(const unsigned char* frames, int T, int H, int W, int 
  *     G = clip8((cy*Y' - cgu*Cb - cgv*Cr + 32768) >> 16)
  *     B = clip8((cy*Y' + cbu*Cb          + 32768) >> 16)
  * The coefficients are the host's: floor(real * 65536 + 0.5) of the matrix and range it chose (preprocess.yuv_coefficients).
+ * This entry is tdc_yuv_to_rgb (below) at bits = 8, 4:2:0: the same refusals, the same choice of form and the same grid,
+ * in front of a kernel written out for bytes.
  * One kernel serves every layout through the two chroma pointers and c_step; the host picks its 8-pixel vector form when W,
  * the pointers, the pitches and the frame strides are multiples of the access widths (8 bytes luma and rgb; chroma 4 bytes
  * each planar, or 8 bytes at the lower pointer when u and v are neighbours), its 2 x 2 byte form otherwise: same bytes.

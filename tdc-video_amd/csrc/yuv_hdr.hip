@@ -22,11 +22,10 @@ __global__ __launch_bounds__(256) void yuv_hdr_to_rgb_kernel(tdc_yuv_planes p, t
 template <int SUBX>
 void launch(const yuv_launch& l, hipStream_t st, const tdc_yuv_planes& p, const tdc_yuv_coef& c, const tdc_hdr_desc& h, int T, int H,
             int W, unsigned char* rgb) {
-    const dim3 block(256);
-    const size_t lds = sizeof(float) << p.bits;
-    if (l.form == WORD) hipLaunchKernelGGL((yuv_hdr_to_rgb_kernel<SUBX, WORD>), l.grid, block, lds, st, p, c, h, T, H, W, l.units_x, 0, rgb);
-    else if (l.form == VEC_PLANAR) hipLaunchKernelGGL((yuv_hdr_to_rgb_kernel<SUBX, VEC_PLANAR>), l.grid, block, lds, st, p, c, h, T, H, W, l.units_x, 0, rgb);
-    else hipLaunchKernelGGL((yuv_hdr_to_rgb_kernel<SUBX, VEC_PAIRED>), l.grid, block, lds, st, p, c, h, T, H, W, l.units_x, l.u_is_high, rgb);
+    with_form(l.form, [&](auto form) {
+        hipLaunchKernelGGL((yuv_hdr_to_rgb_kernel<SUBX, decltype(form)::value>), l.grid, dim3(256), sizeof(float) << p.bits, st, p, c, h, T,
+                           H, W, l.units_x, l.u_is_high, rgb);
+    });
 }
 
 }  // namespace

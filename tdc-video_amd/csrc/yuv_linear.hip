@@ -20,26 +20,7 @@ __device__ __forceinline__ void chroma_row(const tdc_yuv_planes& p, const unsign
                                            int (&hu)[FORM == WORD ? 2 : 8], int (&hv)[FORM == WORD ? 2 : 8]) {
     constexpr int NC = FORM == WORD ? 1 : 4;
     int su[NC + 2], sv[NC + 2];
-    if constexpr (FORM == WORD) {
-        const long long coff = crow + (long long)xu * p.c_step;
-        su[1] = sample_at<BS>(uf + coff, d);
-        sv[1] = sample_at<BS>(vf + coff, d);
-    } else if constexpr (FORM == VEC_PLANAR) {
-        unsigned uw[NC * BS / 4], vw[NC * BS / 4];
-        load_words<NC * BS>(uf + crow + (long long)xu * (NC * BS), uw);
-        load_words<NC * BS>(vf + crow + (long long)xu * (NC * BS), vw);
-#pragma unroll
-        for (int k = 0; k < NC; ++k) { su[1 + k] = sample<BS>(uw, k, d); sv[1 + k] = sample<BS>(vw, k, d); }
-    } else {            // NC pairs at the lower pointer; u_is_high: the pairs are (v, u)
-        unsigned pw[2 * NC * BS / 4];
-        load_words<2 * NC * BS>((u_is_high ? vf : uf) + crow + (long long)xu * (2 * NC * BS), pw);
-#pragma unroll
-        for (int k = 0; k < NC; ++k) {
-            const int first = sample<BS>(pw, 2 * k, d), second = sample<BS>(pw, 2 * k + 1, d);
-            su[1 + k] = u_is_high ? second : first;
-            sv[1 + k] = u_is_high ? first : second;
-        }
-    }
+    chroma_run<BS, NC, FORM>(p, uf, vf, crow, xu, d, u_is_high, su + 1, sv + 1);
     // the halo: by index on the picture's own Wc, never past the row's read set
     const int k0 = xu * NC;
     su[0] = sv[0] = 0;
@@ -55,68 +36,39 @@ __device__ __forceinline__ void chroma_row(const tdc_yuv_planes& p, const unsign
     horizontal_sums<NC>(sv, wx, hv);
 }
 
-// grid, units and ownership: yuv_frames' (yuv_samples.h), sub_x = 1.  Every index is derived from T, H, W and the strides
-// the host has checked against them; a neighbour's index is clamped to [0, Wc - 1] / [0, Hc - 1] of the frame t itself.
+// the walk, the units and the stores are yuv_frames' (yuv_samples.h) at sub_x = 1, with a chroma term per pixel.  A
+// neighbour's index is clamped to [0, Wc - 1] / [0, Hc - 1] of the frame t itself.
 template <int BS, int FORM, class PX>
 __device__ __forceinline__ void yuv_linear_frames(const tdc_yuv_planes& p, const tdc_yuv_coef& c, const depth& d, const PX& px,
                                                   const tdc_chroma_site& s, int T, int H, int W, int units_x, int u_is_high,
                                                   unsigned char* rgb) {
     constexpr int NP = FORM == WORD ? 2 : 8;        // pixels of a unit's row
-    const int suby = p.sub_y;
-    const int Hc = (H + suby) >> suby, Wc = (W + 1) >> 1;
-    const axis_taps wx = axis_taps_of(s.sit_x, 1), wy = axis_taps_of(s.sit_y, suby);
-    const long long units = (long long)units_x * Hc;     // < 2^32: units_x and Hc are at most 65535
-    for (int t = blockIdx.y; t < T; t += gridDim.y) {
-        const unsigned char* yf = p.y + (long long)t * p.y_frame;
-        const unsigned char* uf = p.u + (long long)t * p.c_frame;
-        const unsigned char* vf = p.v + (long long)t * p.c_frame;
-        unsigned char* of = rgb + (long long)t * H * W * 3;
-        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < units; i += (long long)gridDim.x * 256) {
-            const unsigned yc_ = (unsigned)i / (unsigned)units_x;     // i < 2^32: a 32-bit division
-            const int yc = (int)yc_, xu = (int)((unsigned)i - yc_ * (unsigned)units_x);
-            const int y0 = yc << suby;
-            const bool two_rows = suby && y0 + 1 < H;   // 4:2:0 with odd H: the last block has one row
-            const unsigned char* yr = yf + (long long)y0 * p.y_pitch;
-            unsigned char* orow = of + (long long)y0 * W * 3;
+    const int Hc = (H + p.sub_y) >> p.sub_y, Wc = (W + 1) >> 1;
+    const axis_taps wx = axis_taps_of(s.sit_x, 1), wy = axis_taps_of(s.sit_y, p.sub_y);
+    const long long units = yuv_units(p, H, units_x);
+    for (int t = blockIdx.y; t < T; t += gridDim.y)
+        for (long long i = first_unit(); i < units; i += unit_stride()) {
+            const yuv_unit n = yuv_unit_of(p, t, i, units_x, H, W, rgb);
             int hu[NP], hv[NP];                         // the unit's own chroma row
-            chroma_row<BS, FORM>(p, uf, vf, (long long)yc * p.c_pitch, xu, Wc, d, u_is_high, wx, hu, hv);
+            chroma_row<BS, FORM>(p, n.uf, n.vf, (long long)n.yc * p.c_pitch, n.xu, Wc, d, u_is_high, wx, hu, hv);
 #pragma unroll
             for (int dy = 0; dy < 2; ++dy) {
-                if (dy == 1 && !two_rows) break;
+                if (dy == 1 && !n.two_rows) break;
                 const int wa = dy ? wy.oa : wy.ea, wb = dy ? wy.ob : wy.eb;
                 int gu[NP], gv[NP];                     // the other chroma row of this pixel row: above (dy = 0) or below
 #pragma unroll
                 for (int k = 0; k < NP; ++k) gu[k] = gv[k] = 0;
                 if (wb) {       // uniform
-                    const int ro = dy ? (yc + 1 < Hc ? yc + 1 : Hc - 1) : (yc > 0 ? yc - 1 : 0);
-                    chroma_row<BS, FORM>(p, uf, vf, (long long)ro * p.c_pitch, xu, Wc, d, u_is_high, wx, gu, gv);
+                    const int ro = dy ? (n.yc + 1 < Hc ? n.yc + 1 : Hc - 1) : (n.yc > 0 ? n.yc - 1 : 0);
+                    chroma_row<BS, FORM>(p, n.uf, n.vf, (long long)ro * p.c_pitch, n.xu, Wc, d, u_is_high, wx, gu, gv);
                 }
                 chroma_terms ct[NP];
 #pragma unroll
                 for (int k = 0; k < NP; ++k)
                     ct[k] = chroma(c, d, interpolated(wa, hu[k], wb, gu[k]), interpolated(wa, hv[k], wb, gv[k]));
-                if constexpr (FORM == WORD) {
-                    const int x0 = xu << 1;
-#pragma unroll
-                    for (int dx = 0; dx < 2; ++dx) {
-                        if (dx == 1 && x0 + 1 >= W) break;      // odd W: the last column has one pixel
-                        const int yy = c.cy * (sample_at<BS>(yr + (long long)dy * p.y_pitch + (long long)(x0 + dx) * BS, d) - c.y_off);
-                        unsigned char* o = orow + ((long long)dy * W + x0 + dx) * 3;
-                        unsigned r, g, b;
-                        px(d, yy + ct[dx].r, yy + ct[dx].g, yy + ct[dx].b, r, g, b);
-                        o[0] = (unsigned char)r; o[1] = (unsigned char)g; o[2] = (unsigned char)b;
-                    }
-                } else {
-                    unsigned lw[2 * BS];
-                    uint2 o[3];
-                    load_words<8 * BS>(yr + (long long)dy * p.y_pitch + (long long)xu * (8 * BS), lw);
-                    row8<BS, 0>(c, d, px, lw, ct, o);
-                    uint2* dst = reinterpret_cast<uint2*>(orow + (long long)dy * W * 3 + 24ll * xu);
-                    dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
-                }
+                emit_row<BS, 0, FORM, 2>(c, d, px, n.yr + (long long)dy * p.y_pitch, n.orow + (long long)dy * W * 3, n.xu, W, ct);
             }
         }
-    }
 }
 
 template <int BS, int FORM>
@@ -150,9 +102,7 @@ void launch_form(const yuv_launch& l, hipStream_t st, const tdc_yuv_planes& p, c
 template <int BS>
 void launch(const yuv_launch& l, hipStream_t st, const tdc_yuv_planes& p, const tdc_yuv_coef& c, const tdc_hdr_desc* h,
             const tdc_chroma_site& s, int T, int H, int W, unsigned char* rgb) {
-    if (l.form == WORD) launch_form<BS, WORD>(l, st, p, c, h, s, T, H, W, rgb);
-    else if (l.form == VEC_PLANAR) launch_form<BS, VEC_PLANAR>(l, st, p, c, h, s, T, H, W, rgb);
-    else launch_form<BS, VEC_PAIRED>(l, st, p, c, h, s, T, H, W, rgb);
+    with_form(l.form, [&](auto form) { launch_form<BS, decltype(form)::value>(l, st, p, c, h, s, T, H, W, rgb); });
 }
 
 }  // namespace

@@ -9,8 +9,10 @@
 //             a multiple of 8 but not of 24 ends in one or two units of one group (one 16-byte load, byte stores)
 // chosen on the host from alignment facts alone.  Bits outside a sample are masked off before anything else sees them; every
 // form gives the same bytes.
-// The linear kernels at the end (tdc_yuv_packed_linear_to_rgb) are the 4:2:2 families with interpolated
-// chroma: same units, same loads and stores, plus the chroma pair left (centred siting) and right of the unit's run.
+// tdc_yuv_packed_linear_to_rgb is the 4:2:2 families with interpolated chroma.  ONE walk (packed_frames),
+// ONE load of a unit's words (load_unit), ONE set of kernels and ONE pair of launchers serve both entries; what a unit is is a
+// functor: `replicated` (packed_unit), or `interpolated_x` (packed_linear_unit: the chroma pair left (centred siting) and right
+// of the unit's run as well).  The replicate kernels do not pass through the interpolation: their chroma loads are fewer.
 #include "yuv_linear.h"
 #include "yuv_pixels.h"
 
@@ -93,9 +95,38 @@ __device__ __forceinline__ void group_samples(const unsigned (&w)[fam_gw(FAM)], 
     }
 }
 
-// one unit of one row: NG whole groups from src (WIDE: in 16-byte loads from a 16-byte-aligned address; else sample by sample)
-// -> the pixels x0 .. x0 + NG * P - 1 of the row at orow.  Units of a multiple of eight pixels are stored as 8-byte words
-// (their first byte on an 8-byte boundary), the others byte by byte and only below W.
+// interpolated chroma, the 4:2:2 families: chroma pair k of a row, as single-sample loads (v210: the words that hold it;
+// R = k % 3, its place in the group)
+template <int FAM, int R>
+__device__ __forceinline__ void pair_at(const unsigned char* srow, int k, const packed_lay& l, const depth& d, int& u, int& v) {
+    if constexpr (FAM == F422_8) {
+        const unsigned char* g = srow + 4ll * k;
+        u = (int)g[l.u]; v = (int)g[l.v];
+    } else if constexpr (FAM == F422_16) {
+        const unsigned char* g = srow + 8ll * k;
+        u = sample_at<2>(g + 2 * l.u, d); v = sample_at<2>(g + 2 * l.v, d);
+    } else {
+        const unsigned* g = reinterpret_cast<const unsigned*>(srow) + 4ll * (k / 3);
+        if constexpr (R == 0) { const unsigned w = g[0]; u = (int)(w & 1023u); v = (int)(w >> 20 & 1023u); }
+        else { u = (int)(g[2] >> 20 & 1023u); v = (int)(g[3] >> 10 & 1023u); }
+    }
+}
+
+// the words of a unit, NG whole groups at src: WIDE in 16-byte loads from a 16-byte-aligned address, else sample by sample
+template <int FAM, int NG, bool WIDE>
+__device__ __forceinline__ void load_unit(const unsigned char* src, unsigned (&all)[NG * fam_gw(FAM)]) {
+    if constexpr (WIDE) {
+        load_words<NG * fam_gw(FAM) * 4>(src, all);
+    } else {
+        static_assert(NG == 1, "sample-sized loads take one group");
+        load_group<FAM>(src, all);
+    }
+}
+
+// one unit of one row: NG whole groups from src -> the pixels x0 .. x0 + NG * P - 1 of the row at orow.  Units of a multiple of
+// eight pixels are stored as 8-byte words (their first byte on an 8-byte boundary), the others byte by byte and only below W.
+// The store is written out here and in packed_linear_unit: as a function of its own it changed the instructions of six of
+// the replicate kernels, Y210's vector form among them (profiles/yuv_kernel_family.json).
 template <int FAM, int NG, bool WIDE, class PX>
 __device__ __forceinline__ void packed_unit(const unsigned char* src, unsigned char* orow, int x0, int W, const packed_lay& l,
                                             const tdc_yuv_coef& c, const depth& d, const PX& px) {
@@ -104,12 +135,7 @@ __device__ __forceinline__ void packed_unit(const unsigned char* src, unsigned c
     constexpr bool PACK = NPIX % 8 == 0;
     constexpr int CH = PACK ? 8 : NPIX;
     unsigned all[NG * GW];
-    if constexpr (WIDE) {
-        load_words<NG * GW * 4>(src, all);
-    } else {
-        static_assert(NG == 1, "sample-sized loads take one group");
-        load_group<FAM>(src, all);
-    }
+    load_unit<FAM, NG, WIDE>(src, all);
     unsigned r[NPIX / CH][CH], g[NPIX / CH][CH], b[NPIX / CH][CH];
 #pragma unroll
     for (int gi = 0; gi < NG; ++gi) {
@@ -148,138 +174,20 @@ __device__ __forceinline__ void packed_unit(const unsigned char* src, unsigned c
     }
 }
 
-// grid: x strides over the frame's units (units_x per row, H rows), y strides over the frames, as in yuv_frames.  Every
-// index is derived from T, H, W and the strides the host has checked against them.  VEC: the first units_vec units of a row
-// are eight pixels (v210: 24); v210 rows whose width is no multiple of 24 end in units of one group.
-template <int FAM, int FORM, class PX>
-__device__ __forceinline__ void packed_frames(const tdc_yuv_packed& p, const packed_lay& l, const tdc_yuv_coef& c, const depth& d,
-                                              const PX& px, int T, int H, int W, int units_x, int units_vec, unsigned char* rgb) {
-    constexpr int P = fam_px(FAM), GB = fam_gw(FAM) * 4;
-    constexpr int NG = FAM == FV210 ? 4 : 8 / P;          // groups per vector unit
-    const long long units = (long long)units_x * H;       // < 2^32: units_x and H are at most 65535
-    for (int t = blockIdx.y; t < T; t += gridDim.y) {
-        const unsigned char* sf = p.base + (long long)t * p.frame;
-        unsigned char* of = rgb + (long long)t * H * W * 3;
-        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < units; i += (long long)gridDim.x * 256) {
-            // v210 VEC: the frame's vector units come first and its group units after them, so that the two kinds share one wave only once
-            const bool tail = FAM == FV210 && FORM == VEC && i >= (long long)units_vec * H;
-            const unsigned per_row = FAM == FV210 && FORM == VEC ? (unsigned)(tail ? units_x - units_vec : units_vec) : (unsigned)units_x;
-            const unsigned j = (unsigned)(tail ? i - (long long)units_vec * H : i);     // i < 2^32: 32-bit divisions
-            const unsigned row_ = j / per_row;
-            const int row = (int)row_, xu = (int)(j - row_ * per_row);
-            const unsigned char* srow = sf + (long long)row * p.pitch;
-            unsigned char* orow = of + (long long)row * W * 3;
-            if constexpr (FORM == GROUP) {
-                packed_unit<FAM, 1, false>(srow + (long long)xu * GB, orow, xu * P, W, l, c, d, px);
-            } else if constexpr (FAM == FV210) {
-                if (!tail) {
-                    packed_unit<FAM, NG, true>(srow + (long long)xu * (NG * GB), orow, xu * (NG * P), W, l, c, d, px);
-                } else {
-                    const int gi = units_vec * NG + xu;
-                    packed_unit<FAM, 1, true>(srow + (long long)gi * GB, orow, gi * P, W, l, c, d, px);
-                }
-            } else {
-                packed_unit<FAM, NG, true>(srow + (long long)xu * (NG * GB), orow, xu * (NG * P), W, l, c, d, px);
-            }
-        }
+
+// What the walk calls for a unit: per_thread() once before the loops, unit() per unit.
+// replicated chroma: a pixel takes the pair of its own group (v210: of its two pixels); nothing outside the unit is read
+struct replicated {
+    __device__ __forceinline__ int per_thread() const { return 0; }
+    template <int FAM, int NG, bool WIDE, class PX>
+    __device__ __forceinline__ void unit(int, const unsigned char* srow, const unsigned char* src, unsigned char* orow, int x0, int W,
+                                         const packed_lay& l, const tdc_yuv_coef& c, const depth& d, const PX& px) const {
+        packed_unit<FAM, NG, WIDE>(src, orow, x0, W, l, c, d, px);
     }
-}
-
-template <int FAM, int FORM>
-__global__ __launch_bounds__(256) void yuv_packed_to_rgb_kernel(tdc_yuv_packed p, packed_lay l, tdc_yuv_coef c, int T, int H, int W,
-                                                                int units_x, int units_vec, unsigned char* rgb) {
-    packed_frames<FAM, FORM>(p, l, c, depth_of(p.bits, p.msb_aligned, 8), sdr_pixel(), T, H, W, units_x, units_vec, rgb);
-}
-
-template <int FAM, int FORM>
-__global__ __launch_bounds__(256) void yuv_packed_hdr_to_rgb_kernel(tdc_yuv_packed p, packed_lay l, tdc_yuv_coef c, tdc_hdr_desc h,
-                                                                    int T, int H, int W, int units_x, int units_vec, unsigned char* rgb) {
-    extern __shared__ float lut[];      // 2^bits entries
-    stage_hdr_lut(lut, h, p.bits);
-    packed_frames<FAM, FORM>(p, l, c, depth_of(p.bits, p.msb_aligned, p.bits), hdr_pixel{h, lut}, T, H, W, units_x, units_vec, rgb);
-}
-
-struct packed_launch { int form, units_x, units_vec; dim3 grid; };
-
-template <int FAM, int FORM>
-void launch_form(const packed_launch& q, hipStream_t st, const tdc_yuv_packed& p, const packed_lay& l, const tdc_yuv_coef& c,
-                 const tdc_hdr_desc* h, int T, int H, int W, unsigned char* rgb) {
-    const dim3 block(256);
-    if constexpr (FAM != F422_8 && FAM != F444_8) {
-        if (h) {
-            hipLaunchKernelGGL((yuv_packed_hdr_to_rgb_kernel<FAM, FORM>), q.grid, block, sizeof(float) << p.bits, st, p, l, c, *h, T, H, W,
-                               q.units_x, q.units_vec, rgb);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((yuv_packed_to_rgb_kernel<FAM, FORM>), q.grid, block, 0, st, p, l, c, T, H, W, q.units_x, q.units_vec, rgb);
-}
-
-template <int FAM>
-void launch(const packed_launch& q, hipStream_t st, const tdc_yuv_packed& p, const packed_lay& l, const tdc_yuv_coef& c,
-            const tdc_hdr_desc* h, int T, int H, int W, unsigned char* rgb) {
-    if (q.form == VEC) return launch_form<FAM, VEC>(q, st, p, l, c, h, T, H, W, rgb);
-    launch_form<FAM, GROUP>(q, st, p, l, c, h, T, H, W, rgb);
-}
-
-inline int group_bytes(int family) { return 4 * fam_gw(family); }
-
-// everything tdc_yuv_packed_to_rgb refuses, before any launch
-inline bool packed_args_ok(const tdc_yuv_packed* p, const tdc_yuv_coef* c, const tdc_hdr_desc* h, int T, int H, int W,
-                           const unsigned char* rgb, packed_fmt& f) {
-    if (!p || !c || !rgb || !p->base) return false;
-    if (T < 1 || H < 1 || W < 1 || T > 65535 || H > 65535 || W > 65535) return false;
-    if (!packed_fmt_of(p->format, f)) return false;
-    const int ws = fam_ss(f.family);
-    if (ws == 1 ? p->bits != 8 : (ws == 2 ? p->bits != 10 && p->bits != 12 : p->bits != 10)) return false;
-    if ((p->msb_aligned != 0 && p->msb_aligned != 1) || (p->msb_aligned && ws != 2)) return false;
-    if (!aligned(p->base, ws) || p->pitch % ws || p->frame % ws) return false;
-    const long long row = (long long)((W + fam_px(f.family) - 1) / fam_px(f.family)) * group_bytes(f.family);    // the row's read set
-    if (p->pitch < row) return false;
-    if (T > 1 && p->frame < (long long)(H - 1) * p->pitch + row) return false;
-    if (!yuv_coef_ok(c, p->bits)) return false;
-    if (h && (p->bits == 8 || !hdr_desc_ok(h))) return false;
-    return true;
-}
-
-// the vector form: every 16-byte load and every 8-byte RGB store lands on its own alignment in every row of every frame.
-// v210: W % 8 == 0 puts every row and every 24-pixel unit of the output on an 8-byte boundary; what is left of a row after
-// its W / 24 vector units goes group by group.
-inline packed_launch packed_launch_of(const tdc_yuv_packed* p, int family, int T, int H, int W, const unsigned char* rgb) {
-    const int P = fam_px(family);
-    const bool vec = W % 8 == 0 && (family != FV210 || W >= 24) && aligned(p->base, 16) && multiple(p->pitch, 16) &&
-                     (T == 1 || multiple(p->frame, 16)) && aligned(rgb, 8);
-    int units_vec = 0, units_x = (W + P - 1) / P;
-    if (vec) {
-        units_vec = family == FV210 ? W / 24 : W / 8;
-        units_x = units_vec + (family == FV210 ? (W - 24 * units_vec + 5) / 6 : 0);
-    }
-    const long long units = (long long)units_x * H;
-    // memory-bound: about eight blocks per CU in flight, the rest by striding (as yuv_launch_of)
-    const int gx = (int)((units + 255) / 256 < 2048 ? (units + 255) / 256 : 2048);
-    const int gy = T < 2048 / gx ? T : (2048 / gx > 1 ? 2048 / gx : 1);
-    return {vec ? VEC : GROUP, units_x, units_vec, dim3(gx, gy)};
-}
-
-// ---- interpolated chroma: the 4:2:2 families ------------------------------------------------------
-// chroma pair k of a row, as single-sample loads (v210: the words that hold it; R = k % 3, its place in the group)
-template <int FAM, int R>
-__device__ __forceinline__ void pair_at(const unsigned char* srow, int k, const packed_lay& l, const depth& d, int& u, int& v) {
-    if constexpr (FAM == F422_8) {
-        const unsigned char* g = srow + 4ll * k;
-        u = (int)g[l.u]; v = (int)g[l.v];
-    } else if constexpr (FAM == F422_16) {
-        const unsigned char* g = srow + 8ll * k;
-        u = sample_at<2>(g + 2 * l.u, d); v = sample_at<2>(g + 2 * l.v, d);
-    } else {
-        const unsigned* g = reinterpret_cast<const unsigned*>(srow) + 4ll * (k / 3);
-        if constexpr (R == 0) { const unsigned w = g[0]; u = (int)(w & 1023u); v = (int)(w >> 20 & 1023u); }
-        else { u = (int)(g[2] >> 20 & 1023u); v = (int)(g[3] >> 10 & 1023u); }
-    }
-}
-
-// packed_unit with interpolated chroma: the unit's NG groups hold the pairs k0 .. k0 + NG * NC - 1 of the row at srow.  A
-// pair at or past Wc (the unused tail of the row's last group) is never used: the clamp is by index on the picture's Wc.
+};
+// packed_unit with interpolated chroma (the 4:2:2 families): the unit's NG groups hold the pairs k0 .. k0 + NG * NC - 1 of the
+// row at srow, and the pair left (centred siting) and right of them are single-sample loads.  A pair at or past Wc (the unused
+// tail of the row's last group) is never used: the clamp is by index on the picture's Wc.
 template <int FAM, int NG, bool WIDE, class PX>
 __device__ __forceinline__ void packed_linear_unit(const unsigned char* srow, const unsigned char* src, unsigned char* orow, int x0,
                                                    int W, const packed_lay& l, const tdc_yuv_coef& c, const depth& d, const PX& px,
@@ -346,19 +254,34 @@ __device__ __forceinline__ void packed_linear_unit(const unsigned char* srow, co
     }
 }
 
-// packed_frames with interpolated chroma: the same grid, units and order of units
-template <int FAM, int FORM, class PX>
-__device__ __forceinline__ void packed_linear_frames(const tdc_yuv_packed& p, const packed_lay& l, const tdc_yuv_coef& c, const depth& d,
-                                                     const PX& px, const tdc_chroma_site& s, int T, int H, int W, int units_x,
-                                                     int units_vec, unsigned char* rgb) {
+
+// interpolated chroma: the taps of the horizontal axis once per thread
+struct interpolated_x {
+    tdc_chroma_site s;
+    __device__ __forceinline__ axis_taps per_thread() const { return axis_taps_of(s.sit_x, 1); }
+    template <int FAM, int NG, bool WIDE, class PX>
+    __device__ __forceinline__ void unit(const axis_taps& wx, const unsigned char* srow, const unsigned char* src, unsigned char* orow,
+                                         int x0, int W, const packed_lay& l, const tdc_yuv_coef& c, const depth& d, const PX& px) const {
+        packed_linear_unit<FAM, NG, WIDE>(srow, src, orow, x0, W, l, c, d, px, wx);
+    }
+};
+
+// grid: x strides over the frame's units (units_x per row, H rows), y strides over the frames, as in yuv_frames.  Every
+// index is derived from T, H, W and the strides the host has checked against them.  VEC: the first units_vec units of a row
+// are eight pixels (v210: 24); v210 rows whose width is no multiple of 24 end in units of one group.
+template <int FAM, int FORM, class CH, class PX>
+__device__ __forceinline__ void packed_frames(const tdc_yuv_packed& p, const packed_lay& l, const tdc_yuv_coef& c, const depth& d,
+                                              const PX& px, const CH& ch, int T, int H, int W, int units_x, int units_vec,
+                                              unsigned char* rgb) {
     constexpr int P = fam_px(FAM), GB = fam_gw(FAM) * 4;
-    constexpr int NG = FAM == FV210 ? 4 : 8 / P;          // groups per vector unit
-    const axis_taps wx = axis_taps_of(s.sit_x, 1);
-    const long long units = (long long)units_x * H;       // < 2^32: units_x and H are at most 65535
+    constexpr int NG = FAM == FV210 ? 4 : 8 / P;                // groups per vector unit
+    const auto pt = ch.per_thread();
+    const long long units = (long long)units_x * H;             // < 2^32: units_x and H are at most 65535
     for (int t = blockIdx.y; t < T; t += gridDim.y) {
         const unsigned char* sf = p.base + (long long)t * p.frame;
         unsigned char* of = rgb + (long long)t * H * W * 3;
-        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < units; i += (long long)gridDim.x * 256) {
+        for (long long i = first_unit(); i < units; i += unit_stride()) {
+            // v210 VEC: the frame's vector units come first and its group units after them, so that the two kinds share one wave only once
             const bool tail = FAM == FV210 && FORM == VEC && i >= (long long)units_vec * H;
             const unsigned per_row = FAM == FV210 && FORM == VEC ? (unsigned)(tail ? units_x - units_vec : units_vec) : (unsigned)units_x;
             const unsigned j = (unsigned)(tail ? i - (long long)units_vec * H : i);     // i < 2^32: 32-bit divisions
@@ -367,55 +290,94 @@ __device__ __forceinline__ void packed_linear_frames(const tdc_yuv_packed& p, co
             const unsigned char* srow = sf + (long long)row * p.pitch;
             unsigned char* orow = of + (long long)row * W * 3;
             if constexpr (FORM == GROUP) {
-                packed_linear_unit<FAM, 1, false>(srow, srow + (long long)xu * GB, orow, xu * P, W, l, c, d, px, wx);
+                ch.template unit<FAM, 1, false>(pt, srow, srow + (long long)xu * GB, orow, xu * P, W, l, c, d, px);
             } else if constexpr (FAM == FV210) {
                 if (!tail) {
-                    packed_linear_unit<FAM, NG, true>(srow, srow + (long long)xu * (NG * GB), orow, xu * (NG * P), W, l, c, d, px, wx);
+                    ch.template unit<FAM, NG, true>(pt, srow, srow + (long long)xu * (NG * GB), orow, xu * (NG * P), W, l, c, d, px);
                 } else {
                     const int gi = units_vec * NG + xu;
-                    packed_linear_unit<FAM, 1, true>(srow, srow + (long long)gi * GB, orow, gi * P, W, l, c, d, px, wx);
+                    ch.template unit<FAM, 1, true>(pt, srow, srow + (long long)gi * GB, orow, gi * P, W, l, c, d, px);
                 }
             } else {
-                packed_linear_unit<FAM, NG, true>(srow, srow + (long long)xu * (NG * GB), orow, xu * (NG * P), W, l, c, d, px, wx);
+                ch.template unit<FAM, NG, true>(pt, srow, srow + (long long)xu * (NG * GB), orow, xu * (NG * P), W, l, c, d, px);
             }
         }
     }
 }
 
-template <int FAM, int FORM>
-__global__ __launch_bounds__(256) void yuv_packed_linear_to_rgb_kernel(tdc_yuv_packed p, packed_lay l, tdc_yuv_coef c, tdc_chroma_site s,
-                                                                       int T, int H, int W, int units_x, int units_vec, unsigned char* rgb) {
-    packed_linear_frames<FAM, FORM>(p, l, c, depth_of(p.bits, p.msb_aligned, 8), sdr_pixel(), s, T, H, W, units_x, units_vec, rgb);
+// S: nothing for the replicate kernels, the chroma site for the interpolating ones, where the kernels have always taken it
+template <int FAM, int FORM, class CH, class... S>
+__global__ __launch_bounds__(256) void yuv_packed_to_rgb_kernel(tdc_yuv_packed p, packed_lay l, tdc_yuv_coef c, S... s, int T, int H,
+                                                                int W, int units_x, int units_vec, unsigned char* rgb) {
+    packed_frames<FAM, FORM>(p, l, c, depth_of(p.bits, p.msb_aligned, 8), sdr_pixel(), CH{s...}, T, H, W, units_x, units_vec, rgb);
 }
 
-template <int FAM, int FORM>
-__global__ __launch_bounds__(256) void yuv_packed_linear_hdr_to_rgb_kernel(tdc_yuv_packed p, packed_lay l, tdc_yuv_coef c, tdc_hdr_desc h,
-                                                                           tdc_chroma_site s, int T, int H, int W, int units_x,
-                                                                           int units_vec, unsigned char* rgb) {
+template <int FAM, int FORM, class CH, class... S>
+__global__ __launch_bounds__(256) void yuv_packed_hdr_to_rgb_kernel(tdc_yuv_packed p, packed_lay l, tdc_yuv_coef c, tdc_hdr_desc h, S... s,
+                                                                    int T, int H, int W, int units_x, int units_vec, unsigned char* rgb) {
     extern __shared__ float lut[];      // 2^bits entries
     stage_hdr_lut(lut, h, p.bits);
-    packed_linear_frames<FAM, FORM>(p, l, c, depth_of(p.bits, p.msb_aligned, p.bits), hdr_pixel{h, lut}, s, T, H, W, units_x, units_vec, rgb);
+    packed_frames<FAM, FORM>(p, l, c, depth_of(p.bits, p.msb_aligned, p.bits), hdr_pixel{h, lut}, CH{s...}, T, H, W, units_x, units_vec,
+                             rgb);
 }
 
-template <int FAM, int FORM>
-void launch_linear_form(const packed_launch& q, hipStream_t st, const tdc_yuv_packed& p, const packed_lay& l, const tdc_yuv_coef& c,
-                        const tdc_hdr_desc* h, const tdc_chroma_site& s, int T, int H, int W, unsigned char* rgb) {
+struct packed_launch { int form, units_x, units_vec; dim3 grid; };
+
+template <int FAM, int FORM, class CH, class... S>
+void launch_form(const packed_launch& q, hipStream_t st, const tdc_yuv_packed& p, const packed_lay& l, const tdc_yuv_coef& c,
+                 const tdc_hdr_desc* h, int T, int H, int W, unsigned char* rgb, const S&... s) {
     const dim3 block(256);
-    if constexpr (FAM != F422_8) {
+    if constexpr (fam_ss(FAM) != 1) {       // the families that hold more than 8 bits
         if (h) {
-            hipLaunchKernelGGL((yuv_packed_linear_hdr_to_rgb_kernel<FAM, FORM>), q.grid, block, sizeof(float) << p.bits, st, p, l, c, *h, s,
-                               T, H, W, q.units_x, q.units_vec, rgb);
+            hipLaunchKernelGGL((yuv_packed_hdr_to_rgb_kernel<FAM, FORM, CH, S...>), q.grid, block, sizeof(float) << p.bits, st, p, l, c, *h,
+                               s..., T, H, W, q.units_x, q.units_vec, rgb);
             return;
         }
     }
-    hipLaunchKernelGGL((yuv_packed_linear_to_rgb_kernel<FAM, FORM>), q.grid, block, 0, st, p, l, c, s, T, H, W, q.units_x, q.units_vec, rgb);
+    hipLaunchKernelGGL((yuv_packed_to_rgb_kernel<FAM, FORM, CH, S...>), q.grid, block, 0, st, p, l, c, s..., T, H, W, q.units_x, q.units_vec,
+                       rgb);
 }
 
-template <int FAM>
-void launch_linear(const packed_launch& q, hipStream_t st, const tdc_yuv_packed& p, const packed_lay& l, const tdc_yuv_coef& c,
-                   const tdc_hdr_desc* h, const tdc_chroma_site& s, int T, int H, int W, unsigned char* rgb) {
-    if (q.form == VEC) return launch_linear_form<FAM, VEC>(q, st, p, l, c, h, s, T, H, W, rgb);
-    launch_linear_form<FAM, GROUP>(q, st, p, l, c, h, s, T, H, W, rgb);
+template <int FAM, class CH, class... S>
+void launch(const packed_launch& q, hipStream_t st, const tdc_yuv_packed& p, const packed_lay& l, const tdc_yuv_coef& c,
+            const tdc_hdr_desc* h, int T, int H, int W, unsigned char* rgb, const S&... s) {
+    if (q.form == VEC) return launch_form<FAM, VEC, CH>(q, st, p, l, c, h, T, H, W, rgb, s...);
+    launch_form<FAM, GROUP, CH>(q, st, p, l, c, h, T, H, W, rgb, s...);
+}
+
+inline int group_bytes(int family) { return 4 * fam_gw(family); }
+
+// everything tdc_yuv_packed_to_rgb refuses, before any launch
+inline bool packed_args_ok(const tdc_yuv_packed* p, const tdc_yuv_coef* c, const tdc_hdr_desc* h, int T, int H, int W,
+                           const unsigned char* rgb, packed_fmt& f) {
+    if (!p || !c || !rgb || !p->base) return false;
+    if (T < 1 || H < 1 || W < 1 || T > 65535 || H > 65535 || W > 65535) return false;
+    if (!packed_fmt_of(p->format, f)) return false;
+    const int ws = fam_ss(f.family);
+    if (ws == 1 ? p->bits != 8 : (ws == 2 ? p->bits != 10 && p->bits != 12 : p->bits != 10)) return false;
+    if ((p->msb_aligned != 0 && p->msb_aligned != 1) || (p->msb_aligned && ws != 2)) return false;
+    if (!aligned(p->base, ws) || p->pitch % ws || p->frame % ws) return false;
+    const long long row = (long long)((W + fam_px(f.family) - 1) / fam_px(f.family)) * group_bytes(f.family);    // the row's read set
+    if (p->pitch < row) return false;
+    if (T > 1 && p->frame < (long long)(H - 1) * p->pitch + row) return false;
+    if (!yuv_coef_ok(c, p->bits)) return false;
+    if (h && (p->bits == 8 || !hdr_desc_ok(h))) return false;
+    return true;
+}
+
+// the vector form: every 16-byte load and every 8-byte RGB store lands on its own alignment in every row of every frame.
+// v210: W % 8 == 0 puts every row and every 24-pixel unit of the output on an 8-byte boundary; what is left of a row after
+// its W / 24 vector units goes group by group.
+inline packed_launch packed_launch_of(const tdc_yuv_packed* p, int family, int T, int H, int W, const unsigned char* rgb) {
+    const int P = fam_px(family);
+    const bool vec = W % 8 == 0 && (family != FV210 || W >= 24) && aligned(p->base, 16) && multiple(p->pitch, 16) &&
+                     (T == 1 || multiple(p->frame, 16)) && aligned(rgb, 8);
+    int units_vec = 0, units_x = (W + P - 1) / P;
+    if (vec) {
+        units_vec = family == FV210 ? W / 24 : W / 8;
+        units_x = units_vec + (family == FV210 ? (W - 24 * units_vec + 5) / 6 : 0);
+    }
+    return {vec ? VEC : GROUP, units_x, units_vec, stream_grid((long long)units_x * H, T)};
 }
 
 }  // namespace
@@ -427,12 +389,12 @@ extern "C" int tdc_yuv_packed_to_rgb(const tdc_yuv_packed* p, const tdc_yuv_coef
     const packed_launch q = packed_launch_of(p, f.family, T, H, W, rgb);
     hipStream_t st = (hipStream_t)stream;
     switch (f.family) {
-        case F422_8: launch<F422_8>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
-        case F422_16: launch<F422_16>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
-        case F444_8: launch<F444_8>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
-        case F444_16: launch<F444_16>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
-        case F410: launch<F410>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
-        default: launch<FV210>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
+        case F422_8: launch<F422_8, replicated>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
+        case F422_16: launch<F422_16, replicated>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
+        case F444_8: launch<F444_8, replicated>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
+        case F444_16: launch<F444_16, replicated>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
+        case F410: launch<F410, replicated>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
+        default: launch<FV210, replicated>(q, st, *p, f.lay, *c, h, T, H, W, rgb); break;
     }
     return (int)hipGetLastError();
 }
@@ -445,9 +407,9 @@ extern "C" int tdc_yuv_packed_linear_to_rgb(const tdc_yuv_packed* p, const tdc_y
     const packed_launch q = packed_launch_of(p, f.family, T, H, W, rgb);
     hipStream_t st = (hipStream_t)stream;
     switch (f.family) {
-        case F422_8: launch_linear<F422_8>(q, st, *p, f.lay, *c, h, *s, T, H, W, rgb); break;
-        case F422_16: launch_linear<F422_16>(q, st, *p, f.lay, *c, h, *s, T, H, W, rgb); break;
-        default: launch_linear<FV210>(q, st, *p, f.lay, *c, h, *s, T, H, W, rgb); break;
+        case F422_8: launch<F422_8, interpolated_x>(q, st, *p, f.lay, *c, h, T, H, W, rgb, *s); break;
+        case F422_16: launch<F422_16, interpolated_x>(q, st, *p, f.lay, *c, h, T, H, W, rgb, *s); break;
+        default: launch<FV210, interpolated_x>(q, st, *p, f.lay, *c, h, T, H, W, rgb, *s); break;
     }
     return (int)hipGetLastError();
 }

@@ -1,7 +1,9 @@
-// YUV -> RGB for every surface the 8-bit 4:2:0 kernel of yuv.hip does not take: 8, 10 or 12 significant
-// bits (bytes, or little-endian 16-bit words aligned to either end), 4:2:0, 4:2:2 or 4:4:4, planar or interleaved chroma in
-// either order.  The conversion is the stated fixed-point formula of include/tdc_hip.h, section 19's with s = bits - 8 more
-// bits in the samples, the rounding term and the shift; replicated chroma; no library's converter and no transfer function.
+// YUV -> RGB for planar and semi-planar surfaces (DESIGN.md sections 19 and 20): 8, 10 or 12 significant bits (bytes, or
+// little-endian 16-bit words aligned to either end), 4:2:0, 4:2:2 or 4:4:4, planar or interleaved chroma in either order.
+// tdc_yuv420_to_rgb (NV12 / NV21 / I420, yuv.hip) is tdc_yuv_to_rgb at bits = 8, 4:2:0 on the host - the same refusals, choice
+// of form and grid, through yuv_samples.h - in front of a kernel of its own.  The conversion is the stated fixed-point
+// formula of include/tdc_hip.h, section 19's with s = bits - 8 more bits in the samples, the rounding term and the shift;
+// replicated chroma; no library's converter and no transfer function.
 // HBM-bound sample work: a thread owns a block (1 + sub_y) rows high, so a chroma sample is loaded once.  Two forms of ONE
 // kernel, chosen on the host from alignment facts alone:
 //   WORD    (1 + sub_y) x (1 + sub_x) pixels per thread, one sample per load, byte stores: any width, any pitch, any view
@@ -20,12 +22,11 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(tdc_yuv_planes p, tdc_y
 }
 
 template <int BS, int SUBX>
-void launch(int form, dim3 grid, hipStream_t st, const tdc_yuv_planes& p, const tdc_yuv_coef& c, int T, int H, int W, int units_x,
-            int u_is_high, unsigned char* rgb) {
-    const dim3 block(256);
-    if (form == WORD) hipLaunchKernelGGL((yuv_to_rgb_kernel<BS, SUBX, WORD>), grid, block, 0, st, p, c, T, H, W, units_x, 0, rgb);
-    else if (form == VEC_PLANAR) hipLaunchKernelGGL((yuv_to_rgb_kernel<BS, SUBX, VEC_PLANAR>), grid, block, 0, st, p, c, T, H, W, units_x, 0, rgb);
-    else hipLaunchKernelGGL((yuv_to_rgb_kernel<BS, SUBX, VEC_PAIRED>), grid, block, 0, st, p, c, T, H, W, units_x, u_is_high, rgb);
+void launch(const yuv_launch& l, hipStream_t st, const tdc_yuv_planes& p, const tdc_yuv_coef& c, int T, int H, int W, unsigned char* rgb) {
+    with_form(l.form, [&](auto form) {
+        hipLaunchKernelGGL((yuv_to_rgb_kernel<BS, SUBX, decltype(form)::value>), l.grid, dim3(256), 0, st, p, c, T, H, W, l.units_x,
+                           l.u_is_high, rgb);
+    });
 }
 
 }  // namespace
@@ -34,12 +35,10 @@ extern "C" int tdc_yuv_to_rgb(const tdc_yuv_planes* p, const tdc_yuv_coef* c, in
                               void* stream) {
     if (!yuv_args_ok(p, c, T, H, W, rgb)) return TDC_E_BADARG;
     const yuv_launch l = yuv_launch_of(p, T, H, W, rgb);
-    const int bs = p->bits == 8 ? 1 : 2, form = l.form, units_x = l.units_x, u_is_high = l.u_is_high;
-    const dim3 grid = l.grid;
     hipStream_t st = (hipStream_t)stream;
-    if (bs == 1 && p->sub_x == 1) launch<1, 1>(form, grid, st, *p, *c, T, H, W, units_x, u_is_high, rgb);
-    else if (bs == 1) launch<1, 0>(form, grid, st, *p, *c, T, H, W, units_x, u_is_high, rgb);
-    else if (p->sub_x == 1) launch<2, 1>(form, grid, st, *p, *c, T, H, W, units_x, u_is_high, rgb);
-    else launch<2, 0>(form, grid, st, *p, *c, T, H, W, units_x, u_is_high, rgb);
+    if (p->bits == 8 && p->sub_x == 1) launch<1, 1>(l, st, *p, *c, T, H, W, rgb);
+    else if (p->bits == 8) launch<1, 0>(l, st, *p, *c, T, H, W, rgb);
+    else if (p->sub_x == 1) launch<2, 1>(l, st, *p, *c, T, H, W, rgb);
+    else launch<2, 0>(l, st, *p, *c, T, H, W, rgb);
     return (int)hipGetLastError();
 }

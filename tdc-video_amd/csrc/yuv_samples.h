@@ -1,10 +1,14 @@
-// What yuv_planes.hip (tdc_yuv_to_rgb) and yuv_hdr.hip (tdc_yuv_hdr_to_rgb) share: the sample extraction of DESIGN.md section
-// 20 (bytes, or little-endian 16-bit words with the sample masked out of either end), the integer accumulators of the stated
-// formula with the clamp taken before the shift, the kernel body in its two forms (yuv_frames: which thread owns which pixels,
-// what it loads and how it stores) with the one thing the kernels differ in - what a pixel's three accumulators become - as a
-// functor, and on the host the refusals of a tdc_yuv_planes / tdc_yuv_coef pair and the choice between the one-sample form
-// and the 8-pixel vector form from alignment facts alone.
+// What the YUV -> RGB kernels share.  On the device: the sample extraction of DESIGN.md section 20 (bytes, or little-endian
+// 16-bit words with the sample masked out of either end), the integer accumulators of the stated formula with the clamp taken
+// before the shift, and the planar kernel body in pieces - which thread owns which pixels (yuv_unit_of), how it loads its run
+// of chroma samples (chroma_run) and how a pixel row is loaded and stored (emit_row) - under yuv_frames (replicated chroma:
+// yuv_planes.hip, yuv_hdr.hip) and yuv_linear_frames (yuv_linear.hip), with what a pixel's three accumulators become as a
+// functor.  On the host, for every planar entry (tdc_yuv420_to_rgb of yuv.hip included): the refusals of a tdc_yuv_planes /
+// tdc_yuv_coef pair, the choice between the one-sample form and the 8-pixel vector form from alignment facts alone, the grid
+// every kernel of the family takes (stream_grid) and the run-time form as a template argument (with_form).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 #include "../../include/tdc_hip.h"
 
@@ -73,7 +77,7 @@ __device__ __forceinline__ int sample_at(const unsigned char* p, const depth& d)
 }
 
 // four pixels = 12 bytes = three words, twice: eight pixels of one row as three 8-byte words
-__device__ __forceinline__ void pack_row8(const unsigned (&r)[8], const unsigned (&g)[8], const unsigned (&b)[8], uint2 (&o)[3]) {
+__device__ __forceinline__ void pack_row8(const unsigned* r, const unsigned* g, const unsigned* b, uint2 (&o)[3]) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int i = 4 * h;
@@ -99,79 +103,108 @@ __device__ __forceinline__ void row8(const tdc_yuv_coef& c, const depth& d, cons
     pack_row8(r, g, b, o);
 }
 
-// grid: x strides over the frame's units (a unit = one thread's block; units_x per block row, Hc block rows), y strides
-// over the frames.  Every index is derived from T, H, W and the strides the host has checked against them.
-// px(d, accR, accG, accB, r, g, b) turns a pixel's three accumulators into its bytes: the one place the two kernels differ.
+// The walk every planar kernel takes.  grid: x strides over the frame's units (a unit = one thread's block; units_x per
+// block row, Hc block rows), y strides over the frames:
+//     for (int t = blockIdx.y; t < T; t += gridDim.y)
+//         for (long long i = first_unit(); i < units; i += unit_stride()) { const yuv_unit n = yuv_unit_of(p, t, i, ...); ... }
+// Every index is derived from T, H, W and the strides the host has checked against them.
+struct yuv_unit {
+    const unsigned char *uf, *vf;   // the frame's chroma planes
+    const unsigned char* yr;        // the unit's first luma row
+    unsigned char* orow;            // the unit's first output row
+    int yc, xu;                     // its chroma row and its place in it
+    bool two_rows;                  // 4:2:0 and not the last block of an odd H
+};
+
+__device__ __forceinline__ long long first_unit() { return (long long)blockIdx.x * 256 + threadIdx.x; }
+__device__ __forceinline__ long long unit_stride() { return (long long)gridDim.x * 256; }
+
+// units per frame: < 2^32, units_x and Hc are at most 65535
+__device__ __forceinline__ long long yuv_units(const tdc_yuv_planes& p, int H, int units_x) {
+    return (long long)units_x * ((H + p.sub_y) >> p.sub_y);
+}
+
+__device__ __forceinline__ yuv_unit yuv_unit_of(const tdc_yuv_planes& p, int t, long long i, int units_x, int H, int W, unsigned char* rgb) {
+    const unsigned yc_ = (unsigned)i / (unsigned)units_x;     // i < 2^32: a 32-bit division
+    const int yc = (int)yc_, xu = (int)((unsigned)i - yc_ * (unsigned)units_x);
+    const int y0 = yc << p.sub_y;
+    return {p.u + (long long)t * p.c_frame, p.v + (long long)t * p.c_frame, p.y + (long long)t * p.y_frame + (long long)y0 * p.y_pitch,
+            rgb + (long long)t * H * W * 3 + (long long)y0 * W * 3, yc, xu, p.sub_y && y0 + 1 < H};
+}
+
+// the NC chroma samples of unit xu in the chroma row at byte offset crow: WORD one sample per load (NC = 1), VEC_PLANAR one
+// load per plane, VEC_PAIRED the NC pairs at the lower pointer (u_is_high: the pairs are (v, u))
+template <int BS, int NC, int FORM>
+__device__ __forceinline__ void chroma_run(const tdc_yuv_planes& p, const unsigned char* uf, const unsigned char* vf, long long crow,
+                                           int xu, const depth& d, int u_is_high, int* su, int* sv) {
+    if constexpr (FORM == WORD) {
+        const long long coff = crow + (long long)xu * p.c_step;
+        su[0] = sample_at<BS>(uf + coff, d);
+        sv[0] = sample_at<BS>(vf + coff, d);
+    } else if constexpr (FORM == VEC_PLANAR) {
+        unsigned uw[NC * BS / 4], vw[NC * BS / 4];
+        load_words<NC * BS>(uf + crow + (long long)xu * (NC * BS), uw);
+        load_words<NC * BS>(vf + crow + (long long)xu * (NC * BS), vw);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) { su[k] = sample<BS>(uw, k, d); sv[k] = sample<BS>(vw, k, d); }
+    } else {
+        unsigned pw[2 * NC * BS / 4];
+        load_words<2 * NC * BS>((u_is_high ? vf : uf) + crow + (long long)xu * (2 * NC * BS), pw);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            const int first = sample<BS>(pw, 2 * k, d), second = sample<BS>(pw, 2 * k + 1, d);
+            su[k] = u_is_high ? second : first;
+            sv[k] = u_is_high ? first : second;
+        }
+    }
+}
+
+// one pixel row of a unit, from its luma row and the chroma terms of its pixels (pixel k takes ct[k >> CSH]) to its bytes:
+// WORD its NPX pixels, one sample per load and byte stores below W; the vector forms eight pixels, one luma load and three
+// 8-byte stores.  px(d, accR, accG, accB, r, g, b) turns a pixel's three accumulators into its bytes.
+template <int BS, int CSH, int FORM, int NPX, class PX>
+__device__ __forceinline__ void emit_row(const tdc_yuv_coef& c, const depth& d, const PX& px, const unsigned char* yrow, unsigned char* orow,
+                                         int xu, int W, const chroma_terms (&ct)[(FORM == WORD ? NPX : 8) >> CSH]) {
+    if constexpr (FORM == WORD) {
+        const int x0 = xu * NPX;
+#pragma unroll
+        for (int dx = 0; dx < NPX; ++dx) {
+            if (dx == 1 && x0 + 1 >= W) break;      // odd W: the last column has one pixel
+            const int yy = c.cy * (sample_at<BS>(yrow + (long long)(x0 + dx) * BS, d) - c.y_off);
+            const chroma_terms& k = ct[dx >> CSH];
+            unsigned char* o = orow + (long long)(x0 + dx) * 3;
+            unsigned r, g, b;
+            px(d, yy + k.r, yy + k.g, yy + k.b, r, g, b);
+            o[0] = (unsigned char)r; o[1] = (unsigned char)g; o[2] = (unsigned char)b;
+        }
+    } else {
+        unsigned lw[2 * BS];
+        uint2 o[3];
+        load_words<8 * BS>(yrow + (long long)xu * (8 * BS), lw);
+        row8<BS, CSH>(c, d, px, lw, ct, o);
+        uint2* dst = reinterpret_cast<uint2*>(orow + 24ll * xu);
+        dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+    }
+}
+
+// replicated chroma: a thread owns (1 + sub_y) x (1 + SUBX) pixels (WORD) or (1 + sub_y) x 8 (the vector forms), so a chroma
+// sample is loaded once
 template <int BS, int SUBX, int FORM, class PX>
 __device__ __forceinline__ void yuv_frames(const tdc_yuv_planes& p, const tdc_yuv_coef& c, const depth& d, const PX& px, int T, int H,
                                            int W, int units_x, int u_is_high, unsigned char* rgb) {
-    const int suby = p.sub_y;
-    const int Hc = (H + suby) >> suby;
-    const long long units = (long long)units_x * Hc;     // < 2^32: units_x and Hc are at most 65535
-    for (int t = blockIdx.y; t < T; t += gridDim.y) {
-        const unsigned char* yf = p.y + (long long)t * p.y_frame;
-        const unsigned char* uf = p.u + (long long)t * p.c_frame;
-        const unsigned char* vf = p.v + (long long)t * p.c_frame;
-        unsigned char* of = rgb + (long long)t * H * W * 3;
-        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < units; i += (long long)gridDim.x * 256) {
-            const unsigned yc_ = (unsigned)i / (unsigned)units_x;     // i < 2^32: a 32-bit division
-            const int yc = (int)yc_, xu = (int)((unsigned)i - yc_ * (unsigned)units_x);
-            const int y0 = yc << suby;
-            const bool two_rows = suby && y0 + 1 < H;   // 4:2:0 with odd H: the last block has one row
-            const unsigned char* yr = yf + (long long)y0 * p.y_pitch;
-            const long long crow = (long long)yc * p.c_pitch;
-            unsigned char* orow = of + (long long)y0 * W * 3;
-            if (FORM == WORD) {
-                const int x0 = xu << SUBX;
-                const bool two_cols = SUBX && x0 + 1 < W;   // odd W: the last column has one pixel
-                const long long coff = crow + (long long)xu * p.c_step;
-                const chroma_terms k = chroma(c, d, sample_at<BS>(uf + coff, d), sample_at<BS>(vf + coff, d));
+    constexpr int NC = FORM == WORD ? 1 : 8 >> SUBX;    // chroma samples of the unit's columns
+    const long long units = yuv_units(p, H, units_x);
+    for (int t = blockIdx.y; t < T; t += gridDim.y)
+        for (long long i = first_unit(); i < units; i += unit_stride()) {
+            const yuv_unit n = yuv_unit_of(p, t, i, units_x, H, W, rgb);
+            int su[NC], sv[NC];
+            chroma_run<BS, NC, FORM>(p, n.uf, n.vf, (long long)n.yc * p.c_pitch, n.xu, d, u_is_high, su, sv);
+            chroma_terms ct[NC];
 #pragma unroll
-                for (int dy = 0; dy < 2; ++dy) {
-                    if (dy == 1 && !two_rows) break;
-#pragma unroll
-                    for (int dx = 0; dx < 1 + SUBX; ++dx) {
-                        if (dx == 1 && !two_cols) break;
-                        const int yy = c.cy * (sample_at<BS>(yr + (long long)dy * p.y_pitch + (long long)(x0 + dx) * BS, d) - c.y_off);
-                        unsigned char* o = orow + ((long long)dy * W + x0 + dx) * 3;
-                        unsigned r, g, b;
-                        px(d, yy + k.r, yy + k.g, yy + k.b, r, g, b);
-                        o[0] = (unsigned char)r; o[1] = (unsigned char)g; o[2] = (unsigned char)b;
-                    }
-                }
-            } else {
-                constexpr int NC = 8 >> SUBX;       // chroma samples of the thread's eight columns
-                chroma_terms ct[NC];
-                if (FORM == VEC_PLANAR) {
-                    unsigned uw[NC * BS / 4], vw[NC * BS / 4];
-                    load_words<NC * BS>(uf + crow + (long long)xu * (NC * BS), uw);
-                    load_words<NC * BS>(vf + crow + (long long)xu * (NC * BS), vw);
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) ct[k] = chroma(c, d, sample<BS>(uw, k, d), sample<BS>(vw, k, d));
-                } else {            // NC pairs at the lower pointer; u_is_high: the pairs are (v, u)
-                    unsigned pw[2 * NC * BS / 4];
-                    load_words<2 * NC * BS>((u_is_high ? vf : uf) + crow + (long long)xu * (2 * NC * BS), pw);
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) {
-                        const int first = sample<BS>(pw, 2 * k, d), second = sample<BS>(pw, 2 * k + 1, d);
-                        ct[k] = chroma(c, d, u_is_high ? second : first, u_is_high ? first : second);
-                    }
-                }
-                unsigned lw[2 * BS];
-                uint2 o[3];
-                load_words<8 * BS>(yr + (long long)xu * (8 * BS), lw);
-                row8<BS, SUBX>(c, d, px, lw, ct, o);
-                uint2* dst = reinterpret_cast<uint2*>(orow + 24ll * xu);
-                dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
-                if (two_rows) {
-                    load_words<8 * BS>(yr + p.y_pitch + (long long)xu * (8 * BS), lw);
-                    row8<BS, SUBX>(c, d, px, lw, ct, o);
-                    dst = reinterpret_cast<uint2*>(orow + (long long)W * 3 + 24ll * xu);
-                    dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
-                }
-            }
+            for (int k = 0; k < NC; ++k) ct[k] = chroma(c, d, su[k], sv[k]);
+            emit_row<BS, SUBX, FORM, 1 + SUBX>(c, d, px, n.yr, n.orow, n.xu, W, ct);
+            if (n.two_rows) emit_row<BS, SUBX, FORM, 1 + SUBX>(c, d, px, n.yr + p.y_pitch, n.orow + (long long)W * 3, n.xu, W, ct);
         }
-    }
 }
 
 inline bool aligned(const void* p, unsigned a) { return ((unsigned long long)p & (a - 1)) == 0; }
@@ -210,6 +243,22 @@ inline bool yuv_args_ok(const tdc_yuv_planes* p, const tdc_yuv_coef* c, int T, i
     return yuv_coef_ok(c, p->bits);
 }
 
+// the grid of every kernel of the family, blocks of 256 threads over `units` units per frame and T frames.  Memory-bound:
+// about eight blocks per CU in flight, the rest by striding
+inline dim3 stream_grid(long long units, int T) {
+    const int gx = (int)((units + 255) / 256 < 2048 ? (units + 255) / 256 : 2048);
+    const int gy = T < 2048 / gx ? T : (2048 / gx > 1 ? 2048 / gx : 1);
+    return dim3(gx, gy);
+}
+
+// the run-time form as a template argument: f(std::integral_constant<int, FORM>())
+template <class F>
+void with_form(int form, const F& f) {
+    if (form == WORD) f(std::integral_constant<int, WORD>());
+    else if (form == VEC_PLANAR) f(std::integral_constant<int, VEC_PLANAR>());
+    else f(std::integral_constant<int, VEC_PAIRED>());
+}
+
 struct yuv_launch { int form, u_is_high, units_x; dim3 grid; };
 
 // the vector form: every luma load, chroma load and RGB store lands on its own alignment in every row of every frame
@@ -231,11 +280,7 @@ inline yuv_launch yuv_launch_of(const tdc_yuv_planes* p, int T, int H, int W, co
         }
     }
     const int units_x = form == WORD ? Wc : W / 8;
-    const long long units = (long long)units_x * Hc;
-    // memory-bound: about eight blocks per CU in flight, the rest by striding
-    const int gx = (int)((units + 255) / 256 < 2048 ? (units + 255) / 256 : 2048);
-    const int gy = T < 2048 / gx ? T : (2048 / gx > 1 ? 2048 / gx : 1);
-    return {form, u_is_high, units_x, dim3(gx, gy)};
+    return {form, u_is_high, units_x, stream_grid((long long)units_x * Hc, T)};
 }
 
 }  // namespace

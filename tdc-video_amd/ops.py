@@ -731,19 +731,9 @@ def yuv420_to_rgb(y, u, v, c_step, coef, H, W, out=None):
     [T, >= Hc, >= c_step * (Wc - 1) + 1] are uint8 views on the GPU with a dense last dimension whose strides carry the
     pitches and the frame strides; u and v share theirs.  c_step 1: two planes; c_step 2: interleaved samples, u and v views
     of one plane one byte apart.  coef = (y_off, cy, crv, cgu, cgv, cbu), e.g. preprocess.yuv_coefficients(...)."""
-    Hc, Wc = (H + 1) // 2, (W + 1) // 2
-    T = y.shape[0]
-    for t, rows, cols, name in ((y, H, W, "y"), (u, Hc, c_step * (Wc - 1) + 1, "u"), (v, Hc, c_step * (Wc - 1) + 1, "v")):
-        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.stride(2) == 1, "%s must be a uint8 [T, rows, bytes] CUDA view" % name
-        assert t.shape[0] == T and t.shape[1] >= rows and t.shape[2] >= cols, "%s %s is smaller than the frames" % (name, tuple(t.shape))
-    assert u.stride() == v.stride(), "u and v must share their strides"
-    if out is None:
-        out = torch.empty(T, H, W, 3, device=y.device, dtype=torch.uint8)
-    assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (T, H, W, 3) and out.is_contiguous()
-    # torch leaves the stride of a size-1 dimension arbitrary: one frame has no frame stride, one row the dense pitch
-    p = L.Yuv420Planes(y.data_ptr(), u.data_ptr(), v.data_ptr(), y.stride(0) if T > 1 else 0, u.stride(0) if T > 1 else 0,
-                       y.stride(1) if y.shape[1] > 1 else W, u.stride(1) if u.shape[1] > 1 else c_step * Wc, c_step)
-    L.check(L.load().tdc_yuv420_to_rgb(C.byref(p), C.byref(L.YuvCoef(*coef)), T, H, W, _ptr(out), _stream()), "tdc_yuv420_to_rgb")
+    q, out = _yuv_planes(y, u, v, c_step, H, W, 8, False, "420", out)
+    p = L.Yuv420Planes(*(getattr(q, name) for name, _ in L.Yuv420Planes._fields_))     # tdc_yuv_planes' first eight fields
+    L.check(L.load().tdc_yuv420_to_rgb(C.byref(p), C.byref(L.YuvCoef(*coef)), y.shape[0], H, W, _ptr(out), _stream()), "tdc_yuv420_to_rgb")
     return out
 
 
